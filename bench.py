@@ -16,7 +16,7 @@ A "step" is one pass of the hot path over one batch of synthetic input, entirely
 Timing.  W warm-up steps, then the timed block -- EXACTLY K steps enqueued through the pipelined driver (montecarlo.DeviceSimulator: rounds in
 flight, counters all-reduced on the stream, no host sync between kernels; where the decoder takes several steps per launch -- the erasure
 decoder: ldpc_simulate_rounds, one counter row per step -- up to 32 steps travel together), bracketed by barrier + torch.cuda.synchronize()
-on both sides, MAX over ranks -- is repeated `--repeats` times (default 5): `ms_per_step` / `value` are the MEDIAN block, the spread is
+on both sides, MAX over ranks -- is repeated `--repeats` times (default 1, with --full 5): `ms_per_step` / `value` are the MEDIAN block, the spread is
 reported beside them.  No per-kernel instrumentation runs inside a timed block; the per-kernel durations behind `roofline` come from a
 SEPARATE pass of the same launches with the library's HIP events on the decode stream (`ldpc_decoder_profile`).
 
@@ -28,15 +28,26 @@ Roofline.  `roofline.bound` / `binding_unit` name the resource that binds the do
                   each pass's own compulsory bytes (check pass s(2E+n), variable pass s(E+2n)); PMC traffic beside it.
 The 8(d) HBM-model figure of an LDS-resident kernel is kept as `hbm_model` (flagged: the messages never leave the CU, it bounds nothing).
 
+Plain run and --full.  `python bench.py --gpus N --steps K --warmup W` does only what the headline needs: set-up, W warm-up steps,
+ONE timed block of exactly K steps (`--repeats` defaults to 1), the JSON line.  `ms_per_step` is that block's wall time / K, so the whole run
+takes about (K + W) x ms_per_step plus its set-up.  Everything else this file measures -- the repeated blocks (`--repeats` defaults to 5),
+the per-kernel HIP-event pass behind `roofline`, the extra channel parameters under `points`, the side legs (streaming backend, decode from
+HBM, fp32 / exact-in-fp32 / fp16-storage modes), the CPU baselines and the `baseline_configs` block -- runs only with `--full`; without it
+those fields are null or absent.  `--dump-outputs DIR` writes what the timed path returned for its LAST timed step -- the whole-job counter
+row of DeviceSimulator.finish_round: DIR/counters.npy = [frames, word errors, bit errors, sweeps summed over frames] and
+DIR/sweep_histogram.npy = frames per sweep count (last bin: that many sweeps or more), float64.  The simulate path counts on the device and
+hands back only this row (no decisions are stored), so these are the arrays a caller of that path receives; the inputs (Philox noise keyed by seed, stream and
+global frame index) are the same in every run with the same arguments.
+
 Contract: python bench.py --gpus N --steps K --warmup W ; for N>1 one rank per GPU (RCCL) under torch.distributed.run -- started by the
 caller, or, when bench.py is started as a plain process (no WORLD_SIZE), by bench.py itself: the parent makes no GPU call, starts
 `python -m torch.distributed.run --nproc-per-node N ... bench.py <same argv>` as a child process and relays rank 0's line (self_launch);
 a node with fewer than N GPUs, or a WORLD_SIZE that is not N, ends with exit code 3 and NO line.  Frames sharded
 by global frame index, ONE all-reduce of the counters per step (per block of steps); rank 0 prints ONE JSON line.  The default command's
-line also carries `baseline_configs`: BASELINE configs 3-5 (sum-product / BSC, erasure decoder / BEC, n = 10 000, n = 64 800), a few steps
-each through the same run_bench, each with its own `roofline` and (N = 1) `cpu_baseline`.  Every line -- N > 1
-included -- carries `roofline` (rank 0's kernels), `cpu_baseline` (rank 0's host, timed BEFORE the process touches a GPU or joins the
-process group: the scipy leg forks one worker per hardware thread) and `collective` (backend + the number of ranks an all-reduce of ones saw).
+line run with --full also carries `baseline_configs`: BASELINE configs 3-5 (sum-product / BSC, erasure decoder / BEC, n = 10 000, n = 64 800), a few steps
+each through the same run_bench, each with its own `roofline` and (N = 1) `cpu_baseline`.  Every --full line -- N > 1
+included -- carries `roofline` (rank 0's kernels) and `cpu_baseline` (rank 0's host, timed BEFORE the process touches a GPU or joins the
+process group: the scipy leg forks one worker per hardware thread); every line carries `collective` (backend + the number of ranks an all-reduce of ones saw).
 `run_bench(args, comm, make_handle, device)` is the whole driver layer with the decoder handle injected -- tests/test_dist_cpu.py runs it on
 8 gloo ranks with a CPU stand-in for the handle; `main()` run as a script always builds the HIP handle.
 """
@@ -356,7 +367,8 @@ def _sync(device, torch):
 def run_point(sim, handle, comm, snr, steps, warmup, per_round, stream_id, torch, kernel_pass=True, repeats=1, device="cuda"):
     """`repeats` timed blocks of `steps` steps at one channel parameter (uninstrumented, pipelined), then -- separately -- the steps of one
     block again with the library's HIP-event kernel timing switched on.  `per_round` = frames of one step over ALL ranks (each rank
-    decodes its shard of the global frame range).  Returns dict(seconds (median block), blocks, counters (one block), profile)."""
+    decodes its shard of the global frame range).  Returns dict(seconds (median block), blocks, counters (one block), last (the counter
+    row of the last timed step), profile)."""
     frame0 = 0
     if kernel_pass:
         handle.set_profiling(False)
@@ -364,7 +376,7 @@ def run_point(sim, handle, comm, snr, steps, warmup, per_round, stream_id, torch
         sim.run_round(snr, stream_id, frame0, per_round)
         frame0 += per_round
     first = frame0
-    blocks, tot = [], None
+    blocks, tot, last = [], None, None
     rpl = sim.rounds_per_launch() if hasattr(sim, "rounds_per_launch") else 1
     for _rep in range(max(1, repeats)):
         frame0 = first  # every block decodes the same frames: identical work, identical counters
@@ -379,20 +391,26 @@ def run_point(sim, handle, comm, snr, steps, warmup, per_round, stream_id, torch
             left = steps
             while left > 0:
                 if len(inflight) == sim.DEPTH:
-                    tot += sim.finish_rounds(inflight.pop(0)).sum(axis=0)
+                    rows = sim.finish_rounds(inflight.pop(0))
+                    tot += rows.sum(axis=0)
+                    last = rows[-1]
                 r = min(rpl, left)
                 inflight.append(sim.launch_rounds(snr, stream_id, frame0, per_round, r))
                 frame0 += per_round * r
                 left -= r
             while inflight:
-                tot += sim.finish_rounds(inflight.pop(0)).sum(axis=0)
+                rows = sim.finish_rounds(inflight.pop(0))
+                tot += rows.sum(axis=0)
+                last = rows[-1]
         for _ in range(steps if rpl == 1 else 0):
             if len(inflight) == sim.DEPTH:
-                tot += sim.finish_round(inflight.pop(0))
+                last = sim.finish_round(inflight.pop(0))
+                tot += last
             inflight.append(sim.launch_round(snr, stream_id, frame0, per_round))
             frame0 += per_round
         while inflight:
-            tot += sim.finish_round(inflight.pop(0))
+            last = sim.finish_round(inflight.pop(0))
+            tot += last
         _sync(device, torch)
         comm.barrier()
         blocks.append(comm.max_float(time.perf_counter() - t0))
@@ -412,7 +430,7 @@ def run_point(sim, handle, comm, snr, steps, warmup, per_round, stream_id, torch
             left -= r
         prof = handle.read_profile(reset=True)
         handle.set_profiling(False)
-    return dict(seconds=statistics.median(blocks), blocks=blocks, counters=tot, profile=prof)
+    return dict(seconds=statistics.median(blocks), blocks=blocks, counters=tot, last=last, profile=prof)
 
 
 def committed(name):
@@ -506,6 +524,14 @@ def fused_roofline(kernel_name, frame_sweeps_per_s, cus, counters=None):
                 counters_stale=stale, counters_check=fresh_note)
 
 
+def dump_outputs(out_dir, last, hist_bins):
+    """--dump-outputs: the whole-job counter row of the last timed step, as float64 (every count is far below 2^53)."""
+    os.makedirs(out_dir, exist_ok=True)
+    row = np.asarray(last, dtype=np.float64)
+    np.save(os.path.join(out_dir, "counters.npy"), row[:4])
+    np.save(os.path.join(out_dir, "sweep_histogram.npy"), row[4:4 + hist_bins])
+
+
 def run_bench(args, comm, make_handle=None, device="cuda", cpu_base=None):
     """The benchmark driver: returns the result dict on rank 0 (None elsewhere).  `make_handle(code, alg, precision, backend)` builds
     the decoder handle (default: the HIP DecoderHandle -- no CPU path exists in the product).  `cpu_base`: rank 0's CPU baseline,
@@ -527,7 +553,7 @@ def run_bench(args, comm, make_handle=None, device="cuda", cpu_base=None):
     precision = "f32" if alg == "BEC" else ("f64" if alg == "ADMM" else args.precision)  # the erasure decoder has no floating-point state (2-bit messages in bit planes)
     if aux and make_handle is None:
         make_handle = lambda code_, alg_, prec_, backend_: AuxHandle(code_, alg_, prec_, channel)  # noqa: E731
-    points = args.points if args.points is not None else {"biawgn": [2.0, 3.0], "bsc": [0.05], "bec": [0.35]}[channel]
+    points = args.points if args.points is not None else {"biawgn": [2.0, 3.0], "bsc": [0.05], "bec": [0.35]}[channel] if args.full else []
     hist_bins = min(args.max_iter + 1, 60)  # the in-kernel histogram has 60 bins: sweeps >= 59 share the last one (reported on the line)
     msa_biawgn = alg == "MSA" and channel == "biawgn"
     if aux and args.points is None:
@@ -537,8 +563,8 @@ def run_bench(args, comm, make_handle=None, device="cuda", cpu_base=None):
     s = 8 if precision == "f64" else 4
     bytes_per_frame_iter = bytes_per_frame_sweep(code, alg, precision)  # SURVEY.md 8(d) for the LLR decoders
     f16 = precision == "f16"
-    side_legs = not args.no_profile and comm.world == 1 and device == "cuda" and not getattr(args, "headline_only", False) and not aux
-    kernel_pass = not args.no_profile and device == "cuda" and not aux
+    side_legs = args.full and not args.no_profile and comm.world == 1 and device == "cuda" and not getattr(args, "headline_only", False) and not aux
+    kernel_pass = args.full and not args.no_profile and device == "cuda" and not aux
     # frames of one step over all ranks: weak scaling (--batch frames per GPU, the default) or strong (--total-batch frames per step
     # whatever N is -- BASELINE configs 4 and 5 state their batch for the whole 8-GPU node; a total that N does not divide is split
     # as evenly as possible by Comm.shard)
@@ -547,6 +573,8 @@ def run_bench(args, comm, make_handle=None, device="cuda", cpu_base=None):
     rank_batch = comm.shard(0, per_round)[1]  # this rank's frames per step (rank 0: the largest shard)
 
     res = run_point(sim, handle, comm, param, args.steps, args.warmup, per_round, 0, torch, kernel_pass, args.repeats, device)
+    if args.dump_outputs and comm.is_root:
+        dump_outputs(args.dump_outputs, res["last"], hist_bins)
     backend_used, _ = handle.last_stats()
     extra = []
     for i, snr in enumerate(points):
@@ -649,7 +677,7 @@ def run_bench(args, comm, make_handle=None, device="cuda", cpu_base=None):
     c = res["counters"]
     iter_sum_rank0_share = int(c[3]) / comm.world  # the profile is rank 0's; counters are whole-job
     roof = {"bound": None, "achieved": None, "peak": None, "unit": None, "frac": None, "traffic": None,
-            "note": "no per-kernel HIP-event pass in this run (--no-profile, or not on a GPU)"}
+            "note": "no per-kernel HIP-event pass in this run (a run without --full, --no-profile, or not on a GPU)"}
     prof = res["profile"]
     cus = torch.cuda.get_device_properties(0).multi_processor_count if device == "cuda" else 256
     if prof:
@@ -726,7 +754,7 @@ def run_bench(args, comm, make_handle=None, device="cuda", cpu_base=None):
         roof = dict(bound="hbm", achieved=round(gbs, 1), peak=HBM_PEAK_GBS, unit="GB/s", frac=round(gbs / HBM_PEAK_GBS, 4), traffic=None,
                     algorithmic_bytes_per_frame_sweep=bytes_per_frame_iter, kernel="whole step",
                     note="no per-pass HIP events on this backend: executed frame-sweeps x algorithmic bytes / WALL time of the step")
-    if aux and device == "cuda" and not args.no_profile and hasattr(handle, "timed_launches"):
+    if aux and device == "cuda" and args.full and not args.no_profile and hasattr(handle, "timed_launches"):
         # the dominant kernel alone (k_admm_lds / k_ml), HIP events on the stream it is launched on, inputs resident in HBM
         ms, units = handle.timed_launches(channel, param, rank_batch, args.max_iter, max(2, min(args.steps, 8)), torch)
         kname = handle.kernel_name(True)
@@ -826,7 +854,7 @@ def run_bench(args, comm, make_handle=None, device="cuda", cpu_base=None):
             "frames_per_s": round(int(sc[0]) / stream_res["seconds"], 1),
             "note": "same workload with --backend stream (state resident in HBM): the HBM-bound path used for codes that do not fit the LDS; "
                     "sweep_* = executed frame-sweeps x s(4E+n) / time of the two passes; per kernel: its own compulsory bytes"}
-    out["cpu_baseline"] = cpu_base  # rank 0's host; None only with --no-cpu-baseline
+    out["cpu_baseline"] = cpu_base  # rank 0's host; None without --full or with --no-cpu-baseline
     return out
 
 
@@ -835,7 +863,7 @@ def parse_args(argv=None):
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--repeats", type=int, default=5, help="timed blocks of --steps steps; ms_per_step is the median block")
+    ap.add_argument("--repeats", type=int, default=None, help="timed blocks of --steps steps; ms_per_step is the median block (default: 1, with --full 5)")
     ap.add_argument("--batch", type=int, default=65536, help="frames per GPU per step (weak scaling: the whole job decodes N x this per step)")
     ap.add_argument("--total-batch", type=int, default=None,
                     help="frames per step over ALL GPUs (strong scaling: each rank decodes its shard; BASELINE configs 4 / 5 state 2^20 / 2^18 for 8 GPUs)")
@@ -852,13 +880,22 @@ def parse_args(argv=None):
                     help="message arithmetic; f64 is the reference's own (hard decisions bit-identical to it), f32 the throughput mode, f16 = fp16 "
                          "STORAGE of the streaming messages with fp32 arithmetic (codes whose state lives in HBM; a tolerance mode)")
     ap.add_argument("--backend", default="auto", choices=["auto", "stream", "fused"])
-    ap.add_argument("--points", type=float, nargs="*", default=None, help="extra channel parameters reported under 'points' (default: 2.0 3.0 dB / p = 0.05 / eps = 0.35)")
+    ap.add_argument("--points", type=float, nargs="*", default=None,
+                    help="extra channel parameters reported under 'points' (default: none; with --full 2.0 3.0 dB / p = 0.05 / eps = 0.35)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: repeated timed blocks, the HIP-event kernel pass and roofline, points, side legs, "
+                         "CPU baselines, baseline_configs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the counters of the last timed step as DIR/counters.npy and DIR/sweep_histogram.npy (float64)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-baseline-seconds", type=float, default=10.0, help="CPU work per baseline leg (C port, scipy processes)")
     ap.add_argument("--no-profile", action="store_true", help="headline only: skip the HIP-event kernel pass and the side legs")
     ap.add_argument("--no-baseline-configs", action="store_true",
                     help="default workload only: skip the `baseline_configs` block (BASELINE configs 3-5, a few steps each, on the same line)")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.repeats is None:
+        args.repeats = 5 if args.full else 1
+    return args
 
 
 # BASELINE.json configs 3-5 on the line of the DEFAULT command (`baseline_configs`): the selectors of src/main.py:11-12 / src/models.py:3 that
@@ -877,13 +914,13 @@ BASELINE_CONFIGS = [
 
 def baseline_config_args(args, flags):
     """argparse namespace of one `baseline_configs` entry: the entry's own flags, headline-only legs, this run's --gpus."""
-    sub = parse_args(flags + ["--gpus", str(args.gpus), "--repeats", "3", "--points", "--max-iter", str(args.max_iter)])
+    sub = parse_args(flags + ["--gpus", str(args.gpus), "--repeats", "3", "--points", "--max-iter", str(args.max_iter), "--full"])
     sub.headline_only = True
     return sub
 
 
 def is_default_workload(args):
-    """True for the command the round driver runs (the headline of BASELINE.json, no selector passed): only that line carries `baseline_configs`."""
+    """True for the command the round driver runs (the headline of BASELINE.json, no selector passed): only that line, run with --full, carries `baseline_configs`."""
     d = parse_args([])
     return all(getattr(args, k) == getattr(d, k) for k in ("decoder", "channel", "param", "snr", "max_iter", "code", "precision", "backend", "batch",
                                                             "total_batch")) and not args.no_profile and not args.no_baseline_configs
@@ -941,13 +978,13 @@ def main(argv=None, make_handle=None, device="cuda"):
     if world_env != args.gpus:
         print("bench.py: --gpus %d but WORLD_SIZE=%d; refusing to print a line for another N" % (args.gpus, world_env), file=sys.stderr)
         sys.exit(3)
-    # rank 0 times the CPU baselines first: nothing of HIP / torch.cuda / the process group exists in this process yet, so the scipy
+    # with --full, rank 0 times the CPU baselines first: nothing of HIP / torch.cuda / the process group exists in this process yet, so the scipy
     # leg may fork its workers, and at N > 1 the other ranks simply wait at the rendezvous meanwhile (~25 s headline + ~4 s per
     # baseline_configs entry at N = 1; the process-group timeout is 10 min)
     rank0 = int(os.environ.get("RANK", "0")) == 0
-    subs = [(name, what, baseline_config_args(args, flags)) for name, what, flags in BASELINE_CONFIGS] if is_default_workload(args) else []
+    subs = [(name, what, baseline_config_args(args, flags)) for name, what, flags in BASELINE_CONFIGS] if args.full and is_default_workload(args) else []
     cpu_base, sub_base = None, {}
-    if rank0 and not args.no_cpu_baseline:
+    if rank0 and args.full and not args.no_cpu_baseline:
         alg, channel, param = resolve_workload(args.decoder, args.channel, args.param, args.snr)
         cpu_base = cpu_baseline(load_code(args.code), alg, channel, param, args.max_iter, args.precision, args.cpu_baseline_seconds)
         if world_env == 1:  # the contract: the CPU baseline is timed on rank 0 at N = 1 only; the sub-configurations take the C port alone

@@ -219,7 +219,7 @@ def test_bench_strong_scaling_split_on_1_2_4_8_ranks(tmp_path):
 # ranks itself (a fresh torch.distributed.run child, the parent touching no GPU), relay rank 0's line, and never print a line for another N.
 ENTRY = os.path.join(ROOT, "tests", "bench_cpu_entry.py")
 TINY = ["--steps", "3", "--warmup", "1", "--repeats", "2", "--code", "7_4_hamming", "--snr", "2.0", "--max-iter", "10", "--points", "--no-profile",
-        "--cpu-baseline-seconds", "0.2"]
+        "--cpu-baseline-seconds", "0.2", "--full"]
 
 
 def _plain(argv, env_extra=None, script=ENTRY):
@@ -242,6 +242,27 @@ def test_plain_bench_command_launches_its_own_ranks():
     for k in ("frames_counted", "word_errors", "bit_errors", "mean_sweeps", "wer", "ber"):   # same global frames, same counters
         assert one[k] == two[k], k
     assert two["cpu_baseline"]["value"] > 0 and isinstance(two["roofline"], dict)
+
+
+@pytest.mark.timeout(900)
+def test_plain_bench_run_is_lean_and_dumps_its_last_step(tmp_path):
+    # without --full: one timed block of exactly --steps steps and nothing beside it (no CPU baseline, kernel pass, points or side legs);
+    # --dump-outputs writes the counter row of the last timed step, the same in every run with the same arguments
+    flags = ["--gpus", "1", "--batch", "64", "--steps", "3", "--warmup", "1", "--code", "7_4_hamming", "--snr", "2.0", "--max-iter", "10"]
+    lines = []
+    for run in ("a", "b"):
+        rc, out, err = _plain(flags + ["--dump-outputs", str(tmp_path / run)])
+        assert rc == 0 and len(out) == 1, err
+        lines.append(json.loads(out[0]))
+    one = lines[0]
+    assert one["steps"] == 3 and one["timed_blocks"] == 1 and one["frames_counted"] == 3 * 64 and one["ms_per_step"] > 0
+    assert one["cpu_baseline"] is None and one["points"] == [] and one["fp32_mode"] is None and one["roofline"]["frac"] is None
+    for name in ("counters", "sweep_histogram"):
+        a, b = np.load(str(tmp_path / "a" / (name + ".npy"))), np.load(str(tmp_path / "b" / (name + ".npy")))
+        assert a.dtype == np.float64 and np.array_equal(a, b), name
+    c, h = np.load(str(tmp_path / "a" / "counters.npy")), np.load(str(tmp_path / "a" / "sweep_histogram.npy"))
+    assert c.shape == (4,) and h.shape == (11,) and c[0] == 64 and h.sum() == 64 and c[3] == (h * np.arange(11)).sum()
+    assert c[1] <= one["word_errors"] and c[2] <= one["bit_errors"]
 
 
 def test_plain_bench_command_never_prints_a_line_for_another_n():

@@ -159,7 +159,7 @@ def test_bench_lines_of_the_admm_and_ml_decoders():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
     def line(flags):
-        out = subprocess.run([sys.executable, os.path.join(root, "bench.py")] + flags + ["--no-cpu-baseline"], capture_output=True, text=True, timeout=600)
+        out = subprocess.run([sys.executable, os.path.join(root, "bench.py")] + flags + ["--no-cpu-baseline", "--full"], capture_output=True, text=True, timeout=600)
         assert out.returncode == 0, out.stderr[-2000:]
         rows = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
         assert len(rows) == 1

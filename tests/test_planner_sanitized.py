@@ -77,7 +77,7 @@ def test_layout_planner_under_asan(tmp_path, code_name, cr, vr, vrx, nw):
     exe = str(tmp_path / "harness")
     # host-only build of the planner: the HIP header is only needed for types in ldpc_common.hpp -> use hipcc's host pass
     hipcc = "/opt/rocm/bin/hipcc"
-    cmd = [hipcc, "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-omit-frame-pointer", "-I", CSRC, "-x", "hip",
+    cmd = [hipcc, "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-gpu-sanitize", "-fno-omit-frame-pointer", "-I", CSRC, "-x", "hip",
            "--offload-arch=gfx950", "--cuda-host-only", str(src), os.path.join(CSRC, "ldpc_layout.hip"), "-o", exe]
     r = subprocess.run(cmd, capture_output=True, text=True)
     if r.returncode != 0:
@@ -105,7 +105,7 @@ def test_layout_planner_under_asan_pair_rounds(tmp_path):
     src = tmp_path / "harness.cpp"
     src.write_text(HARNESS)
     exe = str(tmp_path / "harness")
-    cmd = ["/opt/rocm/bin/hipcc", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-omit-frame-pointer", "-I", CSRC, "-x", "hip",
+    cmd = ["/opt/rocm/bin/hipcc", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-gpu-sanitize", "-fno-omit-frame-pointer", "-I", CSRC, "-x", "hip",
            "--offload-arch=gfx950", "--cuda-host-only", str(src), os.path.join(CSRC, "ldpc_layout.hip"), "-o", exe]
     r = subprocess.run(cmd, capture_output=True, text=True)
     if r.returncode != 0:
@@ -138,7 +138,7 @@ def test_layout_planner_under_asan_16_wave_shape(tmp_path):
     src = tmp_path / "harness.cpp"
     src.write_text(HARNESS.replace("plan_fused_layout(c, 6, CR, vr, 0x1200, 1200000, &L)", "plan_fused_layout(c, 6, CR, vr, 0x1200, 300000, &L)"))
     exe = str(tmp_path / "harness")
-    cmd = ["/opt/rocm/bin/hipcc", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-omit-frame-pointer", "-I", CSRC, "-x", "hip",
+    cmd = ["/opt/rocm/bin/hipcc", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-gpu-sanitize", "-fno-omit-frame-pointer", "-I", CSRC, "-x", "hip",
            "--offload-arch=gfx950", "--cuda-host-only", str(src), os.path.join(CSRC, "ldpc_layout.hip"), "-o", exe]
     r = subprocess.run(cmd, capture_output=True, text=True)
     if r.returncode != 0:

@@ -6,8 +6,8 @@ OUT=$R/gpurun_out/${1:-r06/ab_fold}
 mkdir -p $OUT
 for rep in 1 2; do
   for F in 1 0; do
-    LDPC_STREAM_REPACK_FOLD=$F python $R/bench.py --code gen:reg:64800:3:6 --batch 32768 --snr 2.0 --steps 2 --warmup 1 --repeats 3 --precision f32 --points --no-cpu-baseline > $OUT/c5_fold$F.$rep.json 2>/dev/null
-    LDPC_STREAM_REPACK_FOLD=$F python $R/bench.py --code gen:irg:10000 --batch 32768 --snr 1.8 --steps 2 --warmup 1 --repeats 3 --precision f64 --points --no-cpu-baseline > $OUT/c4_f64_fold$F.$rep.json 2>/dev/null
+    LDPC_STREAM_REPACK_FOLD=$F python $R/bench.py --code gen:reg:64800:3:6 --batch 32768 --snr 2.0 --steps 2 --warmup 1 --repeats 3 --precision f32 --points --no-cpu-baseline --full > $OUT/c5_fold$F.$rep.json 2>/dev/null
+    LDPC_STREAM_REPACK_FOLD=$F python $R/bench.py --code gen:irg:10000 --batch 32768 --snr 1.8 --steps 2 --warmup 1 --repeats 3 --precision f64 --points --no-cpu-baseline --full > $OUT/c4_f64_fold$F.$rep.json 2>/dev/null
   done
 done
 python - <<PY

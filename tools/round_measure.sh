@@ -14,7 +14,7 @@ timeout 600 python -m pytest tests/test_gpu_parity.py tests/test_gpu_large_codes
 timeout 2400 bash tools/collect_rooflines.sh $TAG > $OUT/collect.log 2>&1
 python tools/summarize_rooflines.py $TAG > $OUT/summarize.log 2>&1
 # one gradeable line per BASELINE configuration: roofline AND cpu_baseline on every one (5 s of CPU work per baseline leg on configs 3-5)
-run() { NAME=$1; shift; timeout 900 python bench.py "$@" > $OUT/$NAME.json 2> $OUT/$NAME.err; cp $OUT/$NAME.json profiles/${TAG}_$NAME.json 2>/dev/null; }
+run() { NAME=$1; shift; timeout 900 python bench.py --full "$@" > $OUT/$NAME.json 2> $OUT/$NAME.err; cp $OUT/$NAME.json profiles/${TAG}_$NAME.json 2>/dev/null; }
 run bench
 run bench_f32 --precision f32 --cpu-baseline-seconds 5
 run bench_config3_spa_bsc --decoder SPA --channel bsc --param 0.07 --precision f32 --batch 65536 --steps 20 --warmup 3 --cpu-baseline-seconds 5

@@ -22,6 +22,6 @@ R=$(cd "$(dirname "$0")/.." && pwd)
 OUT=$R/gpurun_out/scale_$CONFIG
 mkdir -p $OUT
 for N in 1 2 4 8; do
-  python $R/bench.py --gpus $N --steps $STEPS --warmup $WARMUP $FLAGS "$@" | tee $OUT/$N.json
+  python $R/bench.py --gpus $N --steps $STEPS --warmup $WARMUP --full $FLAGS "$@" | tee $OUT/$N.json
   [ ${PIPESTATUS[0]} -eq 3 ] && echo "{\"n_gpus\": $N, \"config\": \"$CONFIG\", \"skipped\": \"bench.py exit 3: fewer than $N GPUs\"}"
 done
