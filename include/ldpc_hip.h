@@ -196,6 +196,29 @@ int ldpc_count_errors_bits(const uint32_t* xhat_bits_dev, const uint32_t* erased
 int ldpc_count_errors_words(const uint8_t* xhat_dev, const uint8_t* sent_dev, const int32_t* iters_dev, int64_t B, int32_t n,
                             int32_t hist_bins, int64_t* counters_dev, void* stream);
 
+/* ---- Systematic GF(2) encoder: a random codeword per frame for ANY code ----------------------------------------
+ * `--codeword -1` (src/main.py:38: x = code.cb[np.random.choice(K)]) upstream needs the code book, i.e. a toy code.  The encoder
+ * takes the systematic form of H computed on the host (ldpc_decoders_amd/encoder.py: GF(2) elimination, pivot = first row with a 1,
+ * columns left to right): par_pos [r] = the r = rank pivot columns, info_pos [k] = the other k = n - r columns, P_bits_host [k, r]
+ * bytes in {0,1} (row-major) with  c[par_pos] = u . P mod 2,  c[info_pos] = u.  Host pointers; P is kept on `device` as bits in
+ * the fragment order of the i8 matrix cores. */
+typedef struct ldpc_encoder_s* ldpc_encoder_t;
+int ldpc_encoder_create(int device, int32_t n, int32_t k, int32_t r, const int32_t* info_pos, const int32_t* par_pos, const uint8_t* P_bits_host,
+                        ldpc_encoder_t* out);
+int ldpc_encoder_destroy(ldpc_encoder_t enc);
+/* Codewords of B given information words: info_dev [B, k] uint8 in {0,1} -> sent_dev [B, n] uint8 (the layout ldpc_count_errors_words
+ * reads).  u . P runs on v_mfma_i32_32x32x32_i8 (int32 accumulation, & 1): exact.  Uses a workspace of the handle (one call at a time). */
+int ldpc_encode(ldpc_encoder_t enc, const uint8_t* info_dev, int64_t B, uint8_t* sent_dev, void* stream);
+/* The same for RANDOM information words: frame f of [frame0, frame0+B) draws its k bits from Philox4x32-10 keyed by (seed, stream_id,
+ * global frame index) like every other draw, blocks 0x80000000 + j: bit t of word w of block j is information bit 128 j + 32 w + t
+ * (disjoint from the noise blocks 0 .. n/4 and 0xFFFFFFFE / 0xFFFFFFFF).  A frame's word does not depend on the batching. */
+int ldpc_encode_random(ldpc_encoder_t enc, uint64_t seed, uint64_t stream_id, uint64_t frame0, int64_t B, uint8_t* sent_dev, void* stream);
+/* Channel.send + LLR of ldpc_channel for a GIVEN word per frame, sent_dev [B, n] uint8: the noise is that of ldpc_channel for the same
+ * (seed, stream_id, frame), draw for draw -- with an all-zero sent_dev the outputs equal ldpc_channel(codeword = 0)'s.  Plain
+ * LDPC_CH_* ids only (no raw-observation or prior-grid flags); priors_dev / y_dev as ldpc_channel. */
+int ldpc_channel_sent(int channel, int dtype, double param, const uint8_t* sent_dev, uint64_t seed, uint64_t stream_id, uint64_t frame0,
+                      int64_t B, int32_t n, void* priors_dev, uint8_t* y_dev, void* stream);
+
 /* ---- Maximum-likelihood decoding of the short codes by codebook search -----------------------------------------
  * Replaces biawgn.ML (src/biawgn.py:66-78), bsc.ML (src/bsc.py:63-75) and bec.ML (src/bec.py:21-36).  `codebook` is
  * Code.cb (src/codes.py:11-14): [K, n] bytes in {0,1}, host pointer, K <= 2^20 words of n <= 64 bits. */

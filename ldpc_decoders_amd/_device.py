@@ -242,15 +242,16 @@ class DecoderHandle:
         return 1
 
     def _simulate_random_words(self, channel, param, seed, stream_id, frame0, B, max_iter, counters, flags, hist_bins, st):
-        """``--codeword -1`` (src/main.py:38): every frame sends a random word of the code book (small codes only, as upstream).  A
-        composition on the device -- channel kernel (picks the word, adds the noise) -> decode -> count against the sent words."""
+        """``--codeword -1`` (src/main.py:38): every frame sends a random codeword.  A composition on the device.  Codes with a code book
+        (the built-in toy codes): channel kernel (picks the word, adds the noise) -> decode -> count against the sent words.  Every other
+        code: systematic encoder on random information bits (``Code.encoder()``) -> channel of the sent words -> decode -> count."""
         import torch
 
         lib = _lib.load()
         if getattr(self, "_cb_dev", None) is None:
             cb = getattr(self.code, "cb", None)
             if cb is None:
-                raise ValueError("--codeword -1 needs the code book of a small code (Code.cb)")
+                return self._simulate_encoded_words(channel, param, seed, stream_id, frame0, B, max_iter, counters, flags, hist_bins, st)
             self._cb_dev = torch.from_numpy(np.ascontiguousarray(cb, dtype=np.uint8)).cuda()
         n, K = self.code.n, int(self._cb_dev.shape[0])
         dt = torch.float64 if self.precision == "f64" else torch.float32
@@ -265,6 +266,42 @@ class DecoderHandle:
                                               None if y is None else y.data_ptr(), sent.data_ptr(), st))
             xhat, iters = self.decode_device(pri, y, max_iter, flags)
             _lib.check(lib.ldpc_count_errors_words(xhat.data_ptr(), sent.data_ptr(), iters.data_ptr(), nb, n, hist_bins, counters.data_ptr(), st))
+
+    WORDS_BYTES = 1 << 30  # what the sent words and the channel output of one chunk of the encoded-word path may occupy together
+
+    def _simulate_encoded_words(self, channel, param, seed, stream_id, frame0, B, max_iter, counters, flags, hist_bins, st):
+        import torch
+
+        lib, n = _lib.load(), self.code.n
+        enc = self.code.encoder().handle(self.code_handle.device)
+        dt = torch.float64 if self.precision == "f64" else torch.float32
+        per_frame = n * (1 + (0 if channel == "bec" else dt.itemsize) + (0 if channel == "biawgn" else 1))
+        step = max(64, min(int(B), self.WORDS_BYTES // per_frame))
+        for b0 in range(0, int(B), step):
+            nb = min(step, int(B) - b0)
+            sent = enc.encode_random(seed, stream_id, int(frame0) + b0, nb)
+            pri = None if channel == "bec" else torch.empty((nb, n), dtype=dt, device="cuda")
+            y = None if channel == "biawgn" else torch.empty((nb, n), dtype=torch.uint8, device="cuda")
+            _lib.check(lib.ldpc_channel_sent(_lib.CHANNEL[channel], _lib.IO_DTYPE[self.precision], float(param), sent.data_ptr(), int(seed),
+                                             int(stream_id), int(frame0) + b0, nb, n, None if pri is None else pri.data_ptr(),
+                                             None if y is None else y.data_ptr(), st))
+            xhat, iters = self.decode_device(pri, y, max_iter, flags)
+            _lib.check(lib.ldpc_count_errors_words(xhat.data_ptr(), sent.data_ptr(), iters.data_ptr(), nb, n, hist_bins, counters.data_ptr(), st))
+
+    def channel_sent_device(self, channel, param, sent, seed, stream_id, frame0):
+        """``ldpc_channel_sent``: the channel of ``channel_device`` for the given words ``sent`` (CUDA uint8 [B, n]), one per frame of
+        [frame0, frame0 + B).  -> (priors or None, y or None)."""
+        import torch
+
+        n, B = self.code.n, sent.shape[0]
+        dt = torch.float64 if self.precision == "f64" else torch.float32
+        pri = None if channel == "bec" else torch.empty((B, n), dtype=dt, device=sent.device)
+        y = None if channel == "biawgn" else torch.empty((B, n), dtype=torch.uint8, device=sent.device)
+        st = torch.cuda.current_stream(sent.device).cuda_stream
+        _lib.check(_lib.load().ldpc_channel_sent(_lib.CHANNEL[channel], _lib.IO_DTYPE[self.precision], float(param), sent.data_ptr(), int(seed),
+                                                 int(stream_id), int(frame0), B, n, None if pri is None else pri.data_ptr(),
+                                                 None if y is None else y.data_ptr(), st))
+        return pri, y
 
     def fused_info(self):
         out = (ctypes.c_double * 8)()

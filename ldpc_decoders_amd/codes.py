@@ -39,6 +39,7 @@ class Code:
         self.gen_mtx = None if gen_mtx is None else np.asarray(gen_mtx, dtype=np.int64)
         self._dense = None
         self._cb = None
+        self._enc = None
         self._handles = {}
         if parity_mtx is not None:
             H = np.asarray(parity_mtx)
@@ -98,6 +99,14 @@ class Code:
             assert self.syndrome(cb).sum() == 0 and cb[0].sum() == 0
             self._cb = cb
         return self._cb
+
+    def encoder(self):
+        """Systematic GF(2) encoder of this code (``encoder.Encoder``), computed on first use and kept."""
+        if getattr(self, "_enc", None) is None:
+            from .encoder import Encoder
+
+            self._enc = Encoder(self)
+        return self._enc
 
     def syndrome(self, words):
         """(H @ words^T) mod 2 without a dense H; words [..., n] -> [..., m]."""

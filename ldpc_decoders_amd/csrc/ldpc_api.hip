@@ -9,6 +9,7 @@
 
 #include "../../include/ldpc_hip.h"
 #include "ldpc_common.hpp"
+#include "ldpc_encode.hpp"
 
 namespace ldpc {
 
@@ -773,6 +774,38 @@ int ldpc_count_errors_words(const uint8_t* xhat, const uint8_t* sent, const int3
             return LDPC_E_ARG;
         }
         return count_errors_words(xhat, sent, 1, 0, iters, B, n, hist_bins, counters, (hipStream_t)stream);
+    });
+}
+
+int ldpc_encoder_create(int device, int32_t n, int32_t k, int32_t r, const int32_t* info_pos, const int32_t* par_pos, const uint8_t* P_bits_host,
+                        ldpc_encoder_t* out) {
+    return guarded("ldpc_encoder_create", [&]() -> int {
+        Encoder* e = nullptr;
+        LDPC_TRY(encoder_create(device, n, k, r, info_pos, par_pos, P_bits_host, &e));
+        *out = (ldpc_encoder_t)e;
+        return LDPC_OK;
+    });
+}
+
+int ldpc_encoder_destroy(ldpc_encoder_t enc) {
+    return guarded("ldpc_encoder_destroy", [&]() -> int {
+        encoder_destroy((Encoder*)enc);
+        return LDPC_OK;
+    });
+}
+
+int ldpc_encode(ldpc_encoder_t enc, const uint8_t* info_dev, int64_t B, uint8_t* sent_dev, void* stream) {
+    return guarded("ldpc_encode", [&]() -> int { return encode((Encoder*)enc, info_dev, B, sent_dev, (hipStream_t)stream); });
+}
+
+int ldpc_encode_random(ldpc_encoder_t enc, uint64_t seed, uint64_t stream_id, uint64_t frame0, int64_t B, uint8_t* sent_dev, void* stream) {
+    return guarded("ldpc_encode_random", [&]() -> int { return encode_random((Encoder*)enc, seed, stream_id, frame0, B, sent_dev, (hipStream_t)stream); });
+}
+
+int ldpc_channel_sent(int channel, int dtype, double param, const uint8_t* sent_dev, uint64_t seed, uint64_t stream_id, uint64_t frame0, int64_t B,
+                      int32_t n, void* priors_dev, uint8_t* y_dev, void* stream) {
+    return guarded("ldpc_channel_sent", [&]() -> int {
+        return channel_sent(channel, dtype, param, sent_dev, seed, stream_id, frame0, B, n, priors_dev, y_dev, (hipStream_t)stream);
     });
 }
 
