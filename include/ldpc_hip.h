@@ -242,6 +242,41 @@ int ldpc_ml_decode(ldpc_ml_t ml, int channel, int dtype, const double* coef2, co
 int ldpc_ml_simulate(ldpc_ml_t ml, int channel, int dtype, double param, int codeword, uint64_t seed, uint64_t stream_id,
                      uint64_t frame0, int64_t B, int64_t* counters_dev, void* stream);
 
+/* ---- Maximum-likelihood decoding over the BEC for EVERY code: GF(2) elimination ---------------------------------
+ * Replaces bec.ML (src/bec.py:21-36: the maximum of the likelihood over the code book, math_utils.arg_max_rand at
+ * src/math_utils.py:72-74 picking uniformly among the maximisers) for codes without a code book.  Over the BEC every codeword that
+ * agrees with the unerased symbols has the same likelihood, so the maximisers are the solutions of  H_E x_E = H_Ebar y_Ebar  over GF(2):
+ *   1. peel: the erasure decoder (LDPC_ALG_BEC, max_iter <= 0) to its stopping-set exit; the bits it leaves erased are the residual
+ *      set R (the largest stopping set inside the erasure pattern);
+ *   2. the system on the columns R, ascending, with the rows (checks) that touch R, right-hand side = XOR of each row's known bits,
+ *      brought to reduced row echelon form (columns in ascending order; pivot = the first unused row, in H's row order, with a 1);
+ *   3. free column number t (the non-pivot columns of R, ascending) takes bit t of Philox4x32-10 keyed by (seed, stream_id, global
+ *      frame index), block 0xC0000000 + j: bit t of word w of block j is free bit 128 j + 32 w + t (disjoint from the noise blocks
+ *      0 .. n/4, the information bits 0x80000000 + j, 0xFFFFFFFE and 0xFFFFFFFF); the pivot columns follow.  The pick is uniform over
+ *      the solution set and depends only on the global frame index;
+ *   4. nullity [B] int32: d = |R| - rank (the solution set has 2^d words; 0 for a frame peeling finished), -1 if the system is
+ *      inconsistent (only possible when the sent word is no codeword; the decisions are then those of the same rule on the
+ *      consistent part and are no codeword).
+ * The system of a frame lives in the LDS of one CU: create fails with LDPC_E_ARG unless the worst case (every bit erased) fits 160 KiB,
+ * i.e.  4 * (3 W + 3 S + S * 64 ceil(m / 64)) <= 163840  with W = ceil(n / 32), S = ceil((n + 1) / 32)  (about m * n <= 1 310 720 bits),
+ * and m <= 4096.  Handles are not thread-safe (one workspace). */
+typedef struct ldpc_bec_ml_s* ldpc_bec_ml_t;
+int ldpc_bec_ml_create(ldpc_code_t code, ldpc_bec_ml_t* out);
+int ldpc_bec_ml_destroy(ldpc_bec_ml_t h);
+/* Steps 2-4 on already peeled frames: bits_dev / erased_bits_dev [B, W] in the layout ldpc_decode_bits writes (LDPC_ALG_BEC, max_iter
+ * <= 0); out_bits_dev [B, W] (may equal bits_dev) receives the resolved words, nullity_dev [B] the nullities.  Frames [frame0, frame0+B). */
+int ldpc_bec_ml_solve(ldpc_bec_ml_t h, const uint32_t* bits_dev, const uint32_t* erased_bits_dev, int64_t B, uint64_t seed, uint64_t stream_id,
+                      uint64_t frame0, uint32_t* out_bits_dev, int32_t* nullity_dev, void* stream);
+/* ML.decode (src/bec.py:21-36) for B frames of symbols y_dev [B, n] uint8 in {0, 1, 2 = erased}: peel + solve; xhat_dev [B, n] uint8
+ * in {0, 1}, nullity_dev [B] int32. */
+int ldpc_bec_ml_decode(ldpc_bec_ml_t h, const uint8_t* y_dev, int64_t B, uint64_t seed, uint64_t stream_id, uint64_t frame0, uint8_t* xhat_dev,
+                       int32_t* nullity_dev, void* stream);
+/* Channel.send (src/bec.py:11-18, ldpc_channel's draws) + ML.decode + the counters of main.test (src/main.py:41-45) for frames
+ * [frame0, frame0+B) of the all-`codeword` word: accumulates tot / wec / bec into counters_dev (int64[4]); ITER_SUM stays 0, as for
+ * ldpc_ml_simulate.  codeword 0 or 1; 1 is refused (LDPC_E_ARG) when a check has odd degree (the all-ones word is then no codeword). */
+int ldpc_bec_ml_simulate(ldpc_bec_ml_t h, double param, int codeword, uint64_t seed, uint64_t stream_id, uint64_t frame0, int64_t B,
+                         int64_t* counters_dev, void* stream);
+
 /* ---- ADMM LP decoding ------------------------------------------------------------------------------------------
  * Replaces admm.ADMM (src/admm.py:9-77) together with its native projection (src/parity_polytope/projection.cpp:30-275, bound
  * upstream through ctypes in exact.py:12-53).  Check degrees up to 16. */

@@ -484,6 +484,84 @@ class MlHandle:
                                                 int(seed), int(stream_id), int(frame0), int(B), counters.data_ptr(), st))
 
 
+class BecMlHandle:
+    """ML decoding over the BEC for a code without a code book (``ldpc_bec_ml_*``): peeling, then GF(2) elimination of the residual
+    system on the device, one wave per frame that keeps erasures."""
+
+    def __init__(self, code, device=None):
+        lib = _lib.load()
+        self.code_handle = code_handle(code, device)
+        self.code, self.device = code, self.code_handle.device
+        h = ctypes.c_void_p()
+        _lib.check(lib.ldpc_bec_ml_create(self.code_handle.h, ctypes.byref(h)))
+        self.h = h
+
+    def __del__(self):
+        try:
+            if getattr(self, "h", None):
+                _lib.load().ldpc_bec_ml_destroy(self.h)
+                self.h = None
+        except Exception:
+            pass
+
+    def decode_device(self, y, seed, stream_id=0, frame0=0):
+        """y: contiguous CUDA uint8 tensor [B, n] of symbols {0, 1, 2} -> (xhat uint8 [B, n], nullity int32 [B]) for frames
+        [frame0, frame0 + B) (the tie-break draws are keyed by (seed, stream_id, global frame index))."""
+        import torch
+
+        n = self.code.n
+        if not y.is_cuda or y.dtype != torch.uint8 or not y.is_contiguous() or y.dim() != 2 or y.shape[1] != n:
+            raise ValueError("y must be a contiguous CUDA uint8 tensor [B, %d]" % n)
+        B = y.shape[0]
+        xhat = torch.empty((B, n), dtype=torch.uint8, device=y.device)
+        nul = torch.empty((B,), dtype=torch.int32, device=y.device)
+        if B:
+            st = torch.cuda.current_stream(y.device).cuda_stream
+            _lib.check(_lib.load().ldpc_bec_ml_decode(self.h, y.data_ptr(), B, int(seed), int(stream_id), int(frame0), xhat.data_ptr(),
+                                                      nul.data_ptr(), st))
+        return xhat, nul
+
+    def solve_bits(self, bits, erased, seed, stream_id=0, frame0=0):
+        """``ldpc_bec_ml_solve`` on peeled packed frames (``DecoderHandle.decode_device_bits`` of an erasure decoder, max_iter <= 0):
+        bits / erased int32 CUDA [B, ceil(n/32)] -> (resolved words int32 [B, W], nullity int32 [B])."""
+        import torch
+
+        B = bits.shape[0]
+        out = torch.empty_like(bits)
+        nul = torch.empty((B,), dtype=torch.int32, device=bits.device)
+        if B:
+            st = torch.cuda.current_stream(bits.device).cuda_stream
+            _lib.check(_lib.load().ldpc_bec_ml_solve(self.h, bits.data_ptr(), erased.data_ptr(), B, int(seed), int(stream_id), int(frame0),
+                                                     out.data_ptr(), nul.data_ptr(), st))
+        return out, nul
+
+    def simulate(self, channel, param, codeword, seed, stream_id, frame0, B, max_iter, counters, flags=0, hist_bins=0):
+        """Same call shape as DecoderHandle.simulate (max_iter / flags / hist_bins have no meaning here; ITER_SUM stays 0).
+        ``codeword == -1``: random codewords from the systematic encoder (``Code.encoder()``) through ``ldpc_channel_sent``."""
+        import torch
+
+        if channel != "bec":
+            raise ValueError("the elimination ML decoder works on the erasure channel only")
+        if B <= 0:
+            return
+        lib = _lib.load()
+        st = torch.cuda.current_stream(counters.device).cuda_stream
+        if int(codeword) != -1:
+            _lib.check(lib.ldpc_bec_ml_simulate(self.h, float(param), int(codeword), int(seed), int(stream_id), int(frame0), int(B),
+                                                counters.data_ptr(), st))
+            return
+        n, enc = self.code.n, self.code.encoder().handle(self.device)
+        step = 1 << 17
+        for b0 in range(0, int(B), step):
+            nb = min(step, int(B) - b0)
+            sent = enc.encode_random(seed, stream_id, int(frame0) + b0, nb)
+            y = torch.empty((nb, n), dtype=torch.uint8, device=counters.device)
+            _lib.check(lib.ldpc_channel_sent(_lib.CHANNEL["bec"], 0, float(param), sent.data_ptr(), int(seed), int(stream_id), int(frame0) + b0,
+                                             nb, n, None, y.data_ptr(), st))
+            xhat, _ = self.decode_device(y, seed, stream_id, int(frame0) + b0)
+            _lib.check(lib.ldpc_count_errors_words(xhat.data_ptr(), sent.data_ptr(), None, nb, n, 0, counters.data_ptr(), st))
+
+
 class AdmmHandle:
     """ADMM LP decoder workspace on one GPU (``ldpc_admm_*``)."""
 

@@ -67,4 +67,16 @@ class ADMM:  # src/bec.py:38-45,58-62: LLR wrapper with +-1e8 for the known symb
         return self.dec.decode_batch(self.llr[np.asarray(y)])
 
 
-from .ml import BecML as ML  # noqa: E402  (src/bec.py: class ML)
+class ML:  # src/bec.py: class ML
+    """A code with a code book (the built-in toy codes): the code-book search ``ml.BecML``.  Every other code: peeling + GF(2)
+    elimination of the residual system on the GPU (``bec_ml.BecEliminationML``).  Both pick uniformly among the maximisers."""
+    id_keys = []
+
+    def __new__(cls, p, _code, **kwargs):
+        if getattr(_code, "gen_mtx", None) is not None:
+            return BecML(p, _code, **kwargs)
+        return BecEliminationML(p, _code, **kwargs)
+
+
+from .bec_ml import BecEliminationML  # noqa: E402
+from .ml import BecML  # noqa: E402

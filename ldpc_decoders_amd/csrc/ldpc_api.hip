@@ -9,6 +9,7 @@
 
 #include "../../include/ldpc_hip.h"
 #include "ldpc_common.hpp"
+#include "ldpc_bec_ml.hpp"
 #include "ldpc_encode.hpp"
 
 namespace ldpc {
@@ -982,6 +983,60 @@ int ldpc_ml_simulate(ldpc_ml_t h, int channel, int dtype, double param, int code
             return LDPC_E_ARG;
         }
         return ml_simulate((MlDecoder*)h, channel, dtype, param, codeword, seed, stream_id, frame0, B, counters_dev, (hipStream_t)stream);
+    });
+}
+
+// ---- ML erasure decoder of every code (ldpc_bec_ml.hip) ----
+int ldpc_bec_ml_create(ldpc_code_t code, ldpc_bec_ml_t* out) {
+    return guarded("ldpc_bec_ml_create", [&]() -> int {
+        if (!code || !out) {
+            set_error("ldpc_bec_ml_create: bad arguments");
+            return LDPC_E_ARG;
+        }
+        BecMl* h = nullptr;
+        LDPC_TRY(bec_ml_create((Code*)code, &h));
+        *out = (ldpc_bec_ml_t)h;
+        return LDPC_OK;
+    });
+}
+
+int ldpc_bec_ml_destroy(ldpc_bec_ml_t h) {
+    return guarded("ldpc_bec_ml_destroy", [&]() -> int {
+        bec_ml_destroy((BecMl*)h);
+        return LDPC_OK;
+    });
+}
+
+int ldpc_bec_ml_solve(ldpc_bec_ml_t h, const uint32_t* bits_dev, const uint32_t* erased_bits_dev, int64_t B, uint64_t seed, uint64_t stream_id,
+                      uint64_t frame0, uint32_t* out_bits_dev, int32_t* nullity_dev, void* stream) {
+    return guarded("ldpc_bec_ml_solve", [&]() -> int {
+        if (!h || !bits_dev || !erased_bits_dev || !out_bits_dev || !nullity_dev || B < 0) {
+            set_error("ldpc_bec_ml_solve: bad arguments");
+            return LDPC_E_ARG;
+        }
+        return bec_ml_solve((BecMl*)h, bits_dev, erased_bits_dev, B, seed, stream_id, frame0, out_bits_dev, nullity_dev, (hipStream_t)stream);
+    });
+}
+
+int ldpc_bec_ml_decode(ldpc_bec_ml_t h, const uint8_t* y_dev, int64_t B, uint64_t seed, uint64_t stream_id, uint64_t frame0, uint8_t* xhat_dev,
+                       int32_t* nullity_dev, void* stream) {
+    return guarded("ldpc_bec_ml_decode", [&]() -> int {
+        if (!h || !y_dev || !xhat_dev || !nullity_dev || B < 0) {
+            set_error("ldpc_bec_ml_decode: bad arguments");
+            return LDPC_E_ARG;
+        }
+        return bec_ml_decode((BecMl*)h, y_dev, B, seed, stream_id, frame0, xhat_dev, nullity_dev, (hipStream_t)stream);
+    });
+}
+
+int ldpc_bec_ml_simulate(ldpc_bec_ml_t h, double param, int codeword, uint64_t seed, uint64_t stream_id, uint64_t frame0, int64_t B,
+                         int64_t* counters_dev, void* stream) {
+    return guarded("ldpc_bec_ml_simulate", [&]() -> int {
+        if (!h || !counters_dev || B < 0) {
+            set_error("ldpc_bec_ml_simulate: bad arguments");
+            return LDPC_E_ARG;
+        }
+        return bec_ml_simulate((BecMl*)h, param, codeword, seed, stream_id, frame0, B, counters_dev, (hipStream_t)stream);
     });
 }
 

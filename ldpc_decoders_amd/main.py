@@ -31,8 +31,10 @@ def test(args, comm=None):
     code_n = code.get_n()
     saver = utils.Saver(args.data_dir, list(zip(id_keys, id_val))) if comm.is_root else None
     # --codeword -1 (a random codeword per frame, src/main.py:38): on the device for the BP decoders -- from the code book where the code
-    # has one, from the systematic GF(2) encoder (Code.encoder()) otherwise -- and the reference's sequential loop on host noise for the others
-    exact = bool(args.exact) or (args.codeword == -1 and args.decoder not in ("SPA", "MSA"))
+    # has one, from the systematic GF(2) encoder (Code.encoder()) otherwise -- and for ML over the BEC of a code without a code book (the
+    # elimination decoder, encoder words); the reference's sequential loop on host noise for the others
+    device_words = args.decoder in ("SPA", "MSA") or (args.channel == "bec" and args.decoder == "ML" and code.gen_mtx is None)
+    exact = bool(args.exact) or (args.codeword == -1 and not device_words)
     if exact and comm.world > 1:
         raise SystemExit("--exact / --codeword -1 follow the reference's sequential rule and run on a single rank")
     if exact and args.np_seed is not None:
