@@ -22,8 +22,10 @@ namespace ldpc {
 
 struct AdmmDecoder {
     Code* code = nullptr;
-    DevBuf z, lam, d1, d2, x, gam, live, flags, part;
-    DevBuf z2, lam2, x2, gam2, live2, fmap, fmap2, rbase;  // second state set + frame maps of the repack (ldpc_repack.hpp)
+    struct Set {  // what moves together in a frame repack (ldpc_repack.hpp); set[0] holds the state when a decode begins
+        DevBuf z, lam, x, gam, live, fmap;
+    } set[2];
+    DevBuf d1, d2, flags, part, rbase;  // shared by both sets
     int last_repacks = 0;
     int32_t* d_leaf_off = nullptr;  // numpy's summation blocks of a length-E vector
     int32_t* d_leaf_len = nullptr;
@@ -969,9 +971,9 @@ int admm_last_backend(const AdmmDecoder* d) { return d ? d->last_backend : 0; }
 
 void admm_destroy(AdmmDecoder* d) {
     if (!d) return;
-    for (DevBuf* b : {&d->z, &d->lam, &d->d1, &d->d2, &d->x, &d->gam, &d->live, &d->flags, &d->part, &d->z2, &d->lam2, &d->x2, &d->gam2, &d->live2, &d->fmap, &d->fmap2,
-                      &d->rbase})
-        b->release();
+    for (AdmmDecoder::Set& s : d->set)
+        for (DevBuf* b : {&s.z, &s.lam, &s.x, &s.gam, &s.live, &s.fmap}) b->release();
+    for (DevBuf* b : {&d->d1, &d->d2, &d->flags, &d->part, &d->rbase}) b->release();
     for (void* q : {(void*)d->d_leaf_off, (void*)d->d_leaf_len, (void*)d->d_prog, (void*)d->d_lvl_a, (void*)d->d_lvl_b, (void*)d->d_lvl_start, (void*)d->d_ticket, (void*)d->d_fold_partner})
         if (q) (void)hipFree(q);
     if (d->pinned) (void)hipHostFree(d->pinned);
@@ -1055,18 +1057,30 @@ int admm_decode(AdmmDecoder* d, const double* gamma, int64_t B, double mu, doubl
     d->last_backend = 0;
     const int tiles = (int)((B + 63) / 64);
     const size_t es = (size_t)tiles * E * 64 * sizeof(double), vs = (size_t)tiles * n * 64 * sizeof(double);
-    LDPC_TRY(d->z.reserve(es));
-    LDPC_TRY(d->lam.reserve(es));
+    AdmmDecoder::Set* const set = d->set;
+    LDPC_TRY(set[0].z.reserve(es));
+    LDPC_TRY(set[0].lam.reserve(es));
     LDPC_TRY(d->d1.reserve(es));
     LDPC_TRY(d->d2.reserve(es));
-    LDPC_TRY(d->x.reserve(vs));
-    LDPC_TRY(d->gam.reserve(vs));
-    LDPC_TRY(d->live.reserve((size_t)tiles * 8));
+    LDPC_TRY(set[0].x.reserve(vs));
+    LDPC_TRY(set[0].gam.reserve(vs));
+    LDPC_TRY(set[0].live.reserve((size_t)tiles * 8));
     LDPC_TRY(d->flags.reserve(64));
     LDPC_TRY(d->part.reserve((size_t)tiles * d->leaves * 128 * sizeof(double)));
-    double *z = (double*)d->z.p, *lam = (double*)d->lam.p, *d1 = (double*)d->d1.p, *d2 = (double*)d->d2.p, *x = (double*)d->x.p,
-           *gam = (double*)d->gam.p;
-    u64* live = (u64*)d->live.p;
+    double *d1 = (double*)d->d1.p, *d2 = (double*)d->d2.p;
+    int cur = 0;  // which set holds the state; the pointers below are re-read from it after a flip
+    double *z, *lam, *x, *gam;
+    u64* live;
+    int32_t* fmap = nullptr;  // frame index of (tile, lane); null = identity (never repacked)
+    auto use_set = [&](int s) {
+        cur = s;
+        z = (double*)set[s].z.p;
+        lam = (double*)set[s].lam.p;
+        x = (double*)set[s].x.p;
+        gam = (double*)set[s].gam.p;
+        live = (u64*)set[s].live.p;
+    };
+    use_set(0);
     int* live_tiles = (int*)d->flags.p;
     int* h_poll = (int*)d->pinned;
     LDPC_HIP_TRY(hipMemsetAsync(iters, 0, (size_t)B * sizeof(int32_t), st));
@@ -1083,14 +1097,7 @@ int admm_decode(AdmmDecoder* d, const double* gamma, int64_t B, double mu, doubl
     double repack_fill = 0.75;
     if (const char* e = std::getenv("LDPC_STREAM_REPACK")) repack_ok = atoi(e) != 0;
     if (const char* e = std::getenv("LDPC_STREAM_REPACK_FILL")) repack_fill = atof(e);
-    DevBuf* set_z[2] = {&d->z, &d->z2};
-    DevBuf* set_l[2] = {&d->lam, &d->lam2};
-    DevBuf* set_x[2] = {&d->x, &d->x2};
-    DevBuf* set_g[2] = {&d->gam, &d->gam2};
-    DevBuf* set_live[2] = {&d->live, &d->live2};
-    DevBuf* set_fmap[2] = {&d->fmap, &d->fmap2};
-    int cur = 0, cur_tiles = tiles, repacks = 0;
-    int32_t* fmap = nullptr;
+    int cur_tiles = tiles, repacks = 0;
     int done = 0;
     for (int it = 0; it < cap; ++it) {
         hipLaunchKernelGGL(k_admm_x, dim3(gv, cur_tiles), dim3(256), 0, st, c->d_col_ptr, c->d_col_edge, z, lam, gam, x, live, n, E, cur_tiles, mu);
@@ -1122,30 +1129,25 @@ int admm_decode(AdmmDecoder* d, const double* gamma, int64_t B, double mu, doubl
             const int lt = h_poll[0], lf = h_poll[1];
             if (lt == 0) break;
             if (repack_ok && lt >= 2 && (double)lf <= repack_fill * 64.0 * lt && it + 1 < cap) {
-                const int nt = (lf + 63) / 64, nx = 1 - cur;
+                const int nt = (lf + 63) / 64;
+                AdmmDecoder::Set& to = set[1 - cur];
                 const size_t es2 = (size_t)nt * E * 64 * sizeof(double), vs2 = (size_t)nt * n * 64 * sizeof(double);
-                LDPC_TRY(set_z[nx]->reserve(es2));
-                LDPC_TRY(set_l[nx]->reserve(es2));
-                LDPC_TRY(set_x[nx]->reserve(vs2));
-                LDPC_TRY(set_g[nx]->reserve(vs2));
-                LDPC_TRY(set_live[nx]->reserve((size_t)nt * 8));
-                LDPC_TRY(set_fmap[nx]->reserve((size_t)nt * 64 * sizeof(int32_t)));
+                LDPC_TRY(to.z.reserve(es2));
+                LDPC_TRY(to.lam.reserve(es2));
+                LDPC_TRY(to.x.reserve(vs2));
+                LDPC_TRY(to.gam.reserve(vs2));
+                LDPC_TRY(to.live.reserve((size_t)nt * 8));
+                LDPC_TRY(to.fmap.reserve((size_t)nt * 64 * sizeof(int32_t)));
                 LDPC_TRY(d->rbase.reserve(((size_t)cur_tiles + 1) * sizeof(int32_t)));
                 // x_hat of every frame of the old tiles as it stands (frames that left keep it; the moved ones overwrite theirs at the end)
                 hipLaunchKernelGGL(k_admm_out, dim3((n + 3) / 4, cur_tiles), dim3(256), 0, st, x, x_out, B, n, fmap);
                 hipLaunchKernelGGL(k_repack_plan, dim3(1), dim3(1024), 0, st, live, cur_tiles, (int32_t*)d->rbase.p);
                 const int rows_per_wave = 128;
                 const int chunks = (int)((E + n + rows_per_wave - 1) / rows_per_wave);
-                hipLaunchKernelGGL(k_admm_repack, dim3((chunks + 3) / 4, nt), dim3(64, 4), 0, st, z, (double*)set_z[nx]->p, lam, (double*)set_l[nx]->p, x,
-                                   (double*)set_x[nx]->p, gam, (double*)set_g[nx]->p, live, (u64*)set_live[nx]->p, (const int32_t*)d->rbase.p, fmap,
-                                   (int32_t*)set_fmap[nx]->p, cur_tiles, n, E, rows_per_wave);
-                cur = nx;
-                z = (double*)set_z[cur]->p;
-                lam = (double*)set_l[cur]->p;
-                x = (double*)set_x[cur]->p;
-                gam = (double*)set_g[cur]->p;
-                live = (u64*)set_live[cur]->p;
-                fmap = (int32_t*)set_fmap[cur]->p;
+                hipLaunchKernelGGL(k_admm_repack, dim3((chunks + 3) / 4, nt), dim3(64, 4), 0, st, z, (double*)to.z.p, lam, (double*)to.lam.p, x, (double*)to.x.p, gam,
+                                   (double*)to.gam.p, live, (u64*)to.live.p, (const int32_t*)d->rbase.p, fmap, (int32_t*)to.fmap.p, cur_tiles, n, E, rows_per_wave);
+                use_set(1 - cur);
+                fmap = (int32_t*)to.fmap.p;
                 cur_tiles = nt;
                 ++repacks;
             }

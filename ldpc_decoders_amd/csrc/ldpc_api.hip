@@ -2,6 +2,7 @@
 #include <array>
 #include <cstring>
 #include <memory>
+#include <mutex>
 #include <new>
 #include <stdexcept>
 #include <thread>
@@ -26,6 +27,24 @@ void set_error(const char* fmt, ...) {
 }
 const char* last_error() { return g_err.c_str(); }
 
+// Fault injection for tests/test_gpu_packed_bits.py (the chunk-halving retry of decode_dev cannot be reached on a 288 GB card without
+// tens of GB of input): LDPC_TEST_FAIL_RESERVE=K makes the K-th growing reservation from then on ask for 2^50 bytes -- a genuine
+// hipMalloc failure, sticky error included.  Read at every growth and counted from the moment the value changes, so that a test arms
+// it in-process right before the call under test; under a lock, since decoders on several host threads grow their workspaces at once.
+static bool test_fail_this_reservation() {
+    static std::mutex mu;
+    static std::string armed;
+    static int grown = 0;
+    const char* env = getenv("LDPC_TEST_FAIL_RESERVE");
+    std::lock_guard<std::mutex> lock(mu);
+    if (armed != (env ? env : "")) {
+        armed = env ? env : "";
+        grown = 0;
+    }
+    const int k = atoi(armed.c_str());
+    return k > 0 && ++grown == k;
+}
+
 int DevBuf::reserve(size_t need) {
     if (need <= bytes) return LDPC_OK;
     if (p) {
@@ -34,19 +53,7 @@ int DevBuf::reserve(size_t need) {
         bytes = 0;
     }
     const size_t slack = need / 8 < ((size_t)64 << 20) ? need / 8 : ((size_t)64 << 20);  // growth headroom, bounded: workspaces reach 100 GB
-    size_t want = need + slack + 256;
-    // fault injection for tests/test_gpu_packed_bits.py (the chunk-halving retry of decode_dev cannot be reached on a 288 GB card without
-    // tens of GB of input): LDPC_TEST_FAIL_RESERVE=K makes the K-th growing reservation from then on ask for 2^50 bytes -- a genuine
-    // hipMalloc failure, sticky error included
-    // (read at every growth, counted from the moment the value changes, so that a test arms it in-process right before the call under test)
-    static std::string armed;
-    static int grown = 0;
-    const char* env = getenv("LDPC_TEST_FAIL_RESERVE");
-    if (armed != (env ? env : "")) {
-        armed = env ? env : "";
-        grown = 0;
-    }
-    if (env && atoi(env) > 0 && ++grown == atoi(env)) want = (size_t)1 << 50;
+    const size_t want = test_fail_this_reservation() ? (size_t)1 << 50 : need + slack + 256;
     hipError_t e = hipMalloc(&p, want);
     if (e != hipSuccess) {
         p = nullptr;
@@ -109,7 +116,8 @@ int64_t stream_chunk_frames(Decoder* d) {
     int64_t step = (int64_t)1 << 17;
     if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && free_b > 0) {
         // what this decoder already holds is re-used, not needed again
-        const size_t held = d->msg.bytes + d->marg.bytes + d->prior.bytes + d->msg2.bytes + d->marg2.bytes + d->prior2.bytes;
+        size_t held = 0;
+        d->for_each_buffer([&](DevBuf& b, BufKind kind) { held += kind == BUF_STATE ? b.bytes : 0; });
         const double budget = 0.8 * ((double)free_b + (double)held);
         const int64_t fit = (int64_t)(budget / per_frame) / 64 * 64;
         if (fit < step) step = fit < 64 ? 64 : fit;
@@ -121,18 +129,13 @@ int64_t stream_chunk_frames(Decoder* d) {
 // Frees the streaming state (both sets): the chunk-halving retry of decode_dev must give back what the failed, larger reservation had
 // already taken -- buffers reserved before the one that failed keep their full size otherwise and the smaller chunk frees nothing.
 static void release_stream_workspaces(Decoder* d) {
-    for (DevBuf* b : {&d->msg, &d->marg, &d->prior, &d->xbits, &d->xera, &d->live, &d->msg2, &d->marg2, &d->prior2, &d->xbits2, &d->live2, &d->fmap,
-                      &d->fmap2, &d->rmap})
-        b->release();
+    d->for_each_buffer([](DevBuf& b, BufKind kind) {
+        if (kind == BUF_STATE) b.release();
+    });
 }
 
-// d->out_bits is per-call state of the streaming kernels (packed decisions straight from the planes): reset on EVERY exit path, an
-// exception caught by guarded() included -- a stale pointer would send the next plain ldpc_decode's decisions to freed caller memory.
-struct OutBitsScope {
-    Decoder* d;
-    OutBitsScope(Decoder* dec, uint32_t* bits) : d(dec) { d->out_bits = bits; }
-    ~OutBitsScope() { d->out_bits = nullptr; }
-};
+// frames of the next chunk of a walk over B frames in chunks of `step`
+inline int64_t chunk_at(int64_t b0, int64_t B, int64_t step) { return (B - b0) < step ? (B - b0) : step; }
 
 // LDPC_FLAG_PRIOR_GRID arms the exactness guard of the LDS-resident fp32 min-sum kernels.  The streaming kernels have no such guard:
 // a call that asks for it there is refused (as ldpc_simulate refuses it) instead of returning frames nobody vouched for.  fp64 decoders
@@ -349,9 +352,7 @@ int ldpc_decoder_destroy(ldpc_decoder_t h) {
         if (!d) return LDPC_OK;
         (void)hipSetDevice(d->code->device);
         fused_plan_destroy(d);
-        for (DevBuf* b : {&d->msg, &d->marg, &d->marg2, &d->prior, &d->xbits, &d->xera, &d->live, &d->flags, &d->scratch, &d->gridviol, &d->msg2, &d->prior2, &d->xbits2, &d->live2, &d->fmap, &d->fmap2, &d->rbase, &d->rmap, &d->h_in, &d->h_y0, &d->h_out,
-                          &d->h_iters, &d->h_bits, &d->h_era})
-            b->release();
+        d->for_each_buffer([](DevBuf& b, BufKind) { b.release(); });
         if (d->pinned) (void)hipHostFree(d->pinned);
         if (d->lat_pin) (void)hipHostFree(d->lat_pin);
         if (d->lat_event) (void)hipEventDestroy(d->lat_event);
@@ -516,17 +517,19 @@ static int decode_dev(Decoder* d, const char* who, const void* priors, const uin
     const bool planes_direct = bits && bk == BK_STREAM && d->alg != ALG_BEC;
     if (bits && !planes_direct) LDPC_TRY(d->h_out.reserve((size_t)(B < step ? B : step) * n));
     int sweeps = 0;
+    DecodeCall k;
+    k.max_iter = max_iter;
+    k.flags = flags;
+    k.stream = st;
     for (int64_t b0 = 0; b0 < B;) {
-        const int64_t nb = (B - b0) < step ? (B - b0) : step;
-        const void* p = priors ? (const char*)priors + (size_t)b0 * n * esz : nullptr;
-        const uint8_t* y = y0 ? y0 + (size_t)b0 * n : nullptr;
-        uint8_t* xh = bits ? (planes_direct ? nullptr : (uint8_t*)d->h_out.p) : xhat + (size_t)b0 * n;
-        int rc;
-        {
-            OutBitsScope scope(d, planes_direct ? bits + (size_t)b0 * W : nullptr);
-            rc = bk == BK_FUSED ? fused_decode(d, p, y, nb, max_iter, flags, xh, iters + b0, nullptr, st)
-                                : stream_decode(d, p, y, nb, max_iter, flags, xh, iters + b0, nullptr, st);
-        }
+        const int64_t nb = chunk_at(b0, B, step);
+        k.B = nb;
+        k.priors = priors ? (const char*)priors + (size_t)b0 * n * esz : nullptr;
+        k.y0 = y0 ? y0 + (size_t)b0 * n : nullptr;
+        uint8_t* xh = k.xhat = bits ? (planes_direct ? nullptr : (uint8_t*)d->h_out.p) : xhat + (size_t)b0 * n;
+        k.bits = planes_direct ? bits + (size_t)b0 * W : nullptr;
+        k.iters = iters + b0;
+        const int rc = bk == BK_FUSED ? fused_decode(d, k) : stream_decode(d, k);
         if (rc == LDPC_E_NOMEM && bk == BK_STREAM && nb > 64) {
             // the chunk was sized from the memory that was free when this decoder first asked (stream_chunk_frames); other allocations
             // since (a twin decoder, torch tensors) may have taken it: halve the chunk -- for this decoder's lifetime -- give back what
@@ -588,8 +591,10 @@ int ldpc_decode_soft(ldpc_decoder_t h, const void* priors, const uint8_t* y0, in
         const int bk = pick_backend(d);
         if (bk < 0) return bk;
         LDPC_TRY(grid_guard_available(d, bk, flags, "ldpc_decode_soft"));
-        if (bk == BK_FUSED) return fused_decode(d, priors, y0, B, max_iter, flags, xhat, iters, marginals, (hipStream_t)stream);
-        return stream_decode(d, priors, y0, B, max_iter, flags, xhat, iters, marginals, (hipStream_t)stream);
+        DecodeCall k;
+        k.priors = priors; k.y0 = y0; k.B = B; k.max_iter = max_iter; k.flags = flags;
+        k.xhat = xhat; k.iters = iters; k.soft = marginals; k.stream = (hipStream_t)stream;
+        return bk == BK_FUSED ? fused_decode(d, k) : stream_decode(d, k);
     });
 }
 
@@ -675,11 +680,10 @@ static int decode_host_impl(Decoder* d, ldpc_decoder_t h, const void* priors, co
         char* gp = (char*)devp;
         if (d->alg != ALG_BEC) memcpy(hp, priors, in_bytes);
         if (y0) memcpy(hp + off_y, y0, y_bytes);
-        d->after_kernel_event = d->lat_event;
-        const int rc = fused_decode(d, d->alg == ALG_BEC ? nullptr : gp, y0 ? (const uint8_t*)(gp + off_y) : nullptr, B, max_iter, flags,
-                                    (uint8_t*)(gp + off_out), (int32_t*)(gp + off_it), nullptr, d->lat_stream);
-        d->after_kernel_event = nullptr;
-        if (rc) return rc;
+        DecodeCall k;
+        k.priors = d->alg == ALG_BEC ? nullptr : gp; k.y0 = y0 ? (const uint8_t*)(gp + off_y) : nullptr; k.B = B; k.max_iter = max_iter; k.flags = flags;
+        k.xhat = (uint8_t*)(gp + off_out); k.iters = (int32_t*)(gp + off_it); k.stream = d->lat_stream; k.done_event = d->lat_event;
+        LDPC_TRY(fused_decode(d, k));
         LDPC_HIP_TRY(hipEventSynchronize(d->lat_event));
         memcpy(xhat, hp + off_out, y_bytes);
         memcpy(iters, hp + off_it, (size_t)B * sizeof(int32_t));
@@ -842,74 +846,67 @@ int ldpc_count_errors_bits(const uint32_t* xhat_bits, const uint32_t* erased_bit
 static int simulate_impl(ldpc_decoder_t h, int channel, double param, int codeword, uint64_t seed, uint64_t stream_id,
                          uint64_t frame0, int64_t B, int32_t max_iter, uint32_t flags, int32_t hist_bins, int64_t* counters,
                          void* stream) {
-    {
-        Decoder* d = (Decoder*)h;
-        if (!d || !counters || B < 0) {
-            set_error("ldpc_simulate: bad arguments");
-            return LDPC_E_ARG;
-        }
-        if ((channel == CH_BEC) != (d->alg == ALG_BEC)) {
-            set_error("ldpc_simulate: the erasure channel pairs with LDPC_ALG_BEC decoders (and only with them)");
-            return LDPC_E_ARG;
-        }
-        if (B == 0) return LDPC_OK;
-        LDPC_HIP_TRY(hipSetDevice(d->code->device));
-        const size_t n = (size_t)d->code->n, esz = d->dtype == DT_F64 ? 8 : 4;
-        hipStream_t st = (hipStream_t)stream;
-        if (codeword != 0 && codeword != 1) {
-            set_error("device channel kernels send the all-zero (0) or all-one (1) word; got codeword=%d", codeword);
-            return LDPC_E_ARG;
-        }
-        const int grid_k = LDPC_FLAG_PRIOR_GRID_OF(flags);
-        // (fp64 decoders with a prior grid take the composed path below: quantised priors from the channel kernel, no guard needed)
-        if (d->backend != BK_STREAM && fused_simulate_supported(d, channel, param, hist_bins) && !(grid_k >= 0 && d->dtype == DT_F64 && d->alg != ALG_BEC))
-            return fused_simulate(d, channel, param, codeword, seed, stream_id, frame0, B, max_iter, flags, hist_bins, counters, st);
-        if (grid_k >= 0 && (d->dtype != DT_F64 || channel == CH_BEC)) {
-            set_error("prior grid: the exactness guard lives in the LDS-resident fp32 min-sum kernels; this decoder runs on the streaming kernels");
-            return LDPC_E_UNSUPPORTED;
-        }
-        const int ch_grid = grid_k >= 0 ? LDPC_CH_PRIOR_GRID(grid_k) : 0;  // fp64 decoders: quantised priors, no guard needed
-        // bounded staging: priors for at most 2^17 frames at a time (fewer where the streaming state would not fit the HBM)
-        const int64_t step = pick_backend(d) == BK_STREAM ? stream_chunk_frames(d) : (int64_t)1 << 17;
-        const int64_t cap = B < step ? B : step;
-        // BI-AWGN on the streaming kernels: the noise is generated straight into the tile layout (no [B,n] prior array, no transposing load)
-        const bool tiled_noise = channel == CH_BIAWGN && d->alg != ALG_BEC && pick_backend(d) == BK_STREAM && grid_k < 0;
-        // erasure decoder on the streaming kernels: received word drawn into the bit planes, decisions counted from them (no [B,n] bytes at all)
-        if (d->alg == ALG_BEC && pick_backend(d) == BK_STREAM) {
-            for (int64_t b0 = 0; b0 < B; b0 += step) {
-                const int64_t nb = (B - b0) < step ? (B - b0) : step;
-                LDPC_TRY(becs_stream_simulate(d, param, codeword, seed, stream_id, frame0 + (uint64_t)b0, nb, max_iter, flags, hist_bins, counters, st));
-            }
-            return LDPC_OK;
-        }
-        if (channel != CH_BEC && !tiled_noise) LDPC_TRY(d->h_in.reserve((size_t)cap * n * esz));
-        if (channel != CH_BIAWGN) LDPC_TRY(d->h_y0.reserve((size_t)cap * n));
-        if (tiled_noise) LDPC_TRY(d->h_bits.reserve((size_t)cap * ((n + 31) / 32) * 4));  // decisions leave the planes as packed words: no [B,n] bytes
-        else LDPC_TRY(d->h_out.reserve((size_t)cap * n));
-        LDPC_TRY(d->h_iters.reserve((size_t)cap * sizeof(int32_t)));
-        for (int64_t b0 = 0; b0 < B; b0 += step) {
-            const int64_t nb = (B - b0) < step ? (B - b0) : step;
-            if (tiled_noise) {
-                int rc;
-                {
-                    OutBitsScope scope(d, (uint32_t*)d->h_bits.p);
-                    rc = stream_simulate_biawgn(d, param, codeword, seed, stream_id, frame0 + (uint64_t)b0, nb, max_iter, flags, nullptr,
-                                                (int32_t*)d->h_iters.p, st);
-                }
-                if (rc) return rc;
-                LDPC_TRY(count_errors_bits((const uint32_t*)d->h_bits.p, nullptr, nullptr, codeword, (int32_t*)d->h_iters.p, nb, (int32_t)n, hist_bins, counters, st));
-                continue;
-            }
-            void* pri = channel == CH_BEC ? nullptr : d->h_in.p;
-            uint8_t* y = channel == CH_BIAWGN ? nullptr : (uint8_t*)d->h_y0.p;
-            LDPC_TRY(channel_generate(channel | ch_grid, d->dtype == DT_F16 ? DT_F32 : d->dtype, param, codeword, seed, stream_id, frame0 + (uint64_t)b0, nb, (int32_t)n, pri,
-                                      y, st));
-            LDPC_TRY(ldpc_decode(h, pri, y, nb, max_iter, flags, (uint8_t*)d->h_out.p, (int32_t*)d->h_iters.p, stream));
-            LDPC_TRY(count_errors((uint8_t*)d->h_out.p, nullptr, codeword, (int32_t*)d->h_iters.p, nb, (int32_t)n, hist_bins, counters,
-                                  st));
-        }
+    Decoder* d = (Decoder*)h;
+    if (!d || !counters || B < 0) {
+        set_error("ldpc_simulate: bad arguments");
+        return LDPC_E_ARG;
+    }
+    if ((channel == CH_BEC) != (d->alg == ALG_BEC)) {
+        set_error("ldpc_simulate: the erasure channel pairs with LDPC_ALG_BEC decoders (and only with them)");
+        return LDPC_E_ARG;
+    }
+    if (B == 0) return LDPC_OK;
+    LDPC_HIP_TRY(hipSetDevice(d->code->device));
+    const size_t n = (size_t)d->code->n, esz = d->dtype == DT_F64 ? 8 : 4;
+    hipStream_t st = (hipStream_t)stream;
+    if (codeword != 0 && codeword != 1) {
+        set_error("device channel kernels send the all-zero (0) or all-one (1) word; got codeword=%d", codeword);
+        return LDPC_E_ARG;
+    }
+    const int grid_k = LDPC_FLAG_PRIOR_GRID_OF(flags);
+    // (fp64 decoders with a prior grid take the composed path below: quantised priors from the channel kernel, no guard needed)
+    if (d->backend != BK_STREAM && fused_simulate_supported(d, channel, param, hist_bins) && !(grid_k >= 0 && d->dtype == DT_F64 && d->alg != ALG_BEC))
+        return fused_simulate(d, channel, param, codeword, seed, stream_id, frame0, B, max_iter, flags, hist_bins, counters, st);
+    if (grid_k >= 0 && (d->dtype != DT_F64 || channel == CH_BEC)) {
+        set_error("prior grid: the exactness guard lives in the LDS-resident fp32 min-sum kernels; this decoder runs on the streaming kernels");
+        return LDPC_E_UNSUPPORTED;
+    }
+    const int ch_grid = grid_k >= 0 ? LDPC_CH_PRIOR_GRID(grid_k) : 0;  // fp64 decoders: quantised priors, no guard needed
+    const bool streaming = pick_backend(d) == BK_STREAM;
+    // bounded staging: priors for at most 2^17 frames at a time (fewer where the streaming state would not fit the HBM)
+    const int64_t step = streaming ? stream_chunk_frames(d) : (int64_t)1 << 17;
+    const int64_t cap = B < step ? B : step;
+    // BI-AWGN on the streaming kernels: the noise is generated straight into the tile layout (no [B,n] prior array, no transposing load)
+    const bool tiled_noise = channel == CH_BIAWGN && d->alg != ALG_BEC && streaming && grid_k < 0;
+    // erasure decoder on the streaming kernels: received word drawn into the bit planes, decisions counted from them (no [B,n] bytes at all)
+    if (d->alg == ALG_BEC && streaming) {
+        for (int64_t b0 = 0; b0 < B; b0 += step)
+            LDPC_TRY(becs_stream_simulate(d, param, codeword, seed, stream_id, frame0 + (uint64_t)b0, chunk_at(b0, B, step), max_iter, flags, hist_bins, counters, st));
         return LDPC_OK;
     }
+    if (channel != CH_BEC && !tiled_noise) LDPC_TRY(d->h_in.reserve((size_t)cap * n * esz));
+    if (channel != CH_BIAWGN) LDPC_TRY(d->h_y0.reserve((size_t)cap * n));
+    if (tiled_noise) LDPC_TRY(d->h_bits.reserve((size_t)cap * ((n + 31) / 32) * 4));  // decisions leave the planes as packed words: no [B,n] bytes
+    else LDPC_TRY(d->h_out.reserve((size_t)cap * n));
+    LDPC_TRY(d->h_iters.reserve((size_t)cap * sizeof(int32_t)));
+    for (int64_t b0 = 0; b0 < B; b0 += step) {
+        const int64_t nb = chunk_at(b0, B, step);
+        if (tiled_noise) {
+            DecodeCall k;
+            k.B = nb; k.max_iter = max_iter; k.flags = flags; k.bits = (uint32_t*)d->h_bits.p; k.iters = (int32_t*)d->h_iters.p; k.stream = st;
+            LDPC_TRY(stream_simulate_biawgn(d, k, param, codeword, seed, stream_id, frame0 + (uint64_t)b0));
+            LDPC_TRY(count_errors_bits(k.bits, nullptr, nullptr, codeword, k.iters, nb, (int32_t)n, hist_bins, counters, st));
+            continue;
+        }
+        void* pri = channel == CH_BEC ? nullptr : d->h_in.p;
+        uint8_t* y = channel == CH_BIAWGN ? nullptr : (uint8_t*)d->h_y0.p;
+        LDPC_TRY(channel_generate(channel | ch_grid, d->dtype == DT_F16 ? DT_F32 : d->dtype, param, codeword, seed, stream_id, frame0 + (uint64_t)b0, nb, (int32_t)n, pri,
+                                  y, st));
+        LDPC_TRY(ldpc_decode(h, pri, y, nb, max_iter, flags, (uint8_t*)d->h_out.p, (int32_t*)d->h_iters.p, stream));
+        LDPC_TRY(count_errors((uint8_t*)d->h_out.p, nullptr, codeword, (int32_t*)d->h_iters.p, nb, (int32_t)n, hist_bins, counters,
+                              st));
+    }
+    return LDPC_OK;
 }
 
 int ldpc_simulate(ldpc_decoder_t h, int channel, double param, int codeword, uint64_t seed, uint64_t stream_id,

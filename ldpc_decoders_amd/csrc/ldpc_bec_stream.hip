@@ -400,10 +400,14 @@ int upload_i32(const std::vector<T>& h, DevBuf* buf) {
 
 }  // namespace
 
-// Batched bec.SPA.decode (src/bec.py:83-122) on the streaming kernels.  y0 [B, n] symbols, xhat [B, n], iters [B] -- device buffers; or, with
-// `sim`, channel -> decode -> count on the planes (iters [B] is still needed: scratch of the caller).
-static int becs_run(Decoder* d, const uint8_t* y0, const BecsSim* sim, int64_t B, int32_t max_iter, uint32_t flags_in, uint8_t* xhat, int32_t* iters,
-                    hipStream_t st) {
+// Batched bec.SPA.decode (src/bec.py:83-122) on the streaming kernels.  call.y0 [B, n] symbols, call.xhat [B, n], call.iters [B] -- device buffers; or,
+// with `sim`, channel -> decode -> count on the planes (iters [B] is still needed: scratch of the caller).  One state set, never repacked.
+static int becs_run(Decoder* d, const DecodeCall& call, const BecsSim* sim) {
+    const int64_t B = call.B;
+    const int32_t max_iter = call.max_iter;
+    int32_t* const iters = call.iters;
+    const hipStream_t st = call.stream;
+    TileSet& s = d->set[0];
     const Code* c = d->code;
     const int n = c->n, m = c->m;
     const int64_t E = c->E;
@@ -411,10 +415,10 @@ static int becs_run(Decoder* d, const uint8_t* y0, const BecsSim* sim, int64_t B
         set_error("streaming erasure decoder supports variable degrees up to 64 (max_dv=%d)", c->max_dv);
         return LDPC_E_UNSUPPORTED;
     }
-    const bool early = !(flags_in & FLAG_NO_EARLY_EXIT);
+    const bool early = !(call.flags & FLAG_NO_EARLY_EXIT);
     const int tiles = (int)((B + SUPER - 1) / SUPER);
     // graph in variable-major order, once per decoder: edge_vpos[k] = position of row-major edge k in the CSC list, chk_of_pos
-    if (!d->scratch.p) {
+    if (!d->graph_tab.p) {
         std::vector<int32_t> idx((size_t)2 * E);
         for (int v = 0; v < n; ++v)
             for (int p = c->col_ptr[v]; p < c->col_ptr[v + 1]; ++p) {
@@ -422,21 +426,21 @@ static int becs_run(Decoder* d, const uint8_t* y0, const BecsSim* sim, int64_t B
                 idx[(size_t)k] = p;                        // edge_vpos
                 idx[(size_t)E + p] = c->edge_chk[k];       // chk_of_pos
             }
-        LDPC_TRY(upload_i32(idx, &d->scratch));
+        LDPC_TRY(upload_i32(idx, &d->graph_tab));
     }
-    const int32_t* edge_vpos = (const int32_t*)d->scratch.p;
+    const int32_t* edge_vpos = (const int32_t*)d->graph_tab.p;
     const int32_t* chk_of_pos = edge_vpos + E;
-    LDPC_TRY(d->msg.reserve((size_t)tiles * E * 64 * 8));
-    LDPC_TRY(d->marg.reserve((size_t)tiles * m * 64 * 8));
-    LDPC_TRY(d->prior.reserve((size_t)tiles * n * 64 * 8));
-    LDPC_TRY(d->xbits.reserve((size_t)tiles * n * 64 * 8));
-    LDPC_TRY(d->live.reserve((size_t)tiles * 64 * 4));
+    LDPC_TRY(s.edge.reserve((size_t)tiles * E * 64 * 8));
+    LDPC_TRY(s.node.reserve((size_t)tiles * m * 64 * 8));
+    LDPC_TRY(s.prior.reserve((size_t)tiles * n * 64 * 8));
+    LDPC_TRY(s.planes.reserve((size_t)tiles * n * 64 * 8));
+    LDPC_TRY(s.live.reserve((size_t)tiles * 64 * 4));
     LDPC_TRY(d->flags.reserve((size_t)tiles * 2 * 64 * 4 + 64));
-    uint2* v2c = (uint2*)d->msg.p;
-    uint2* sum = (uint2*)d->marg.p;
-    uint2* prior = (uint2*)d->prior.p;
-    uint2* xh = (uint2*)d->xbits.p;
-    uint32_t* live = (uint32_t*)d->live.p;
+    uint2* v2c = (uint2*)s.edge.p;
+    uint2* sum = (uint2*)s.node.p;  // per check
+    uint2* prior = (uint2*)s.prior.p;
+    uint2* xh = (uint2*)s.planes.p;  // value plane + erased plane per variable
+    uint32_t* live = (uint32_t*)s.live.p;
     uint32_t* tflags = (uint32_t*)d->flags.p;
     int* live_tiles = (int*)((char*)d->flags.p + (size_t)tiles * 2 * 64 * 4);
     volatile int* poll_host = (volatile int*)d->pinned;
@@ -448,7 +452,7 @@ static int becs_run(Decoder* d, const uint8_t* y0, const BecsSim* sim, int64_t B
         hipLaunchKernelGGL(k_becs_channel, dim3((unsigned)((bpf + 4 * qpw - 1) / (4 * qpw)), tiles), dim3(256), 0, st, sim->thr, sim->codeword, sim->seed, sim->stream,
                            sim->frame0, B, n, bpf, qpw, prior, xh, live, tflags);
     } else {
-        hipLaunchKernelGGL(k_becs_load, dim3((n + 63) / 64, tiles), dim3(256), 0, st, y0, B, n, prior, xh, live, tflags);
+        hipLaunchKernelGGL(k_becs_load, dim3((n + 63) / 64, tiles), dim3(256), 0, st, call.y0, B, n, prior, xh, live, tflags);
     }
 
     const int cpw = 4, vpw = 8;  // nodes per wave task: short runs keep a supertile's summary lines on chip between the two passes
@@ -494,15 +498,15 @@ static int becs_run(Decoder* d, const uint8_t* y0, const BecsSim* sim, int64_t B
     }
     hipLaunchKernelGGL(k_becs_finish, dim3(tiles), dim3(64), 0, st, live, iters, B, sweeps);
     if (sim) {
-        LDPC_TRY(d->h_out.reserve((size_t)B * sizeof(int32_t)));  // bit errors per frame
-        int32_t* errs = (int32_t*)d->h_out.p;
+        LDPC_TRY(d->sim_errs.reserve((size_t)B * sizeof(int32_t)));  // bit errors per frame
+        int32_t* errs = (int32_t*)d->sim_errs.p;
         LDPC_HIP_TRY(hipMemsetAsync(errs, 0, (size_t)B * sizeof(int32_t), st));
         const int vpb = 1020;
         hipLaunchKernelGGL(k_becs_errs, dim3((n + vpb - 1) / vpb, tiles), dim3(256), 0, st, xh, sim->codeword, n, B, vpb, errs);
         hipLaunchKernelGGL(k_becs_tally, dim3((unsigned)((B + 255) / 256)), dim3(256), (size_t)sim->hist_bins * sizeof(unsigned int), st, errs, iters, B,
                            sim->hist_bins, (unsigned long long*)sim->counters);
     } else {
-        hipLaunchKernelGGL(k_becs_unpack, dim3((n + 63) / 64, tiles), dim3(256), 0, st, xh, xhat, B, n);
+        hipLaunchKernelGGL(k_becs_unpack, dim3((n + 63) / 64, tiles), dim3(256), 0, st, xh, call.xhat, B, n);
     }
     LDPC_HIP_TRY(hipGetLastError());
     d->last_repacks = 0;
@@ -511,9 +515,7 @@ static int becs_run(Decoder* d, const uint8_t* y0, const BecsSim* sim, int64_t B
     return LDPC_OK;
 }
 
-int becs_stream_decode(Decoder* d, const uint8_t* y0, int64_t B, int32_t max_iter, uint32_t flags, uint8_t* xhat, int32_t* iters, hipStream_t st) {
-    return becs_run(d, y0, nullptr, B, max_iter, flags, xhat, iters, st);
-}
+int becs_stream_decode(Decoder* d, const DecodeCall& k) { return becs_run(d, k, nullptr); }
 
 // ldpc_simulate on the streaming erasure decoder: frames [frame0, frame0 + B) of the Philox stream, counters accumulated
 int becs_stream_simulate(Decoder* d, double param, int codeword, uint64_t seed, uint64_t stream_id, uint64_t frame0, int64_t B, int32_t max_iter,
@@ -530,7 +532,9 @@ int becs_stream_simulate(Decoder* d, double param, int codeword, uint64_t seed, 
     if (t < 0) t = 0;
     BecsSim sim{(uint64_t)t, seed, frame0, (uint32_t)stream_id, codeword, hist_bins, counters};
     LDPC_TRY(d->h_iters.reserve((size_t)B * sizeof(int32_t)));
-    return becs_run(d, nullptr, &sim, B, max_iter, flags, nullptr, (int32_t*)d->h_iters.p, st);
+    DecodeCall k;
+    k.B = B; k.max_iter = max_iter; k.flags = flags; k.iters = (int32_t*)d->h_iters.p; k.stream = st;
+    return becs_run(d, k, &sim);
 }
 
 }  // namespace ldpc

@@ -7,6 +7,8 @@
 //     wave-uniform (scalar loads) and every message access is one contiguous 64-element line.
 //   * Streaming backend: per tile, check -> variable messages c2v[tile][edge][64] and marginals marg[tile][n][64] live in HBM;
 //     the check pass forms v2c = marg - c2v_old on the fly, the variable pass rebuilds the marginals (ldpc_stream.hip).
+//     That state is a TileSet; a Decoder holds two (a frame repack gathers the live frames from one into the other) beside
+//     the few tables both share.  A decode call's arguments travel in a DecodeCall, never in the Decoder.
 //   * Fused backend (regular codes whose state fits the LDS): one wavefront owns one frame for all
 //     iterations; messages never leave the CU.
 #pragma once
@@ -80,16 +82,62 @@ struct DevBuf {
 
 struct FusedPlan;  // ldpc_fused.hip
 
+// Arguments of ONE decode call (ldpc_api.hip builds one per chunk of frames): nothing of a call is kept in the Decoder.
+struct DecodeCall {
+    const void* priors = nullptr;  // [B, n] LLRs in the decoder's precision (LLR decoders)
+    const uint8_t* y0 = nullptr;   // [B, n] received symbols (erasure decoder; optional first syndrome check of the LLR decoders)
+    int64_t B = 0;
+    int32_t max_iter = 0;
+    uint32_t flags = 0;
+    uint8_t* xhat = nullptr;   // decisions as bytes [B, n] ...
+    uint32_t* bits = nullptr;  // ... or, if set, as packed words [B, ceil(n/32)] straight from the planes (streaming LLR decoders only)
+    int32_t* iters = nullptr;
+    void* soft = nullptr;  // [B, n] marginals of the last sweep (ldpc_decode_soft)
+    hipStream_t stream = nullptr;
+    hipEvent_t done_event = nullptr;  // LDS-resident backend: recorded right behind the decode kernel (low-latency host path)
+};
+
+// One state set of the streaming decoders: what exists once per set and moves together in a frame repack.
+struct TileSet {
+    DevBuf edge;    // one line per edge: check -> variable messages (fp32 / fp64), variable -> check messages (fp16 storage, erasure)
+    DevBuf node;    // one line per node: marginals per variable (LLR decoders; fp16 storage: only with a soft output), summaries per check (erasure)
+    DevBuf prior;   // one line per variable
+    DevBuf planes;  // decision (erasure: value + erased) bit planes per variable
+    DevBuf live;    // live-frame words per tile
+    DevBuf fmap;    // frame index of (tile, lane) once repacked
+};
+
+enum BufKind : int {
+    BUF_STATE = 0,    // streaming state, sized by the chunk of frames: given back by the chunk-halving retry, counted as re-usable
+    BUF_SHARED = 1,   // small tables that live as long as the decoder
+    BUF_STAGING = 2,  // staging of the *_host and simulate entry points
+};
+
 struct Decoder {
     Code* code = nullptr;
     int alg = ALG_MSA, dtype = DT_F32, backend = BK_AUTO;
-    // streaming workspace
-    DevBuf msg, marg, prior, xbits, xera, live, flags, scratch;  // msg = check -> variable messages
-    DevBuf msg2, marg2, prior2, xbits2, live2, fmap, fmap2, rbase, rmap;  // second state set + frame maps of the early-termination repack
+    // streaming workspace: set[0] holds the state when a decode begins, every frame repack moves it to the other set
+    TileSet set[2];
+    DevBuf c2v16;      // fp16 storage: check -> variable lines, rebuilt by every check pass (not part of a set: a repack does not move them)
+    DevBuf rmap;       // folded repack: source (tile, lane) of every frame of the new set
+    DevBuf rbase;      // repack plan: first destination slot of every source tile
+    DevBuf flags;      // per-tile syndrome flags + the device poll words behind them
+    DevBuf graph_tab;  // variable-major view of the graph, built once (fp16 storage: edge_vpos; erasure: edge_vpos + chk_of_pos)
+    DevBuf gridviol;   // exact-in-fp32 mode: device counter of guard events (LDPC_FLAG_PRIOR_GRID, ldpc_decoder_grid_violations)
+    // staging: priors / received symbols / decisions / iteration counts of the *_host and simulate entry points, packed decisions and
+    // erased mask of ldpc_decode_host, bit errors per frame of the streaming erasure simulation
+    DevBuf h_in, h_y0, h_out, h_iters, h_bits, h_era, sim_errs;
+    // THE list of a decoder's device buffers: destroy, the halving retry and the chunk sizing all walk it
+    template <class F>
+    void for_each_buffer(F&& f) {
+        for (TileSet& s : set)
+            for (DevBuf* b : {&s.edge, &s.node, &s.prior, &s.planes, &s.live, &s.fmap}) f(*b, BUF_STATE);
+        for (DevBuf* b : {&c2v16, &rmap}) f(*b, BUF_STATE);
+        for (DevBuf* b : {&rbase, &flags, &graph_tab, &gridviol}) f(*b, BUF_SHARED);
+        for (DevBuf* b : {&h_in, &h_y0, &h_out, &h_iters, &h_bits, &h_era, &sim_errs}) f(*b, BUF_STAGING);
+    }
     // fused backend
     FusedPlan* fused = nullptr;
-    // staging used by the *_host entry points
-    DevBuf h_in, h_y0, h_out, h_iters;
     void* pinned = nullptr;  // small page-locked host block (polling word, counters)
     // low-latency host path (ldpc_decode_host, a few frames per call -- the reference's one-frame-per-call loop, src/main.py:37-48):
     // page-locked, device-mapped staging the decode kernel reads priors from and writes decisions to DIRECTLY (no copy engine in the
@@ -98,7 +146,6 @@ struct Decoder {
     size_t lat_bytes = 0;
     hipStream_t lat_stream = nullptr;
     hipEvent_t lat_event = nullptr;
-    hipEvent_t after_kernel_event = nullptr;  // set for the duration of a low-latency call
     // optional per-kernel timing with HIP events recorded on the decode stream (bench.py roofline leg)
     bool profile = false;
     std::vector<hipEvent_t> ev_pool;
@@ -108,13 +155,7 @@ struct Decoder {
     int last_sweeps = 0;
     int last_backend = BK_STREAM;
     int last_repacks = 0;  // frame repacks of the last streaming decode
-    // exact-in-fp32 mode: device counter of guard events (LDPC_FLAG_PRIOR_GRID, ldpc_decoder_grid_violations)
-    DevBuf gridviol;
-    // ldpc_decode_bits: for the duration of that call the streaming kernels write their decisions here as packed words [B, ceil(n/32)]
-    // instead of bytes (null otherwise)
-    uint32_t* out_bits = nullptr;
     int chunk_retries = 0;  // how often decode_dev halved the streaming chunk after a failed reservation (ldpc_decoder_chunk_state)
-    DevBuf h_bits, h_era;  // packed staging of ldpc_decode_host (decisions, erased mask)
     int64_t stream_chunk = 0;  // frames per pass through the streaming kernels (0: not decided yet; ldpc_api.hip stream_chunk_frames)
 };
 
@@ -127,16 +168,14 @@ int prof_event(Decoder* d, size_t idx, hipEvent_t* out);
 int prof_collect(Decoder* d, const std::vector<ProfSpan>& spans);
 
 // ---- backends (each returns an LDPC_* code) -------------------------------------------------------
-int stream_decode(Decoder* d, const void* priors, const uint8_t* y0, int64_t B, int32_t max_iter, uint32_t flags,
-                  uint8_t* xhat, int32_t* iters, void* soft_out, hipStream_t st);
+int stream_decode(Decoder* d, const DecodeCall& k);
 
 // bit-sliced erasure decoder on the streaming kernels (ldpc_bec_stream.hip)
-int becs_stream_decode(Decoder* d, const uint8_t* y0, int64_t B, int32_t max_iter, uint32_t flags, uint8_t* xhat, int32_t* iters, hipStream_t st);
+int becs_stream_decode(Decoder* d, const DecodeCall& k);
 int becs_stream_simulate(Decoder* d, double param, int codeword, uint64_t seed, uint64_t stream_id, uint64_t frame0, int64_t B, int32_t max_iter,
                          uint32_t flags, int32_t hist_bins, int64_t* counters, hipStream_t st);
 
-int stream_simulate_biawgn(Decoder* d, double param, int codeword, uint64_t seed, uint64_t stream_id, uint64_t frame0, int64_t B,
-                           int32_t max_iter, uint32_t flags, uint8_t* xhat, int32_t* iters, hipStream_t st);
+int stream_simulate_biawgn(Decoder* d, const DecodeCall& k, double param, int codeword, uint64_t seed, uint64_t stream_id, uint64_t frame0);
 
 int fused_plan_create(Decoder* d);
 int fused_plan_host(const Code* c, int alg, int dtype, long moves, const char* out_dir, double* info4);  // host only, no device
@@ -148,8 +187,7 @@ int fused_simulate(Decoder* d, int channel, double param, int codeword, uint64_t
 bool fused_simulate_rounds_supported(const Decoder* d);
 int fused_info(const Decoder* d, double* out8);
 int fused_kernel_name(const Decoder* d, bool sim, char* buf, size_t len);
-int fused_decode(Decoder* d, const void* priors, const uint8_t* y0, int64_t B, int32_t max_iter, uint32_t flags,
-                 uint8_t* xhat, int32_t* iters, void* soft_out, hipStream_t st);
+int fused_decode(Decoder* d, const DecodeCall& k);
 
 // ---- channel / counting kernels -------------------------------------------------------------------
 int channel_generate(int channel, int dtype, double param, int codeword, uint64_t seed, uint64_t stream_id,

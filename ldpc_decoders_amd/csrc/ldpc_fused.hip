@@ -645,7 +645,8 @@ void fused_plan_destroy(Decoder* d) {
     d->fused = nullptr;
 }
 
-static int fused_launch(Decoder* d, FusedArgs& a, bool sim, int64_t B, int32_t max_iter, uint32_t flags, hipStream_t st) {
+// done_event (low-latency host path): recorded right behind the kernel; such calls draw from a frame dispenser of their own
+static int fused_launch(Decoder* d, FusedArgs& a, bool sim, int64_t B, int32_t max_iter, uint32_t flags, hipStream_t st, hipEvent_t done_event = nullptr) {
     FusedPlan* p = d->fused;
     if (B >= ((int64_t)1 << 31)) {
         set_error("fused backend: at most 2^31-1 frames per call");
@@ -653,7 +654,7 @@ static int fused_launch(Decoder* d, FusedArgs& a, bool sim, int64_t B, int32_t m
     }
     const ShapeEntry& shape = all_shapes()[p->shape];
     const Code* c = d->code;
-    FusedPlan::Dispenser& dsp = p->disp[d->after_kernel_event ? 1 : 0];
+    FusedPlan::Dispenser& dsp = p->disp[done_event ? 1 : 0];
     if (!dsp.d) LDPC_HIP_TRY(hipMalloc((void**)&dsp.d, 2 * 8 * 64));
     unsigned long long* next_set = dsp.d + (size_t)dsp.sel * 64;
     if (!(dsp.clean && dsp.stream == st)) LDPC_HIP_TRY(hipMemsetAsync(next_set, 0, 8 * 64, st));
@@ -723,7 +724,7 @@ static int fused_launch(Decoder* d, FusedArgs& a, bool sim, int64_t B, int32_t m
         LDPC_HIP_TRY(hipEventRecord(e0, st));
     }
     LDPC_HIP_TRY(hipLaunchKernel(kern, dim3((unsigned)groups), dim3(64 * shape.NW), args, p->lds_bytes, st));
-    if (d->after_kernel_event) LDPC_HIP_TRY(hipEventRecord(d->after_kernel_event, st));  // low-latency host path: wait for the kernel only
+    if (done_event) LDPC_HIP_TRY(hipEventRecord(done_event, st));  // low-latency host path: wait for the kernel only
     // the other counter set for the next launch, zeroed behind this kernel (off the critical path of both launches)
     dsp.sel ^= 1;
     dsp.clean = hipMemsetAsync(dsp.d + (size_t)dsp.sel * 64, 0, 8 * 64, st) == hipSuccess;
@@ -738,25 +739,24 @@ static int fused_launch(Decoder* d, FusedArgs& a, bool sim, int64_t B, int32_t m
     return LDPC_OK;
 }
 
-int fused_decode(Decoder* d, const void* priors, const uint8_t* y0, int64_t B, int32_t max_iter, uint32_t flags,
-                 uint8_t* xhat, int32_t* iters, void* soft_out, hipStream_t st) {
+int fused_decode(Decoder* d, const DecodeCall& k) {
     FusedPlan* p = d->fused;
     if (!p || !p->ok) {
         set_error("fused backend not available for this decoder");
         return LDPC_E_UNSUPPORTED;
     }
-    if (B <= 0) return LDPC_OK;
-    if (d->alg == ALG_BEC ? !y0 : !priors) {
+    if (k.B <= 0) return LDPC_OK;
+    if (d->alg == ALG_BEC ? !k.y0 : !k.priors) {
         set_error(d->alg == ALG_BEC ? "erasure decoder needs the received symbols (y0)" : "priors pointer is null");
         return LDPC_E_ARG;
     }
     FusedArgs a{};
-    a.priors = priors;
-    a.y0 = y0;
-    a.xhat = xhat;
-    a.iters = iters;
-    a.soft = soft_out;
-    return fused_launch(d, a, false, B, max_iter, flags, st);
+    a.priors = k.priors;
+    a.y0 = k.y0;
+    a.xhat = k.xhat;
+    a.iters = k.iters;
+    a.soft = k.soft;
+    return fused_launch(d, a, false, k.B, k.max_iter, k.flags, k.stream, k.done_event);
 }
 
 // channel -> LLR -> decode -> count in ONE kernel (BI-AWGN, all-`codeword` word): priors never touch HBM.

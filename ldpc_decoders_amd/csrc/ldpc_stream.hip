@@ -29,6 +29,7 @@
 
 #include <cstdlib>
 #include <string>
+#include <type_traits>
 
 #include "ldpc_cn.hpp"
 #include "ldpc_common.hpp"
@@ -541,17 +542,131 @@ __global__ __launch_bounds__(256) void k_unpack_bits(const u64* __restrict__ xbi
 }
 
 // decisions of the frames of `tiles` tiles in the form the caller asked for: bytes [B,n] (ldpc_decode) or packed words (ldpc_decode_bits)
-void launch_unpack(const Decoder* d, const u64* xbits, uint8_t* xhat, int64_t B, int n, int tiles, const int32_t* fmap, hipStream_t st) {
-    if (d->out_bits)
-        hipLaunchKernelGGL(k_unpack_bits, dim3(((n + 63) / 64 + 3) / 4, tiles), dim3(64, 4), 0, st, xbits, d->out_bits, B, n, (n + 31) / 32, fmap);
+void launch_unpack(const DecodeCall& k, const u64* xbits, int n, int tiles, const int32_t* fmap) {
+    if (k.bits)
+        hipLaunchKernelGGL(k_unpack_bits, dim3(((n + 63) / 64 + 3) / 4, tiles), dim3(64, 4), 0, k.stream, xbits, k.bits, k.B, n, (n + 31) / 32, fmap);
     else
-        hipLaunchKernelGGL(k_unpack, dim3((n + 255) / 256, tiles), dim3(256), 0, st, xbits, xhat, B, n, fmap);
+        hipLaunchKernelGGL(k_unpack, dim3((n + 255) / 256, tiles), dim3(256), 0, k.stream, xbits, k.xhat, k.B, n, fmap);
+}
+
+// syndrome of the decisions of `tiles` tiles: frames that satisfy every check leave (live bit cleared, iteration count written); with
+// `poll_dev` the live tiles / live frames are added into it
+void launch_syndrome(const Code* c, const DecodeCall& k, const u64* xbits, u64* live, u64* tflags, int* poll_dev, int tiles, int sweeps, const int32_t* fmap) {
+    // groups of eight tiles x chunks of the checks: enough blocks to fill the chip (about 4 per CU), at least 1024 checks each
+    const int groups = (tiles + 7) / 8;
+    int sblocks = (1024 + groups - 1) / groups;
+    const int smax = (c->m + 1023) / 1024;
+    sblocks = sblocks < 1 ? 1 : (sblocks > smax ? smax : sblocks);
+    const int cpb = (c->m + sblocks - 1) / sblocks;
+    hipLaunchKernelGGL(k_syndrome_part, dim3(sblocks, groups), dim3(256), 0, k.stream, c->d_row_ptr, c->d_edge_var, xbits, live, tflags, c->m, c->n, tiles, cpb);
+    hipLaunchKernelGGL(k_syndrome_fin, dim3(tiles), dim3(64), 0, k.stream, tflags, live, k.iters, poll_dev, k.B, sweeps, fmap);
+}
+
+// what every LLR decode ends with: iteration counts of the frames still live, decisions in the form the caller asked for
+void launch_decisions(const DecodeCall& k, const u64* xbits, const u64* live, int n, int tiles, int sweeps, const int32_t* fmap) {
+    hipLaunchKernelGGL(k_finish_iters, dim3(tiles), dim3(64), 0, k.stream, live, k.iters, k.B, sweeps, fmap);
+    launch_unpack(k, xbits, n, tiles, fmap);
+}
+
+bool degrees_supported(const Code* c) {
+    if (c->max_dc <= 64 && c->max_dv <= 64) return true;
+    set_error("streaming backend supports node degrees up to 64 (max_dc=%d, max_dv=%d)", c->max_dc, c->max_dv);
+    return false;
+}
+
+// Frame repack (see k_repack): LLR decoders without soft output.  Policy: at a poll, when the live frames would fill less than
+// `fill` of the tiles that still hold one, gather them into dense tiles -- a repack moves (E + 2n) lines per tile once, a sweep
+// moves about (3E + 3n), so it pays as soon as about one more sweep follows.  Read from the environment at the top of every decode.
+struct RepackPolicy {
+    bool on;
+    double fill = 0.75;
+    explicit RepackPolicy(bool eligible) : on(eligible) {
+        if (const char* e = std::getenv("LDPC_STREAM_REPACK")) on = on && atoi(e) != 0;
+        if (const char* e = std::getenv("LDPC_STREAM_REPACK_FILL")) fill = atof(e);
+        if (fill > 0.95) fill = 0.95;
+    }
+    // (a "rent or buy" schedule -- repack once the tile-sweeps spent on departed lanes reach the cost of a repack -- was measured within
+    // the run-to-run spread of this rule in round 5 and removed in round 6: HISTORY.md)
+    bool wants(int live_tiles, int live_frames) const { return live_tiles >= 2 && (double)live_frames <= fill * 64.0 * live_tiles; }
+};
+
+// Per-kernel timing of a decode when Decoder::profile is set (no-ops otherwise): event pairs around the two passes of every sweep
+// (kinds 0 and 1) and, optionally, around the whole decode (kind 3).  `next`: first free entry of the decoder's event pool.
+struct DecodeProf {
+    Decoder* d;
+    hipStream_t st;
+    size_t next;
+    hipEvent_t e[3] = {}, whole[2] = {};
+    std::vector<ProfSpan> spans = {};
+    int begin_decode() {
+        if (!d->profile) return LDPC_OK;
+        for (hipEvent_t& x : whole) LDPC_TRY(prof_event(d, next++, &x));
+        LDPC_HIP_TRY(hipEventRecord(whole[0], st));
+        return LDPC_OK;
+    }
+    int mark(int i) {  // 0: a sweep begins, 1: between its passes, 2: behind it
+        if (!d->profile) return LDPC_OK;
+        if (i == 0)
+            for (hipEvent_t& x : e) LDPC_TRY(prof_event(d, next++, &x));
+        LDPC_HIP_TRY(hipEventRecord(e[i], st));
+        if (i == 2) spans.insert(spans.end(), {{0, e[0], e[1]}, {1, e[1], e[2]}});
+        return LDPC_OK;
+    }
+    int collect() {
+        if (!d->profile) return LDPC_OK;
+        if (whole[0]) LDPC_HIP_TRY(hipEventRecord(whole[1], st));
+        LDPC_HIP_TRY(hipStreamSynchronize(st));
+        LDPC_TRY(prof_collect(d, spans));
+        if (whole[0]) LDPC_TRY(prof_collect(d, {{3, whole[0], whole[1]}}));  // everything the decode enqueued: the two passes + load, syndrome, repack, unpack kernels
+        return LDPC_OK;
+    }
+};
+
+// the host side of every LLR decode ends here: launch errors, profile, statistics of the call
+int end_decode(Decoder* d, DecodeProf& prof, int sweeps, int repacks) {
+    LDPC_HIP_TRY(hipGetLastError());
+    LDPC_TRY(prof.collect());
+    d->last_repacks = repacks;
+    d->last_sweeps = sweeps;
+    d->last_backend = BK_STREAM;
+    return LDPC_OK;
 }
 
 int pick_pow2_ge(int x, int lo, int hi) {
     int p = lo;
     while (p < x && p < hi) p <<= 1;
     return p;
+}
+
+// Degree classes of the pass kernels, handed to f as std::integral_constants (f is a generic lambda that launches the instantiation).
+template <int V>
+using int_c = std::integral_constant<int, V>;
+template <class F>
+void pow2_class(int deg, F&& f) {
+    switch (pick_pow2_ge(deg, 4, 64)) {
+        case 4: return f(int_c<4>{}, int_c<0>{});
+        case 8: return f(int_c<8>{}, int_c<0>{});
+        case 16: return f(int_c<16>{}, int_c<0>{});
+        case 32: return f(int_c<32>{}, int_c<0>{});
+        default: return f(int_c<64>{}, int_c<0>{});
+    }
+}
+// checks -> f(DCMAX, FIXED_DC): regular dc = 6; degrees up to 6 (the rho = x^5 ensembles: no lines fetched for positions that never
+// exist); else the next power of two
+template <class F>
+void check_class(const Code* c, F&& f) {
+    if (c->min_dc == c->max_dc && c->max_dc == 6) return f(int_c<6>{}, int_c<6>{});
+    if (c->max_dc > 4 && c->max_dc <= 6) return f(int_c<6>{}, int_c<0>{});
+    pow2_class(c->max_dc, f);
+}
+// variables -> f(DVMAX, FIXED_DV): (3, r)-regular codes; regular dv = 4 where the pass has that form (FIXED4); else the next power of two
+template <bool FIXED4, class F>
+void var_class(const Code* c, F&& f) {
+    const bool regular = c->min_dv == c->max_dv;
+    if (regular && c->max_dv == 3) return f(int_c<3>{}, int_c<3>{});
+    if constexpr (FIXED4)
+        if (regular && c->max_dv == 4) return f(int_c<4>{}, int_c<4>{});
+    pow2_class(c->max_dv, f);
 }
 
 // nodes kept in flight per wave: about 32 VGPRs (128 bytes per lane) of messages, at most 4 nodes
@@ -566,90 +681,28 @@ struct Geometry {
     int freeze = 0;  // lanes of departed frames do not compute or store (soft-output decodes)
 };
 
-template <typename T, int ALG, int DCMAX, int FIXED_DC>
-void launch_cn(const Code* c, T* c2v, const T* src, const u64* live, const Geometry& g, int first, hipStream_t st) {
-    constexpr int UNR = unroll_for(2 * DCMAX * (int)sizeof(T));  // old message + marginal line per edge
-    hipLaunchKernelGGL((k_cn<T, ALG, DCMAX, FIXED_DC, UNR>), dim3(task_blocks(g.tiles, g.cn_chunks, g.xcd_aware)), dim3(64, 4), 0, st, c->d_row_ptr,
-                       c->d_edge_var, c2v, src, live, c->m, c->n, c->E, g.tiles, g.cn_chunks, g.cpw, first, g.xcd_aware, g.freeze);
-}
-
-template <typename T, int ALG, int DVMAX, int FIXED_DV = 0>
-void launch_vn(const Code* c, const T* c2v, const T* prior, T* marg, const u64* live, u64* xbits, const Geometry& g, hipStream_t st) {
-    constexpr int UNR = unroll_for((DVMAX + 1) * (int)sizeof(T));
-    hipLaunchKernelGGL((k_vn<T, ALG, DVMAX, UNR, FIXED_DV>), dim3(task_blocks(g.tiles, g.vn_chunks, g.xcd_aware)), dim3(64, 4), 0, st, c->d_col_ptr, c->d_col_edge,
-                       c2v, prior, marg, live, xbits, c->n, c->E, g.tiles, g.vn_chunks, g.vpw, g.xcd_aware, g.freeze);
-}
-
-// GATHER variants of the two passes (folded repack): built for the node degrees the LDPC ensembles of the reference have (dc <= 8, dv <= 8)
-template <typename T, int ALG, int DCMAX, int FIXED_DC>
-void launch_cn_gather(const Code* c, T* c2v, const T* c2v_in, const T* src, const u64* live, const int32_t* srcmap, const Geometry& g, hipStream_t st) {
-    constexpr int UNR = unroll_for(2 * DCMAX * (int)sizeof(T));
-    hipLaunchKernelGGL((k_cn<T, ALG, DCMAX, FIXED_DC, UNR, true>), dim3(task_blocks(g.tiles, g.cn_chunks, g.xcd_aware)), dim3(64, 4), 0, st, c->d_row_ptr,
-                       c->d_edge_var, c2v, src, live, c->m, c->n, c->E, g.tiles, g.cn_chunks, g.cpw, 0, g.xcd_aware, 0, c2v_in, srcmap);
-}
-template <typename T, int ALG, int DVMAX, int FIXED_DV = 0>
-void launch_vn_gather(const Code* c, const T* c2v, const T* prior_in, T* prior_out, T* marg, const u64* live, u64* xbits, const int32_t* srcmap,
-                      const Geometry& g, hipStream_t st) {
-    constexpr int UNR = unroll_for((DVMAX + 1) * (int)sizeof(T));
-    hipLaunchKernelGGL((k_vn<T, ALG, DVMAX, UNR, FIXED_DV, true>), dim3(task_blocks(g.tiles, g.vn_chunks, g.xcd_aware)), dim3(64, 4), 0, st, c->d_col_ptr,
-                       c->d_col_edge, c2v, prior_in, marg, live, xbits, c->n, c->E, g.tiles, g.vn_chunks, g.vpw, g.xcd_aware, 0, prior_out, srcmap);
-}
+// The two passes.  GATHER (c2v_in / prior_out + srcmap): the sweep that carries a folded repack; those forms are built for the node
+// degrees the LDPC ensembles of the reference have (dc <= 8, dv <= 8).
 inline bool gather_passes_built(const Code* c) { return c->max_dc <= 8 && c->max_dv <= 8; }
-template <typename T, int ALG>
-void dispatch_cn_gather(const Code* c, T* c2v, const T* c2v_in, const T* src, const u64* live, const int32_t* srcmap, const Geometry& g, hipStream_t st) {
-    if (c->min_dc == c->max_dc && c->max_dc == 6) launch_cn_gather<T, ALG, 6, 6>(c, c2v, c2v_in, src, live, srcmap, g, st);
-    else if (c->max_dc > 4 && c->max_dc <= 6) launch_cn_gather<T, ALG, 6, 0>(c, c2v, c2v_in, src, live, srcmap, g, st);
-    else if (c->max_dc <= 4) launch_cn_gather<T, ALG, 4, 0>(c, c2v, c2v_in, src, live, srcmap, g, st);
-    else launch_cn_gather<T, ALG, 8, 0>(c, c2v, c2v_in, src, live, srcmap, g, st);
+template <typename T, int ALG, bool GATHER = false>
+void dispatch_cn(const Code* c, T* c2v, const T* src, const u64* live, const Geometry& g, int first, hipStream_t st, const T* c2v_in = nullptr,
+                 const int32_t* srcmap = nullptr) {
+    check_class(c, [&](auto dcm, auto fdc) {
+        constexpr int DCMAX = decltype(dcm)::value, UNR = unroll_for(2 * DCMAX * (int)sizeof(T));  // old message + marginal line per edge
+        if constexpr (!GATHER || DCMAX <= 8)
+            hipLaunchKernelGGL((k_cn<T, ALG, DCMAX, decltype(fdc)::value, UNR, GATHER>), dim3(task_blocks(g.tiles, g.cn_chunks, g.xcd_aware)), dim3(64, 4), 0, st,
+                               c->d_row_ptr, c->d_edge_var, c2v, src, live, c->m, c->n, c->E, g.tiles, g.cn_chunks, g.cpw, first, g.xcd_aware, g.freeze, c2v_in, srcmap);
+    });
 }
-template <typename T, int ALG>
-void dispatch_vn_gather(const Code* c, const T* c2v, const T* prior_in, T* prior_out, T* marg, const u64* live, u64* xbits, const int32_t* srcmap,
-                        const Geometry& g, hipStream_t st) {
-    if (c->min_dv == c->max_dv && c->max_dv == 3) launch_vn_gather<T, ALG, 3, 3>(c, c2v, prior_in, prior_out, marg, live, xbits, srcmap, g, st);
-    else if (c->min_dv == c->max_dv && c->max_dv == 4) launch_vn_gather<T, ALG, 4, 4>(c, c2v, prior_in, prior_out, marg, live, xbits, srcmap, g, st);
-    else if (c->max_dv <= 4) launch_vn_gather<T, ALG, 4>(c, c2v, prior_in, prior_out, marg, live, xbits, srcmap, g, st);
-    else launch_vn_gather<T, ALG, 8>(c, c2v, prior_in, prior_out, marg, live, xbits, srcmap, g, st);
-}
-
-template <typename T, int ALG>
-int dispatch_cn(const Code* c, T* c2v, const T* src, const u64* live, const Geometry& g, int first, hipStream_t st) {
-    const bool regular = c->min_dc == c->max_dc;
-    if (regular && c->max_dc == 6) {
-        launch_cn<T, ALG, 6, 6>(c, c2v, src, live, g, first, st);
-        return 0;
-    }
-    if (c->max_dc > 4 && c->max_dc <= 6) {  // check degrees up to 6 (the rho = x^5 ensembles): no lines fetched for positions that never exist
-        launch_cn<T, ALG, 6, 0>(c, c2v, src, live, g, first, st);
-        return 0;
-    }
-    switch (pick_pow2_ge(c->max_dc, 4, 64)) {
-        case 4: launch_cn<T, ALG, 4, 0>(c, c2v, src, live, g, first, st); break;
-        case 8: launch_cn<T, ALG, 8, 0>(c, c2v, src, live, g, first, st); break;
-        case 16: launch_cn<T, ALG, 16, 0>(c, c2v, src, live, g, first, st); break;
-        case 32: launch_cn<T, ALG, 32, 0>(c, c2v, src, live, g, first, st); break;
-        default: launch_cn<T, ALG, 64, 0>(c, c2v, src, live, g, first, st); break;
-    }
-    return 0;
-}
-
-template <typename T, int ALG>
-int dispatch_vn(const Code* c, const T* c2v, const T* prior, T* marg, const u64* live, u64* xbits, const Geometry& g, hipStream_t st) {
-    if (c->min_dv == c->max_dv && c->max_dv == 3) {  // (3, r)-regular codes
-        launch_vn<T, ALG, 3, 3>(c, c2v, prior, marg, live, xbits, g, st);
-        return 0;
-    }
-    if (c->min_dv == c->max_dv && c->max_dv == 4) {
-        launch_vn<T, ALG, 4, 4>(c, c2v, prior, marg, live, xbits, g, st);
-        return 0;
-    }
-    switch (pick_pow2_ge(c->max_dv, 4, 64)) {
-        case 4: launch_vn<T, ALG, 4>(c, c2v, prior, marg, live, xbits, g, st); break;
-        case 8: launch_vn<T, ALG, 8>(c, c2v, prior, marg, live, xbits, g, st); break;
-        case 16: launch_vn<T, ALG, 16>(c, c2v, prior, marg, live, xbits, g, st); break;
-        case 32: launch_vn<T, ALG, 32>(c, c2v, prior, marg, live, xbits, g, st); break;
-        default: launch_vn<T, ALG, 64>(c, c2v, prior, marg, live, xbits, g, st); break;
-    }
-    return 0;
+template <typename T, int ALG, bool GATHER = false>
+void dispatch_vn(const Code* c, const T* c2v, const T* prior, T* marg, const u64* live, u64* xbits, const Geometry& g, hipStream_t st, T* prior_out = nullptr,
+                 const int32_t* srcmap = nullptr) {
+    var_class<true>(c, [&](auto dvm, auto fdv) {
+        constexpr int DVMAX = decltype(dvm)::value, UNR = unroll_for((DVMAX + 1) * (int)sizeof(T));
+        if constexpr (!GATHER || DVMAX <= 8)
+            hipLaunchKernelGGL((k_vn<T, ALG, DVMAX, UNR, decltype(fdv)::value, GATHER>), dim3(task_blocks(g.tiles, g.vn_chunks, g.xcd_aware)), dim3(64, 4), 0, st,
+                               c->d_col_ptr, c->d_col_edge, c2v, prior, marg, live, xbits, c->n, c->E, g.tiles, g.vn_chunks, g.vpw, g.xcd_aware, g.freeze, prior_out, srcmap);
+    });
 }
 
 int env_int(const char* name, int dflt) {
@@ -667,60 +720,62 @@ struct PendingPoll {
 constexpr int POLL_RING = 4;
 
 template <typename T, int ALG>
-int run(Decoder* d, const void* priors_v, const uint8_t* y0, int64_t B, int32_t max_iter, uint32_t flags_in, uint8_t* xhat,
-        int32_t* iters, void* soft_out, hipStream_t st, const SimSource* sim = nullptr) {
+int run(Decoder* d, const DecodeCall& k, const SimSource* sim = nullptr) {
     const Code* c = d->code;
     const int n = c->n, m = c->m;
-    const int64_t E = c->E;
+    const int64_t E = c->E, B = k.B;
+    const int32_t max_iter = k.max_iter;
+    const uint8_t* const y0 = k.y0;
+    int32_t* const iters = k.iters;
+    const hipStream_t st = k.stream;
     const int tiles = (int)((B + 63) / 64);
-    if (c->max_dc > 64 || c->max_dv > 64) {
-        set_error("streaming backend supports node degrees up to 64 (max_dc=%d, max_dv=%d)", c->max_dc, c->max_dv);
-        return LDPC_E_UNSUPPORTED;
-    }
-    const bool early = !(flags_in & FLAG_NO_EARLY_EXIT);
-    // Frame repack (see k_repack): LLR decoders without soft output.  Policy: at a poll, when the live frames would fill less than
-    // `fill` of the tiles that still hold one, gather them into dense tiles -- a repack moves (E + 2n) lines per tile once, a sweep
-    // moves about (3E + 3n), so it pays as soon as about one more sweep follows.
-    bool repack_ok = early && soft_out == nullptr && tiles >= 2;
-    double repack_fill = 0.75;
-    if (const char* e = std::getenv("LDPC_STREAM_REPACK")) repack_ok = repack_ok && atoi(e) != 0;
-    if (const char* e = std::getenv("LDPC_STREAM_REPACK_FILL")) repack_fill = atof(e);
-    if (repack_fill > 0.95) repack_fill = 0.95;
+    if (!degrees_supported(c)) return LDPC_E_UNSUPPORTED;
+    const bool early = !(k.flags & FLAG_NO_EARLY_EXIT);
+    RepackPolicy repack(early && k.soft == nullptr && tiles >= 2);
 
     // every buffer of the decode is reserved here, before the first sweep (no allocation -- a device synchronisation -- in the loop)
-    LDPC_TRY(d->msg.reserve((size_t)tiles * E * 64 * sizeof(T)));
-    LDPC_TRY(d->marg.reserve((size_t)tiles * n * 64 * sizeof(T)));
-    LDPC_TRY(d->prior.reserve((size_t)tiles * n * 64 * sizeof(T)));
-    LDPC_TRY(d->xbits.reserve(plane_words(tiles, n) * 8));
-    LDPC_TRY(d->live.reserve((size_t)tiles * 8));
+    TileSet* const set = d->set;
+    LDPC_TRY(set[0].edge.reserve((size_t)tiles * E * 64 * sizeof(T)));
+    LDPC_TRY(set[0].node.reserve((size_t)tiles * n * 64 * sizeof(T)));
+    LDPC_TRY(set[0].prior.reserve((size_t)tiles * n * 64 * sizeof(T)));
+    LDPC_TRY(set[0].planes.reserve(plane_words(tiles, n) * 8));
+    LDPC_TRY(set[0].live.reserve((size_t)tiles * 8));
     LDPC_TRY(d->flags.reserve((size_t)tiles * 16 + 64 + POLL_RING * 16));
-    if (repack_ok) {
+    if (repack.on) {
         // second state set: the first repack fires at <= fill * 64 live frames per tile, later ones only shrink
-        const size_t nt = (size_t)(repack_fill * tiles) + 2;
-        if (d->msg2.reserve(nt * E * 64 * sizeof(T)) || d->marg2.reserve(nt * n * 64 * sizeof(T)) ||
-            d->prior2.reserve(nt * n * 64 * sizeof(T)) || d->xbits2.reserve(plane_words((int)nt, n) * 8) || d->live2.reserve(nt * 8) ||
-            d->fmap2.reserve(nt * 64 * sizeof(int32_t)) || d->fmap.reserve(nt * 64 * sizeof(int32_t)) ||
+        const size_t nt = (size_t)(repack.fill * tiles) + 2;
+        if (set[1].edge.reserve(nt * E * 64 * sizeof(T)) || set[1].node.reserve(nt * n * 64 * sizeof(T)) ||
+            set[1].prior.reserve(nt * n * 64 * sizeof(T)) || set[1].planes.reserve(plane_words((int)nt, n) * 8) || set[1].live.reserve(nt * 8) ||
+            set[1].fmap.reserve(nt * 64 * sizeof(int32_t)) || set[0].fmap.reserve(nt * 64 * sizeof(int32_t)) ||
             d->rbase.reserve(((size_t)tiles + 1) * sizeof(int32_t)) || d->rmap.reserve(nt * 64 * sizeof(int32_t)))
-            repack_ok = false;  // no room for a second set: decode without repacking
+            repack.on = false;  // no room for a second set: decode without repacking
     }
     // the repack folded into the sweep behind it (k_repack_map + GATHER passes) where those passes are built; LDPC_STREAM_REPACK_FOLD=0: the
     // separate copy kernel (k_repack), kept for the degrees beyond and as the A/B reference
     const bool fold_repack = gather_passes_built(c) && env_int("LDPC_STREAM_REPACK_FOLD", 1) != 0;
-    T* msg = (T*)d->msg.p;
-    T* marg = (T*)d->marg.p;
-    T* prior = (T*)d->prior.p;
-    u64* xbits = (u64*)d->xbits.p;
-    u64* live = (u64*)d->live.p;
+    int cur = 0;  // which set holds the state; the pointers below are re-read from it after a flip
+    T *msg, *marg, *prior;
+    u64 *xbits, *live;
+    int32_t* fmap = nullptr;  // frame index of (tile, lane); null = identity (never repacked)
+    auto use_set = [&](int s) {
+        cur = s;
+        msg = (T*)set[s].edge.p;
+        marg = (T*)set[s].node.p;
+        prior = (T*)set[s].prior.p;
+        xbits = (u64*)set[s].planes.p;
+        live = (u64*)set[s].live.p;
+    };
+    use_set(0);
     u64* tflags = (u64*)d->flags.p;                                        // [tiles][2]
     int* poll_dev = (int*)((char*)d->flags.p + (size_t)tiles * 16 + 64);  // [POLL_RING][4] ints: live tiles, live frames
     volatile int* poll_host = (volatile int*)d->pinned;                    // [POLL_RING][4] page-locked
     hipEvent_t poll_ev[POLL_RING];
     for (int i = 0; i < POLL_RING; ++i) LDPC_TRY(prof_event(d, i, &poll_ev[i]));
-    size_t ev_next = POLL_RING;
+    DecodeProf prof{d, st, POLL_RING};
 
     Geometry g;
     g.tiles = tiles;
-    g.freeze = soft_out != nullptr ? 1 : 0;
+    g.freeze = k.soft != nullptr ? 1 : 0;
     // Nodes per wave.  The marginal lines a check pass gathers are re-used dv times; the fewer tiles are in flight at once, the
     // more of those re-reads hit on chip -- so a tile is cut into MANY short wave tasks (tile-major task order).  Measured on one
     // MI355X (sweep of 32 768 frames of the (3,6) n = 64 800 shape, profiles/r03_stream_chunking.txt): 64 checks per wave 20.9 ms,
@@ -741,22 +796,17 @@ int run(Decoder* d, const void* priors_v, const uint8_t* y0, int64_t B, int32_t 
     // (16.6 MB of marginals per tile) nothing is re-used either way and the plain order is 2.5 % faster
     g.xcd_aware = (size_t)n * 64 * sizeof(T) <= ((size_t)4 << 20) ? 1 : 0;
 
-    hipEvent_t e_begin = nullptr, e_end = nullptr;
-    if (d->profile) {
-        LDPC_TRY(prof_event(d, ev_next++, &e_begin));
-        LDPC_TRY(prof_event(d, ev_next++, &e_end));
-        LDPC_HIP_TRY(hipEventRecord(e_begin, st));
-    }
+    LDPC_TRY(prof.begin_decode());
     LDPC_HIP_TRY(hipMemsetAsync(xbits, 0, plane_words(tiles, n) * 8, st));
     LDPC_HIP_TRY(hipMemsetAsync(tflags, 0, (size_t)tiles * 16 + 64 + POLL_RING * 16, st));
     LDPC_HIP_TRY(hipMemsetAsync(iters, 0, (size_t)B * sizeof(int32_t), st));
-    if (soft_out) LDPC_HIP_TRY(hipMemsetAsync(marg, 0, (size_t)tiles * n * 64 * sizeof(T), st));  // frames that never sweep report 0
+    if (k.soft) LDPC_HIP_TRY(hipMemsetAsync(marg, 0, (size_t)tiles * n * 64 * sizeof(T), st));  // frames that never sweep report 0
     if (sim) {  // device Monte-Carlo over BI-AWGN: the noise goes straight into the tile layout
         const int bpf = (n + 3) / 4, bpw = 16;
         hipLaunchKernelGGL((k_biawgn_tile<T>), dim3(((bpf + bpw - 1) / bpw + 3) / 4, tiles), dim3(64, 4), 0, st, *sim, B, n, bpf, bpw, prior);
     }
     if (!sim)
-        hipLaunchKernelGGL((k_load_tile<T>), dim3((n + 63) / 64, tiles), dim3(256), 0, st, (const T*)priors_v, y0, B, n, prior, xbits);
+        hipLaunchKernelGGL((k_load_tile<T>), dim3((n + 63) / 64, tiles), dim3(256), 0, st, (const T*)k.priors, y0, B, n, prior, xbits);
     hipLaunchKernelGGL(k_init_live, dim3((tiles + 255) / 256), dim3(256), 0, st, live, B, tiles);
 
     const int cap = max_iter > 0 ? max_iter : 100000;  // max_iter <= 0 == unlimited upstream (src/bpa.py:28); bounded here
@@ -764,21 +814,12 @@ int run(Decoder* d, const void* priors_v, const uint8_t* y0, int64_t B, int32_t 
     const double iter_us = 15.0 + (double)tiles * 64.0 * sizeof(T) * (4.0 * E + n) / 5.0e6;
     int poll_every = (int)(300.0 / iter_us);
     poll_every = poll_every < 1 ? 1 : (poll_every > 16 ? 16 : poll_every);
-    DevBuf* set_msg[2] = {&d->msg, &d->msg2};
-    DevBuf* set_marg[2] = {&d->marg, &d->marg2};
-    DevBuf* set_prior[2] = {&d->prior, &d->prior2};
-    DevBuf* set_xbits[2] = {&d->xbits, &d->xbits2};
-    DevBuf* set_live[2] = {&d->live, &d->live2};
-    DevBuf* set_fmap[2] = {&d->fmap, &d->fmap2};
-    int cur = 0;                 // which buffer set holds the state
-    int32_t* fmap = nullptr;     // frame index of (tile, lane); null = identity (never repacked)
     int cur_tiles = tiles;
     int repacks = 0;
     int sweeps = 0;
     int polls = 0;
     const T *gather_msg = nullptr, *gather_marg = nullptr, *gather_prior = nullptr;  // non-null: the next sweep carries a folded repack out of that set
     std::vector<PendingPoll> pending;
-    std::vector<ProfSpan> spans;
     bool all_left = false;
     for (int it = 0; it < cap && !all_left; ++it) {
         const bool check = early && (it > 0 || y0 != nullptr);
@@ -791,17 +832,7 @@ int run(Decoder* d, const void* priors_v, const uint8_t* y0, int64_t B, int32_t 
                 slot_dev = poll_dev + 4 * slot;
                 LDPC_HIP_TRY(hipMemsetAsync(slot_dev, 0, 2 * sizeof(int), st));
             }
-            {
-                // groups of eight tiles x chunks of the checks: enough blocks to fill the chip (about 4 per CU), at least 1024 checks each
-                const int groups = (cur_tiles + 7) / 8;
-                int sblocks = (1024 + groups - 1) / groups;
-                const int smax = (m + 1023) / 1024;
-                sblocks = sblocks < 1 ? 1 : (sblocks > smax ? smax : sblocks);
-                const int cpb = (m + sblocks - 1) / sblocks;
-                hipLaunchKernelGGL(k_syndrome_part, dim3(sblocks, groups), dim3(256), 0, st, c->d_row_ptr, c->d_edge_var, xbits, live, tflags, m, n,
-                                   cur_tiles, cpb);
-                hipLaunchKernelGGL(k_syndrome_fin, dim3(cur_tiles), dim3(64), 0, st, tflags, live, iters, slot_dev, B, sweeps, fmap);
-            }
+            launch_syndrome(c, k, xbits, live, tflags, slot_dev, cur_tiles, sweeps, fmap);
             if (poll) {
                 LDPC_HIP_TRY(hipMemcpyAsync((void*)(poll_host + 4 * slot), slot_dev, 2 * sizeof(int), hipMemcpyDeviceToHost, st));
                 LDPC_HIP_TRY(hipEventRecord(poll_ev[slot], st));
@@ -824,38 +855,28 @@ int run(Decoder* d, const void* priors_v, const uint8_t* y0, int64_t B, int32_t 
                         sweeps = pp.sweeps;
                         break;
                     }
-                    // When to repack: the live frames fill at most `repack_fill` (0.75) of the live tiles.  (A "rent or buy" schedule -- repack once
-                    // the tile-sweeps spent on departed lanes reach the cost of a repack -- was measured within the run-to-run spread of this
-                    // rule in round 5 and removed in round 6: HISTORY.md.)
-                    const bool want_repack = (double)lf <= repack_fill * 64.0 * lt;
-                    if (repack_ok && pp.tiling_current && pp.it > 0 && lt >= 2 && want_repack && it + 1 < cap) {
+                    if (repack.on && pp.tiling_current && pp.it > 0 && repack.wants(lt, lf) && it + 1 < cap) {
                         const int nt = (lf + 63) / 64;
-                        const int nx = 1 - cur;
+                        const TileSet& to = set[1 - cur];
                         // the decisions of every frame of the old tiles (those that left keep them; the moved ones overwrite theirs later)
-                        launch_unpack(d, xbits, xhat, B, n, cur_tiles, fmap, st);
+                        launch_unpack(k, xbits, n, cur_tiles, fmap);
                         hipLaunchKernelGGL(k_repack_plan, dim3(1), dim3(1024), 0, st, live, cur_tiles, (int32_t*)d->rbase.p);
                         if (fold_repack) {
                             // only the map now; the sweep enqueued below moves the state (GATHER passes: old set in, new set out)
-                            hipLaunchKernelGGL(k_repack_map, dim3(nt), dim3(64), 0, st, live, (u64*)set_live[nx]->p, (const int32_t*)d->rbase.p, fmap,
-                                               (int32_t*)set_fmap[nx]->p, (int32_t*)d->rmap.p, cur_tiles);
+                            hipLaunchKernelGGL(k_repack_map, dim3(nt), dim3(64), 0, st, live, (u64*)to.live.p, (const int32_t*)d->rbase.p, fmap,
+                                               (int32_t*)to.fmap.p, (int32_t*)d->rmap.p, cur_tiles);
                             gather_msg = msg;
                             gather_marg = marg;
                             gather_prior = prior;
                         } else {
                             const int rows_per_wave = 128;
                             const int chunks = (int)((E + n + rows_per_wave - 1) / rows_per_wave);
-                            hipLaunchKernelGGL((k_repack<T>), dim3((chunks + 3) / 4, nt), dim3(64, 4), 0, st, msg, (T*)set_msg[nx]->p, marg,
-                                               (T*)set_marg[nx]->p, prior, (T*)set_prior[nx]->p, xbits, (u64*)set_xbits[nx]->p, live,
-                                               (u64*)set_live[nx]->p, (const int32_t*)d->rbase.p, fmap, (int32_t*)set_fmap[nx]->p, cur_tiles, n, E,
-                                               rows_per_wave);
+                            hipLaunchKernelGGL((k_repack<T>), dim3((chunks + 3) / 4, nt), dim3(64, 4), 0, st, msg, (T*)to.edge.p, marg, (T*)to.node.p, prior,
+                                               (T*)to.prior.p, xbits, (u64*)to.planes.p, live, (u64*)to.live.p, (const int32_t*)d->rbase.p, fmap,
+                                               (int32_t*)to.fmap.p, cur_tiles, n, E, rows_per_wave);
                         }
-                        cur = nx;
-                        msg = (T*)set_msg[cur]->p;
-                        marg = (T*)set_marg[cur]->p;
-                        prior = (T*)set_prior[cur]->p;
-                        xbits = (u64*)set_xbits[cur]->p;
-                        live = (u64*)set_live[cur]->p;
-                        fmap = (int32_t*)set_fmap[cur]->p;
+                        use_set(1 - cur);
+                        fmap = (int32_t*)to.fmap.p;
                         cur_tiles = nt;
                         g.tiles = nt;
                         ++repacks;
@@ -865,51 +886,27 @@ int run(Decoder* d, const void* priors_v, const uint8_t* y0, int64_t B, int32_t 
                 if (all_left) break;
             }
         }
-        hipEvent_t e0 = nullptr, e1 = nullptr, e2 = nullptr;
-        if (d->profile) {
-            LDPC_TRY(prof_event(d, ev_next++, &e0));
-            LDPC_TRY(prof_event(d, ev_next++, &e1));
-            LDPC_TRY(prof_event(d, ev_next++, &e2));
-            LDPC_HIP_TRY(hipEventRecord(e0, st));
-        }
+        LDPC_TRY(prof.mark(0));
         if (gather_msg) {  // the sweep that carries a repack: state read from the old set through the map, written densely into the new one
-            dispatch_cn_gather<T, ALG>(c, msg, gather_msg, gather_marg, live, (const int32_t*)d->rmap.p, g, st);
-            if (d->profile) LDPC_HIP_TRY(hipEventRecord(e1, st));
-            dispatch_vn_gather<T, ALG>(c, msg, gather_prior, prior, marg, live, xbits, (const int32_t*)d->rmap.p, g, st);
+            // (never the first sweep, never a soft-output decode: first == 0 and g.freeze == 0)
+            dispatch_cn<T, ALG, true>(c, msg, gather_marg, live, g, 0, st, gather_msg, (const int32_t*)d->rmap.p);
+            LDPC_TRY(prof.mark(1));
+            dispatch_vn<T, ALG, true>(c, msg, gather_prior, marg, live, xbits, g, st, prior, (const int32_t*)d->rmap.p);
             gather_msg = gather_marg = gather_prior = nullptr;
         } else {
             dispatch_cn<T, ALG>(c, msg, it == 0 ? prior : marg, live, g, it == 0 ? 1 : 0, st);
-            if (d->profile) LDPC_HIP_TRY(hipEventRecord(e1, st));
+            LDPC_TRY(prof.mark(1));
             dispatch_vn<T, ALG>(c, msg, prior, marg, live, xbits, g, st);
         }
-        if (d->profile) {
-            LDPC_HIP_TRY(hipEventRecord(e2, st));
-            spans.push_back({0, e0, e1});
-            spans.push_back({1, e1, e2});
-        }
+        LDPC_TRY(prof.mark(2));
         ++sweeps;
     }
-    hipLaunchKernelGGL(k_finish_iters, dim3(cur_tiles), dim3(64), 0, st, live, iters, B, sweeps, fmap);
-    launch_unpack(d, xbits, xhat, B, n, cur_tiles, fmap, st);
-    if (soft_out)
-        hipLaunchKernelGGL(k_soft_out<T>, dim3((n + 3) / 4, tiles), dim3(256), 0, st, marg, (T*)soft_out, B, n);
-    LDPC_HIP_TRY(hipGetLastError());
+    launch_decisions(k, xbits, live, n, cur_tiles, sweeps, fmap);
+    if (k.soft) hipLaunchKernelGGL(k_soft_out<T>, dim3((n + 3) / 4, tiles), dim3(256), 0, st, marg, (T*)k.soft, B, n);
     // polls still in flight copy into the pinned ring; the next decode of this handle may run on another stream and reuse the slots:
     // let the last copy land first (everything of this decode is enqueued by now, the GPU is not waiting for the host)
     if (!pending.empty()) LDPC_HIP_TRY(hipEventSynchronize(poll_ev[pending.back().slot]));
-    if (d->profile) {
-        LDPC_HIP_TRY(hipEventRecord(e_end, st));
-        LDPC_HIP_TRY(hipStreamSynchronize(st));
-        LDPC_TRY(prof_collect(d, spans));
-        float total = 0.f;
-        LDPC_HIP_TRY(hipEventElapsedTime(&total, e_begin, e_end));
-        d->prof_ms[3] += total;  // everything the decode enqueued: the two passes + load, syndrome, repack, unpack kernels
-        d->prof_launches[3] += 1;
-    }
-    d->last_repacks = repacks;
-    d->last_sweeps = sweeps;
-    d->last_backend = BK_STREAM;
-    return LDPC_OK;
+    return end_decode(d, prof, sweeps, repacks);
 }
 
 }  // namespace
@@ -1202,52 +1199,59 @@ __global__ __launch_bounds__(256) void k_repack16(const __half2* __restrict__ v2
 }
 
 template <int ALG>
-int run16(Decoder* d, const float* priors, const uint8_t* y0, int64_t B, int32_t max_iter, uint32_t flags_in, uint8_t* xhat, int32_t* iters,
-          float* soft_out, hipStream_t st, const SimSource* sim) {
+int run16(Decoder* d, const DecodeCall& k, const SimSource* sim) {
     const Code* c = d->code;
     const int n = c->n, m = c->m;
-    const int64_t E = c->E;
-    if (c->max_dc > 64 || c->max_dv > 64) {
-        set_error("streaming backend supports node degrees up to 64 (max_dc=%d, max_dv=%d)", c->max_dc, c->max_dv);
-        return LDPC_E_UNSUPPORTED;
-    }
+    const int64_t E = c->E, B = k.B;
+    const int32_t max_iter = k.max_iter;
+    const uint8_t* const y0 = k.y0;
+    int32_t* const iters = k.iters;
+    float* const soft_out = (float*)k.soft;
+    const hipStream_t st = k.stream;
+    if (!degrees_supported(c)) return LDPC_E_UNSUPPORTED;
     const int tiles0 = (int)((B + 63) / 64), pairs0 = (tiles0 + 1) / 2;
     int tiles = tiles0, pairs = pairs0;  // shrink when the live frames are repacked into dense pair-tiles
-    const bool early = !(flags_in & FLAG_NO_EARLY_EXIT);
-    LDPC_TRY(d->msg.reserve((size_t)pairs * E * 64 * sizeof(__half2)));
-    LDPC_TRY(d->msg2.reserve((size_t)pairs * E * 64 * sizeof(__half2)));  // variable -> check lines, variable-major
-    // Frame repack (k_repack16; policy of the fp32 passes): at a poll, when the live frames would fill less than `fill` of the tiles that
-    // still hold one, they are gathered into dense pair-tiles.  Second state set: variable -> check lines, priors, planes, live words, map.
-    bool repack_ok = early && soft_out == nullptr && tiles0 >= 4;
-    double repack_fill = 0.75;
-    if (const char* e = std::getenv("LDPC_STREAM_REPACK")) repack_ok = repack_ok && atoi(e) != 0;
-    if (const char* e = std::getenv("LDPC_STREAM_REPACK_FILL")) repack_fill = atof(e);
-    if (repack_fill > 0.95) repack_fill = 0.95;
-    if (repack_ok) {
-        const size_t np2 = ((size_t)(repack_fill * tiles0) + 2 + 1) / 2;  // pairs of the second set: the first repack fires at <= fill * tiles
-        if (d->marg2.reserve(np2 * E * 64 * sizeof(__half2)) || d->prior2.reserve(np2 * n * 64 * sizeof(float2)) ||
-            d->xbits2.reserve(plane_words((int)(2 * np2), n) * 8) || d->live2.reserve(2 * np2 * 8) || d->fmap2.reserve(2 * np2 * 64 * sizeof(int32_t)) ||
-            d->fmap.reserve(2 * np2 * 64 * sizeof(int32_t)) || d->rbase.reserve(((size_t)tiles0 + 2) * sizeof(int32_t)))
-            repack_ok = false;  // no room for a second set: decode without repacking
+    const bool early = !(k.flags & FLAG_NO_EARLY_EXIT);
+    // a state set of this mode: variable -> check lines (edge), priors, planes, live words, map; marginals (node) only with a soft output
+    TileSet* const set = d->set;
+    LDPC_TRY(d->c2v16.reserve((size_t)pairs * E * 64 * sizeof(__half2)));
+    LDPC_TRY(set[0].edge.reserve((size_t)pairs * E * 64 * sizeof(__half2)));  // variable -> check lines, variable-major
+    // Frame repack (k_repack16; policy of the fp32 passes): the live frames are gathered into dense pair-tiles
+    RepackPolicy repack(early && soft_out == nullptr && tiles0 >= 4);
+    if (repack.on) {
+        const size_t np2 = ((size_t)(repack.fill * tiles0) + 2 + 1) / 2;  // pairs of the second set: the first repack fires at <= fill * tiles
+        if (set[1].edge.reserve(np2 * E * 64 * sizeof(__half2)) || set[1].prior.reserve(np2 * n * 64 * sizeof(float2)) ||
+            set[1].planes.reserve(plane_words((int)(2 * np2), n) * 8) || set[1].live.reserve(2 * np2 * 8) || set[1].fmap.reserve(2 * np2 * 64 * sizeof(int32_t)) ||
+            set[0].fmap.reserve(2 * np2 * 64 * sizeof(int32_t)) || d->rbase.reserve(((size_t)tiles0 + 2) * sizeof(int32_t)))
+            repack.on = false;  // no room for a second set: decode without repacking
     }
-    if (soft_out) LDPC_TRY(d->marg.reserve((size_t)pairs * n * 64 * sizeof(float2)));
-    if (!d->scratch.p) {  // row-major edge k -> its position in the CSC edge list (where the variable pass writes its v2c line)
+    if (soft_out) LDPC_TRY(set[0].node.reserve((size_t)pairs * n * 64 * sizeof(float2)));
+    if (!d->graph_tab.p) {  // row-major edge k -> its position in the CSC edge list (where the variable pass writes its v2c line)
         std::vector<int32_t> vpos((size_t)E);
         for (int64_t p = 0; p < E; ++p) vpos[(size_t)c->col_edge[(size_t)p]] = (int32_t)p;
-        LDPC_TRY(d->scratch.reserve((size_t)E * sizeof(int32_t) + 16));
-        LDPC_HIP_TRY(hipMemcpy(d->scratch.p, vpos.data(), (size_t)E * sizeof(int32_t), hipMemcpyHostToDevice));
+        LDPC_TRY(d->graph_tab.reserve((size_t)E * sizeof(int32_t) + 16));
+        LDPC_HIP_TRY(hipMemcpy(d->graph_tab.p, vpos.data(), (size_t)E * sizeof(int32_t), hipMemcpyHostToDevice));
     }
-    const int32_t* edge_vpos = (const int32_t*)d->scratch.p;
-    LDPC_TRY(d->prior.reserve((size_t)pairs * n * 64 * sizeof(float2)));
-    LDPC_TRY(d->xbits.reserve(plane_words(2 * pairs, n) * 8));
-    LDPC_TRY(d->live.reserve((size_t)2 * pairs * 8));
+    const int32_t* edge_vpos = (const int32_t*)d->graph_tab.p;
+    LDPC_TRY(set[0].prior.reserve((size_t)pairs * n * 64 * sizeof(float2)));
+    LDPC_TRY(set[0].planes.reserve(plane_words(2 * pairs, n) * 8));
+    LDPC_TRY(set[0].live.reserve((size_t)2 * pairs * 8));
     LDPC_TRY(d->flags.reserve((size_t)2 * pairs * 16 + 64));
-    __half2* msg = (__half2*)d->msg.p;
-    __half2* v2c = (__half2*)d->msg2.p;
-    float2* marg = soft_out ? (float2*)d->marg.p : nullptr;
-    float2* prior = (float2*)d->prior.p;
-    u64* xbits = (u64*)d->xbits.p;
-    u64* live = (u64*)d->live.p;
+    __half2* msg = (__half2*)d->c2v16.p;
+    float2* marg = soft_out ? (float2*)set[0].node.p : nullptr;
+    int cur = 0;  // which set holds the state; the pointers below are re-read from it after a flip
+    __half2* v2c;
+    float2* prior;
+    u64 *xbits, *live;
+    int32_t* fmap = nullptr;  // frame of (tile, lane); null = identity (never repacked)
+    auto use_set = [&](int s) {
+        cur = s;
+        v2c = (__half2*)set[s].edge.p;
+        prior = (float2*)set[s].prior.p;
+        xbits = (u64*)set[s].planes.p;
+        live = (u64*)set[s].live.p;
+    };
+    use_set(0);
     u64* tflags = (u64*)d->flags.p;
     int* live_tiles = (int*)((char*)d->flags.p + (size_t)2 * pairs * 16);
     volatile int* poll_host = (volatile int*)d->pinned;
@@ -1260,40 +1264,24 @@ int run16(Decoder* d, const float* priors, const uint8_t* y0, int64_t B, int32_t
         const int bpf = (n + 3) / 4, bpw = 16;
         hipLaunchKernelGGL(k_biawgn_tile16, dim3(((bpf + bpw - 1) / bpw + 3) / 4, pairs), dim3(64, 4), 0, st, *sim, B, n, bpf, bpw, prior);
     } else {
-        hipLaunchKernelGGL(k_load_tile16, dim3((n + 63) / 64, pairs), dim3(256), 0, st, priors, y0, B, n, prior, xbits);
+        hipLaunchKernelGGL(k_load_tile16, dim3((n + 63) / 64, pairs), dim3(256), 0, st, (const float*)k.priors, y0, B, n, prior, xbits);
     }
     hipLaunchKernelGGL(k_init_live, dim3((tiles + 255) / 256), dim3(256), 0, st, live, B, tiles);
-    DevBuf* set_v2c[2] = {&d->msg2, &d->marg2};
-    DevBuf* set_prior[2] = {&d->prior, &d->prior2};
-    DevBuf* set_xbits[2] = {&d->xbits, &d->xbits2};
-    DevBuf* set_live[2] = {&d->live, &d->live2};
-    DevBuf* set_fmap[2] = {&d->fmap, &d->fmap2};
-    int32_t* fmap = nullptr;  // frame of (tile, lane); null = identity (never repacked)
-    int cur = 0, repacks = 0;
+    int repacks = 0;
     const int cpw = 4, vpw = 16;
     const int cn_chunks = (m + cpw - 1) / cpw, vn_chunks = (n + vpw - 1) / vpw;
     const int cap = max_iter > 0 ? max_iter : 100000;
     // the live counters are read (synchronously) every fourth sweep; every sweep where a sweep is more than ~1.5 ms of streaming work
     // (the round trip is then a percent of it, and frames leave by the thousand per sweep: the repack should not wait three sweeps)
     const int poll_every = (double)tiles * 64.0 * (8.0 * E + 4.0 * n) / 5.0e6 > 1500.0 ? 1 : 4;
-    const bool reg36 = c->min_dc == c->max_dc && c->max_dc == 6;
-    const bool dv3 = c->min_dv == c->max_dv && c->max_dv == 3;
-    hipEvent_t e0 = nullptr, e1 = nullptr, e2 = nullptr;
-    std::vector<ProfSpan> spans;
-    size_t ev_next = 0;
+    DecodeProf prof{d, st, 0};
     int sweeps = 0;
     bool all_left = false;
     for (int it = 0; it < cap && !all_left; ++it) {
         if (early && (it > 0 || y0 != nullptr)) {
             const bool poll = (it % poll_every) == 0;
             if (poll) LDPC_HIP_TRY(hipMemsetAsync(live_tiles, 0, 2 * sizeof(int), st));
-            const int groups = (tiles + 7) / 8;
-            int sblocks = (1024 + groups - 1) / groups;
-            const int smax = (m + 1023) / 1024;
-            sblocks = sblocks < 1 ? 1 : (sblocks > smax ? smax : sblocks);
-            hipLaunchKernelGGL(k_syndrome_part, dim3(sblocks, groups), dim3(256), 0, st, c->d_row_ptr, c->d_edge_var, xbits, live, tflags, m, n, tiles,
-                               (m + sblocks - 1) / sblocks);
-            hipLaunchKernelGGL(k_syndrome_fin, dim3(tiles), dim3(64), 0, st, tflags, live, iters, poll ? live_tiles : nullptr, B, sweeps, (const int32_t*)fmap);
+            launch_syndrome(c, k, xbits, live, tflags, poll ? live_tiles : nullptr, tiles, sweeps, fmap);
             if (poll) {
                 LDPC_HIP_TRY(hipMemcpyAsync((void*)poll_host, live_tiles, 2 * sizeof(int), hipMemcpyDeviceToHost, st));
                 LDPC_HIP_TRY(hipStreamSynchronize(st));
@@ -1302,144 +1290,86 @@ int run16(Decoder* d, const float* priors, const uint8_t* y0, int64_t B, int32_t
                     all_left = true;
                     break;
                 }
-                const bool want_repack = (double)lf <= repack_fill * 64.0 * lt;
-                if (repack_ok && it > 0 && lt >= 2 && want_repack && it + 1 < cap) {
-                    const int nt = (lf + 63) / 64, np = (nt + 1) / 2, nx = 1 - cur;
+                if (repack.on && it > 0 && repack.wants(lt, lf) && it + 1 < cap) {
+                    const int nt = (lf + 63) / 64, np = (nt + 1) / 2;
+                    const TileSet& to = set[1 - cur];
                     // the decisions of every frame of the old tiles (those that left keep them; the moved ones overwrite theirs at the end)
-                    launch_unpack(d, xbits, xhat, B, n, tiles, fmap, st);
+                    launch_unpack(k, xbits, n, tiles, fmap);
                     hipLaunchKernelGGL(k_repack_plan, dim3(1), dim3(1024), 0, st, live, tiles, (int32_t*)d->rbase.p);
                     const int rows_per_wave = 128;
                     const int chunks = (int)((E + n + rows_per_wave - 1) / rows_per_wave);
-                    hipLaunchKernelGGL(k_repack16, dim3((chunks + 3) / 4, np), dim3(64, 4), 0, st, v2c, (__half2*)set_v2c[nx]->p, prior, (float2*)set_prior[nx]->p,
-                                       xbits, (u64*)set_xbits[nx]->p, live, (u64*)set_live[nx]->p, (const int32_t*)d->rbase.p, (const int32_t*)fmap,
-                                       (int32_t*)set_fmap[nx]->p, tiles, n, E, rows_per_wave);
-                    cur = nx;
-                    v2c = (__half2*)set_v2c[cur]->p;
-                    prior = (float2*)set_prior[cur]->p;
-                    xbits = (u64*)set_xbits[cur]->p;
-                    live = (u64*)set_live[cur]->p;
-                    fmap = (int32_t*)set_fmap[cur]->p;
+                    hipLaunchKernelGGL(k_repack16, dim3((chunks + 3) / 4, np), dim3(64, 4), 0, st, v2c, (__half2*)to.edge.p, prior, (float2*)to.prior.p, xbits,
+                                       (u64*)to.planes.p, live, (u64*)to.live.p, (const int32_t*)d->rbase.p, (const int32_t*)fmap, (int32_t*)to.fmap.p, tiles, n, E,
+                                       rows_per_wave);
+                    use_set(1 - cur);
+                    fmap = (int32_t*)to.fmap.p;
                     pairs = np;
                     tiles = 2 * np;  // (an odd tile count leaves the last pair's second tile without a live frame)
                     ++repacks;
                 }
             }
         }
-        if (d->profile) {
-            LDPC_TRY(prof_event(d, ev_next++, &e0));
-            LDPC_TRY(prof_event(d, ev_next++, &e1));
-            LDPC_TRY(prof_event(d, ev_next++, &e2));
-            LDPC_HIP_TRY(hipEventRecord(e0, st));
-        }
-        const bool first = it == 0;
+        LDPC_TRY(prof.mark(0));
         const dim3 cgrid(task_blocks(pairs, cn_chunks, 0)), vgrid(task_blocks(pairs, vn_chunks, 0)), blk(64, 4);
-#define LDPC_CN16_LAUNCH(DCM, FDC, UNR, FIRST) \
-    hipLaunchKernelGGL((k_cn16<ALG, DCM, FDC, UNR, FIRST>), cgrid, blk, 0, st, c->d_row_ptr, c->d_edge_var, edge_vpos, msg, v2c, prior, live, m, n, E, pairs, tiles, cn_chunks, cpw)
-#define LDPC_CN16(DCM, FDC, UNR)                       \
-    do {                                               \
-        if (first) LDPC_CN16_LAUNCH(DCM, FDC, UNR, true); \
-        else LDPC_CN16_LAUNCH(DCM, FDC, UNR, false);      \
-    } while (0)
-        if (reg36) LDPC_CN16(6, 6, 2);
-        else if (c->max_dc <= 4) LDPC_CN16(4, 0, 2);
-        else if (c->max_dc <= 6) LDPC_CN16(6, 0, 2);
-        else if (c->max_dc <= 8) LDPC_CN16(8, 0, 1);
-        else if (c->max_dc <= 16) LDPC_CN16(16, 0, 1);
-        else if (c->max_dc <= 32) LDPC_CN16(32, 0, 1);
-        else LDPC_CN16(64, 0, 1);
-#undef LDPC_CN16
-#undef LDPC_CN16_LAUNCH
-        if (d->profile) LDPC_HIP_TRY(hipEventRecord(e1, st));
-#define LDPC_VN16(DVM, UNR, FDV) \
-    hipLaunchKernelGGL((k_vn16<ALG, DVM, UNR, FDV>), vgrid, blk, 0, st, c->d_col_ptr, c->d_col_edge, msg, v2c, prior, marg, live, xbits, n, E, pairs, tiles, vn_chunks, vpw)
-        if (dv3) LDPC_VN16(3, 4, 3);
-        else if (c->max_dv <= 4) LDPC_VN16(4, 4, 0);
-        else if (c->max_dv <= 8) LDPC_VN16(8, 2, 0);
-        else if (c->max_dv <= 16) LDPC_VN16(16, 1, 0);
-        else if (c->max_dv <= 32) LDPC_VN16(32, 1, 0);
-        else LDPC_VN16(64, 1, 0);
-#undef LDPC_VN16
-        if (d->profile) {
-            LDPC_HIP_TRY(hipEventRecord(e2, st));
-            spans.push_back({0, e0, e1});
-            spans.push_back({1, e1, e2});
-        }
+        check_class(c, [&](auto dcm, auto fdc) {
+            constexpr int DCM = decltype(dcm)::value, FDC = decltype(fdc)::value, UNR = DCM <= 6 ? 2 : 1;
+            const auto kern = it == 0 ? k_cn16<ALG, DCM, FDC, UNR, true> : k_cn16<ALG, DCM, FDC, UNR, false>;
+            hipLaunchKernelGGL(kern, cgrid, blk, 0, st, c->d_row_ptr, c->d_edge_var, edge_vpos, msg, v2c, prior, live, m, n, E, pairs, tiles, cn_chunks, cpw);
+        });
+        LDPC_TRY(prof.mark(1));
+        var_class<false>(c, [&](auto dvm, auto fdv) {
+            constexpr int DVM = decltype(dvm)::value, UNR = DVM <= 4 ? 4 : (DVM == 8 ? 2 : 1);
+            hipLaunchKernelGGL((k_vn16<ALG, DVM, UNR, decltype(fdv)::value>), vgrid, blk, 0, st, c->d_col_ptr, c->d_col_edge, msg, v2c, prior, marg, live, xbits, n, E,
+                               pairs, tiles, vn_chunks, vpw);
+        });
+        LDPC_TRY(prof.mark(2));
         ++sweeps;
     }
-    hipLaunchKernelGGL(k_finish_iters, dim3(tiles), dim3(64), 0, st, live, iters, B, sweeps, (const int32_t*)fmap);
-    launch_unpack(d, xbits, xhat, B, n, tiles, fmap, st);
+    launch_decisions(k, xbits, live, n, tiles, sweeps, fmap);
     if (soft_out) hipLaunchKernelGGL(k_soft_out16, dim3((n + 3) / 4, pairs), dim3(256), 0, st, marg, soft_out, B, n);  // (no repack with a soft output)
-    LDPC_HIP_TRY(hipGetLastError());
-    if (d->profile) {
-        LDPC_HIP_TRY(hipStreamSynchronize(st));
-        LDPC_TRY(prof_collect(d, spans));
-    }
-    d->last_repacks = repacks;
-    d->last_sweeps = sweeps;
-    d->last_backend = BK_STREAM;
-    return LDPC_OK;
+    return end_decode(d, prof, sweeps, repacks);
+}
+
+bool batch_fits(int64_t B) {
+    if (B <= (int64_t)65535 * 64) return true;
+    set_error("batch of %lld frames exceeds one launch (max %d); split the call", (long long)B, 65535 * 64);
+    return false;
+}
+
+template <typename T>
+int run_alg(Decoder* d, const DecodeCall& k, const SimSource* sim) {
+    return d->alg == ALG_MSA ? run<T, ALG_MSA>(d, k, sim) : run<T, ALG_SPA>(d, k, sim);
+}
+
+// LLR decoders: the driver of the decoder's storage type; with `sim` the priors are drawn into the tiles instead of loaded
+int run_llr(Decoder* d, const DecodeCall& k, const SimSource* sim) {
+    if (d->dtype == DT_F16) return d->alg == ALG_MSA ? run16<ALG_MSA>(d, k, sim) : run16<ALG_SPA>(d, k, sim);  // priors are fp32
+    return d->dtype == DT_F64 ? run_alg<double>(d, k, sim) : run_alg<float>(d, k, sim);
 }
 
 }  // namespace
 
-// fp16-storage mode entry points (LDPC_DTYPE_F16): priors are fp32
-static int stream_decode_f16(Decoder* d, const void* priors, const uint8_t* y0, int64_t B, int32_t max_iter, uint32_t flags, uint8_t* xhat, int32_t* iters,
-                             float* soft_out, hipStream_t st, const SimSource* sim) {
-    if (B <= 0) return LDPC_OK;
-    if (B > (int64_t)65535 * 64) {
-        set_error("batch of %lld frames exceeds one launch (max %d); split the call", (long long)B, 65535 * 64);
-        return LDPC_E_ARG;
-    }
-    if (d->alg == ALG_MSA) return run16<ALG_MSA>(d, (const float*)priors, y0, B, max_iter, flags, xhat, iters, soft_out, st, sim);
-    if (d->alg == ALG_SPA) return run16<ALG_SPA>(d, (const float*)priors, y0, B, max_iter, flags, xhat, iters, soft_out, st, sim);
-    set_error("fp16 storage: LLR decoders (the erasure decoder moves 2 bits per message already)");
-    return LDPC_E_UNSUPPORTED;
-}
-
-
 // ldpc_simulate on the streaming kernels, BI-AWGN with the all-`codeword` word: channel + LLR generated into the tiles, then the decode
-int stream_simulate_biawgn(Decoder* d, double param, int codeword, uint64_t seed, uint64_t stream_id, uint64_t frame0, int64_t B,
-                           int32_t max_iter, uint32_t flags, uint8_t* xhat, int32_t* iters, hipStream_t st) {
-    if (B <= 0) return LDPC_OK;
-    if (d->alg == ALG_BEC || B > (int64_t)65535 * 64) {
-        set_error("stream_simulate_biawgn: LLR decoders, at most %d frames per call", 65535 * 64);
+int stream_simulate_biawgn(Decoder* d, const DecodeCall& k, double param, int codeword, uint64_t seed, uint64_t stream_id, uint64_t frame0) {
+    if (k.B <= 0) return LDPC_OK;
+    if (d->alg == ALG_BEC) {
+        set_error("stream_simulate_biawgn: LLR decoders only");
         return LDPC_E_ARG;
     }
+    if (!batch_fits(k.B)) return LDPC_E_ARG;
     const double var = pow(10.0, -param / 10.0);  // src/biawgn.py:10 -- the host arithmetic of channel_generate()
     const SimSource s{sqrt(var), 2.0 / var, codeword, seed, frame0, (uint32_t)stream_id};
-    if (d->dtype == DT_F16) return stream_decode_f16(d, nullptr, nullptr, B, max_iter, flags, xhat, iters, nullptr, st, &s);
-    if (d->alg == ALG_MSA)
-        return d->dtype == DT_F64 ? run<double, ALG_MSA>(d, nullptr, nullptr, B, max_iter, flags, xhat, iters, nullptr, st, &s)
-                                  : run<float, ALG_MSA>(d, nullptr, nullptr, B, max_iter, flags, xhat, iters, nullptr, st, &s);
-    return d->dtype == DT_F64 ? run<double, ALG_SPA>(d, nullptr, nullptr, B, max_iter, flags, xhat, iters, nullptr, st, &s)
-                              : run<float, ALG_SPA>(d, nullptr, nullptr, B, max_iter, flags, xhat, iters, nullptr, st, &s);
+    return run_llr(d, k, &s);
 }
 
-int stream_decode(Decoder* d, const void* priors, const uint8_t* y0, int64_t B, int32_t max_iter, uint32_t flags,
-                  uint8_t* xhat, int32_t* iters, void* soft_out, hipStream_t st) {
-    if (B <= 0) return LDPC_OK;
-    if (B > (int64_t)65535 * 64) {
-        set_error("batch of %lld frames exceeds one launch (max %d); split the call", (long long)B, 65535 * 64);
+int stream_decode(Decoder* d, const DecodeCall& k) {
+    if (k.B <= 0) return LDPC_OK;
+    if (!batch_fits(k.B)) return LDPC_E_ARG;
+    if (d->alg == ALG_BEC ? !k.y0 : !k.priors) {
+        set_error(d->alg == ALG_BEC ? "erasure decoder needs the received symbols (y0)" : "priors pointer is null");
         return LDPC_E_ARG;
     }
-    if (d->alg == ALG_BEC) {
-        if (!y0) {
-            set_error("erasure decoder needs the received symbols (y0)");
-            return LDPC_E_ARG;
-        }
-        return becs_stream_decode(d, y0, B, max_iter, flags, xhat, iters, st);  // bit-sliced: ldpc_bec_stream.hip
-    }
-    if (!priors) {
-        set_error("priors pointer is null");
-        return LDPC_E_ARG;
-    }
-    if (d->dtype == DT_F16) return stream_decode_f16(d, priors, y0, B, max_iter, flags, xhat, iters, (float*)soft_out, st, nullptr);
-    if (d->alg == ALG_MSA) {
-        return d->dtype == DT_F64 ? run<double, ALG_MSA>(d, priors, y0, B, max_iter, flags, xhat, iters, soft_out, st)
-                                  : run<float, ALG_MSA>(d, priors, y0, B, max_iter, flags, xhat, iters, soft_out, st);
-    }
-    return d->dtype == DT_F64 ? run<double, ALG_SPA>(d, priors, y0, B, max_iter, flags, xhat, iters, soft_out, st)
-                              : run<float, ALG_SPA>(d, priors, y0, B, max_iter, flags, xhat, iters, soft_out, st);
+    return d->alg == ALG_BEC ? becs_stream_decode(d, k) : run_llr(d, k, nullptr);  // erasure: bit-sliced, ldpc_bec_stream.hip
 }
 
 }  // namespace ldpc
