@@ -30,6 +30,15 @@ typedef struct ldpc_code_s* ldpc_code_t;
 typedef struct ldpc_decoder_s* ldpc_decoder_t;
 
 enum { LDPC_ALG_MSA = 0, LDPC_ALG_SPA = 1, LDPC_ALG_BEC = 2 };      /* decoder selector: src/utils.py:16, main.py:12 */
+/* Corrected (normalised and / or offset) min-sum.  No upstream counterpart: it modifies the min-sum rule of src/bpa.py:86-102, which sends
+ * on edge j of a check the sign s_j times m_j = min_{i != j} |v2c_i|.  The corrected decoder sends
+ *     c2v_j = s_j * max( fl( fl(scale * m_j) - offset ), 0 )
+ * in the decoder's arithmetic (fp64 or fp32; fp16 storage: in fp32, before the message is rounded to half), scale and offset rounded to
+ * that type once on the host, two roundings (a multiply, then a subtraction: never a fused multiply-add).  A clamped message is +-0 and
+ * contributes nothing.  Everything else of BPA.decode (src/bpa.py:17-63) is untouched.  scale = 1, offset = 0 (the state after create)
+ * is bit-identical to LDPC_ALG_MSA.  Every dtype and backend, the same kernel shapes and layout plans as LDPC_ALG_MSA; accepted wherever
+ * LDPC_ALG_MSA is, except LDPC_FLAG_PRIOR_GRID (LDPC_E_UNSUPPORTED on every backend: a scale takes values off the grid). */
+enum { LDPC_ALG_NMSA = 3 };
 enum { LDPC_DTYPE_F32 = 0, LDPC_DTYPE_F64 = 1,                       /* message arithmetic                             */
        LDPC_DTYPE_F16 = 2 };  /* fp16 STORAGE of the check messages on the streaming kernels, fp32 arithmetic, fp32 priors / channel output:
                                * a throughput mode for codes whose state lives in HBM (the E-sized traffic halves); held to a
@@ -125,6 +134,13 @@ int ldpc_plan_layout(int32_t m, int32_t n, int64_t E, const int32_t* edge_chk, c
  * rocprofv3 prints it, e.g. "k_fused_bp<0, 6, 3, 5, 10, 2, true, 0, 3>" -- the key under which its committed PMC counters are filed
  * (profiles/roofline_counters.json).  Empty string: the decoder runs on the streaming kernels.  No upstream counterpart. */
 int ldpc_decoder_kernel_name(ldpc_decoder_t dec, int simulate, char* buf, int64_t len);
+
+/* Scale and offset of a corrected min-sum decoder (LDPC_ALG_NMSA).  No upstream counterpart: the rule they modify is src/bpa.py:86-102
+ * (see LDPC_ALG_NMSA above).  0 < scale <= 1, offset >= 0, both finite; LDPC_E_ARG otherwise and for a decoder of another algorithm.
+ * After ldpc_decoder_create: 1, 0.  Decoder state, read when a call is enqueued: a change takes effect from the next call. */
+int ldpc_decoder_set_correction(ldpc_decoder_t dec, double scale, double offset);
+/* The values in force (LDPC_E_ARG for a decoder of another algorithm).  No upstream counterpart (src/bpa.py:86-102 has neither). */
+int ldpc_decoder_get_correction(ldpc_decoder_t dec, double* scale, double* offset);
 
 /* Per-kernel timing for roofline reports: when enabled, decode calls bracket their dominant kernels with HIP events
  * recorded ON THE DECODE STREAM and accumulate elapsed milliseconds / launch counts per kernel class:

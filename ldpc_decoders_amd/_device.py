@@ -37,6 +37,14 @@ def unpack_bits(bits, n, erased=None):
     return x
 
 
+def check_correction(scale, offset):
+    """The range ``ldpc_decoder_set_correction`` accepts (0 < scale <= 1, finite offset >= 0), checked before any device call."""
+    scale, offset = float(scale), float(offset)
+    if not (0.0 < scale <= 1.0) or not (0.0 <= offset < float("inf")):
+        raise ValueError("corrected min-sum needs 0 < scale <= 1 and a finite offset >= 0 (got scale=%r, offset=%r)" % (scale, offset))
+    return scale, offset
+
+
 class CodeHandle:
     def __init__(self, code, device):
         lib = _lib.load()
@@ -84,6 +92,16 @@ class DecoderHandle:
                 self.h = None
         except Exception:
             pass
+
+    # ---- corrected min-sum (alg="NMSA"): c2v = sign * max(scale * min - offset, 0); decoder state, in force from the next call
+    def set_correction(self, scale, offset=0.0):
+        check_correction(scale, offset)
+        _lib.check(_lib.load().ldpc_decoder_set_correction(self.h, float(scale), float(offset)))
+
+    def correction(self):
+        s, o = ctypes.c_double(0), ctypes.c_double(0)
+        _lib.check(_lib.load().ldpc_decoder_get_correction(self.h, ctypes.byref(s), ctypes.byref(o)))
+        return s.value, o.value
 
     # ---- host (numpy) buffers
     def decode_host(self, priors, y0, max_iter, flags=0):

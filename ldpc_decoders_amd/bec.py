@@ -51,6 +51,15 @@ class MSA(SPA):
     pass
 
 
+class NMSA:
+    """Corrected min-sum has no meaning over the erasure channel: the ternary decoder has no magnitudes to scale or offset."""
+    id_keys = ["max_iter", "msa_scale", "msa_offset"]
+
+    def __init__(self, *a, **k):
+        raise NotImplementedError("decoder NMSA (corrected min-sum) does not exist over the bec: the erasure decoder has no magnitudes "
+                                  "to correct; use SPA / MSA there")
+
+
 class ADMM:  # src/bec.py:38-45,58-62: LLR wrapper with +-1e8 for the known symbols, 0 for an erasure
     id_keys = admm.ADMM.id_keys
     channel = "bec"

@@ -47,6 +47,13 @@ class MSA(LLR):
         super().__init__(snr_in_db, bpa.MSA(_code, **kwargs))
 
 
+class NMSA(LLR):  # corrected (normalised / offset) min-sum: no upstream counterpart, wrapped like MSA
+    id_keys = bpa.NMSA.id_keys
+
+    def __init__(self, snr_in_db, _code, **kwargs):
+        super().__init__(snr_in_db, bpa.NMSA(_code, **kwargs))
+
+
 class ADMM(LLR):  # src/biawgn.py:52-56
     id_keys = admm.ADMM.id_keys
 

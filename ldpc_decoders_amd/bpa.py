@@ -12,7 +12,7 @@ Extra constructor keywords (all optional):
 """
 import numpy as np
 
-from ._device import DecoderHandle, as_code
+from ._device import DecoderHandle, as_code, check_correction
 
 
 class BPA:
@@ -84,3 +84,19 @@ class SPA(BPA):
 class MSA(BPA):
     """Min-sum: two-min + sign-parity check rule (src/bpa.py:78-102)."""
     alg = "MSA"
+
+
+class NMSA(BPA):
+    """Corrected min-sum (no upstream counterpart): the rule of src/bpa.py:86-102 with every check message scaled and / or offset,
+    ``c2v = sign * max(msa_scale * min - msa_offset, 0)`` -- normalised min-sum (0 < msa_scale <= 1), offset min-sum (msa_offset >= 0) or
+    both.  (1, 0) is ``MSA`` bit for bit.  Same ``decode`` / ``decode_batch``, kernels, shapes and precisions as ``MSA``."""
+    alg = "NMSA"
+    id_keys = ["max_iter", "msa_scale", "msa_offset"]
+
+    def __init__(self, parity_mtx, **kwargs):
+        scale = kwargs.get("msa_scale")
+        offset = kwargs.get("msa_offset")
+        # (checked before the decoder is created: a bad value never reaches the device)
+        self.msa_scale, self.msa_offset = check_correction(0.8125 if scale is None else scale, 0.0 if offset is None else offset)
+        super().__init__(parity_mtx, **kwargs)
+        self.handle.set_correction(self.msa_scale, self.msa_offset)

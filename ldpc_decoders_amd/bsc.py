@@ -49,6 +49,13 @@ class MSA(LLR):
         super().__init__(p, bpa.MSA(_code, **kwargs))
 
 
+class NMSA(LLR):  # corrected (normalised / offset) min-sum: no upstream counterpart, wrapped like MSA
+    id_keys = bpa.NMSA.id_keys
+
+    def __init__(self, p, _code, **kwargs):
+        super().__init__(p, bpa.NMSA(_code, **kwargs))
+
+
 class ADMM(LLR):  # src/bsc.py:49-53
     id_keys = admm.ADMM.id_keys
 

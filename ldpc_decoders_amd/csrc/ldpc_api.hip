@@ -1,5 +1,6 @@
 // extern "C" surface of libldpc_hip.so (declared in include/ldpc_hip.h).
 #include <array>
+#include <cmath>
 #include <cstring>
 #include <memory>
 #include <mutex>
@@ -141,6 +142,10 @@ inline int64_t chunk_at(int64_t b0, int64_t B, int64_t step) { return (B - b0) <
 // a call that asks for it there is refused (as ldpc_simulate refuses it) instead of returning frames nobody vouched for.  fp64 decoders
 // need no guard (their arithmetic IS the reference's), the flag is then a no-op.
 int grid_guard_available(const Decoder* d, int bk, uint32_t flags, const char* who) {
+    if (LDPC_FLAG_PRIOR_GRID_OF(flags) >= 0 && d->alg == ALG_NMSA) {  // in any arithmetic, on every backend
+        set_error("%s: prior grid: corrected min-sum (LDPC_ALG_NMSA) has no exact-in-fp32 mode (a scale takes values off the grid)", who);
+        return LDPC_E_UNSUPPORTED;
+    }
     if (LDPC_FLAG_PRIOR_GRID_OF(flags) < 0 || d->dtype == DT_F64) return LDPC_OK;
     if (bk == BK_FUSED && d->alg == ALG_MSA) return LDPC_OK;
     set_error("%s: prior grid: the exactness guard lives in the LDS-resident fp32 min-sum kernels; this decoder runs on the streaming kernels", who);
@@ -295,7 +300,7 @@ int ldpc_code_info(ldpc_code_t h, int32_t* m, int32_t* n, int64_t* E, int32_t* m
 int ldpc_plan_layout(int32_t m, int32_t n, int64_t E, const int32_t* chk, const int32_t* var, int alg, int dtype, int64_t moves,
                      const char* out_dir, double* info4) {
     return guarded("ldpc_plan_layout", [&]() -> int {
-        if (!info4 || alg < 0 || alg > 2 || dtype < 0 || dtype > 1) {
+        if (!info4 || alg < 0 || alg > ALG_NMSA || dtype < 0 || dtype > 1) {
             set_error("ldpc_plan_layout: bad arguments (alg=%d dtype=%d)", alg, dtype);
             return LDPC_E_ARG;
         }
@@ -307,7 +312,7 @@ int ldpc_plan_layout(int32_t m, int32_t n, int64_t E, const int32_t* chk, const 
 
 int ldpc_decoder_create(ldpc_code_t code, int alg, int dtype, int backend, ldpc_decoder_t* out) {
     return guarded("ldpc_decoder_create", [&]() -> int {
-        if (!code || !out || alg < 0 || alg > 2 || dtype < 0 || dtype > 2 || (dtype == DT_F16 && (alg == ALG_BEC || backend == BK_FUSED)) ||
+        if (!code || !out || alg < 0 || alg > ALG_NMSA || dtype < 0 || dtype > 2 || (dtype == DT_F16 && (alg == ALG_BEC || backend == BK_FUSED)) ||
             backend < 0 || backend > 2) {
             set_error("ldpc_decoder_create: bad arguments (alg=%d dtype=%d backend=%d)", alg, dtype, backend);
             return LDPC_E_ARG;
@@ -359,6 +364,37 @@ int ldpc_decoder_destroy(ldpc_decoder_t h) {
         if (d->lat_stream) (void)hipStreamDestroy(d->lat_stream);
         for (hipEvent_t e : d->ev_pool) (void)hipEventDestroy(e);
         delete d;
+        return LDPC_OK;
+    });
+}
+
+int ldpc_decoder_set_correction(ldpc_decoder_t h, double scale, double offset) {
+    return guarded("ldpc_decoder_set_correction", [&]() -> int {
+        Decoder* d = (Decoder*)h;
+        if (!d || d->alg != ALG_NMSA) {
+            set_error("ldpc_decoder_set_correction: a corrected min-sum decoder (LDPC_ALG_NMSA) is needed");
+            return LDPC_E_ARG;
+        }
+        // (written so that a NaN fails every test)
+        if (!(scale > 0.0 && scale <= 1.0) || !(offset >= 0.0 && offset < HUGE_VAL)) {
+            set_error("ldpc_decoder_set_correction: 0 < scale <= 1 and a finite offset >= 0 are needed (scale=%g offset=%g)", scale, offset);
+            return LDPC_E_ARG;
+        }
+        d->corr_scale = scale;
+        d->corr_offset = offset;
+        return LDPC_OK;
+    });
+}
+
+int ldpc_decoder_get_correction(ldpc_decoder_t h, double* scale, double* offset) {
+    return guarded("ldpc_decoder_get_correction", [&]() -> int {
+        Decoder* d = (Decoder*)h;
+        if (!d || !scale || !offset || d->alg != ALG_NMSA) {
+            set_error("ldpc_decoder_get_correction: a corrected min-sum decoder (LDPC_ALG_NMSA) and two result pointers are needed");
+            return LDPC_E_ARG;
+        }
+        *scale = d->corr_scale;
+        *offset = d->corr_offset;
         return LDPC_OK;
     });
 }
@@ -864,6 +900,10 @@ static int simulate_impl(ldpc_decoder_t h, int channel, double param, int codewo
         return LDPC_E_ARG;
     }
     const int grid_k = LDPC_FLAG_PRIOR_GRID_OF(flags);
+    if (grid_k >= 0 && d->alg == ALG_NMSA) {
+        set_error("ldpc_simulate: prior grid: corrected min-sum (LDPC_ALG_NMSA) has no exact-in-fp32 mode (a scale takes values off the grid)");
+        return LDPC_E_UNSUPPORTED;
+    }
     // (fp64 decoders with a prior grid take the composed path below: quantised priors from the channel kernel, no guard needed)
     if (d->backend != BK_STREAM && fused_simulate_supported(d, channel, param, hist_bins) && !(grid_k >= 0 && d->dtype == DT_F64 && d->alg != ALG_BEC))
         return fused_simulate(d, channel, param, codeword, seed, stream_id, frame0, B, max_iter, flags, hist_bins, counters, st);

@@ -4,12 +4,15 @@
 // variable->check messages in edge order, and overwrites it with the check->variable messages.
 //
 //   min-sum      reference src/bpa.py:86-102 (+ src/math_utils.py:10,38-43,78-94)
+//   corrected min-sum (normalised / offset; no upstream counterpart): the same with |c2v| = max(fl(fl(scale * min) - offset), 0)
 //   sum-product  reference src/bpa.py:71-75  (+ src/math_utils.py:47-60)
 //   (erasure decoder, src/bec.py:100-112: bit-sliced, ldpc_bec_planes.hpp / ldpc_bec_kernels.hpp / ldpc_bec_stream.hip)
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+
+#include "ldpc_common.hpp"
 
 namespace ldpc {
 
@@ -26,12 +29,31 @@ struct real_traits<double> {
     static __device__ __forceinline__ double abs(double x) { return __builtin_fabs(x); }
 };
 
-// ---- min-sum ------------------------------------------------------------------------------------
+// ---- min-sum, plain and corrected -----------------------------------------------------------------
 // |extrinsic| = second minimum at the FIRST arg-min edge, first minimum elsewhere (== leave-one-out min);
 // extrinsic sign = (-1)^(#(v<0) in the row) / sgn(v_own) with sgn(0) = +1.  Only compares and negations:
 // bit-exact against the fp64 reference in any precision that represents the inputs.
-template <typename T, int DCMAX>
-__device__ __forceinline__ void cn_msa(T (&v)[DCMAX], int deg) {
+//
+// CORRECTED (normalised and / or offset min-sum; no upstream counterpart).  The reference's rule (src/bpa.py:86-102) over-estimates
+// every check message; the two textbook corrections are one multiply (0 < scale <= 1) and one subtraction (offset >= 0) per message,
+// clamped at zero:
+//     |c2v_j| = max( fl( fl(scale * m_j) - offset ), 0 ),   m_j = min_{i != j} |v_i|,   sign as above
+// in the decoder's arithmetic T, scale and offset rounded to T once on the host.  TWO roundings -- multiply, then subtract, never an
+// fma (the library is built with -ffp-contract=off) -- so a CPU restatement in IEEE arithmetic gives the same bits.  The map is monotone
+// non-decreasing, rounding included, hence commutes with min exactly: a kernel may correct its d inputs before the minimum network or
+// the minima after it.  +inf stays +inf (padding positions); scale = 1, offset = 0 is the identity on m >= 0.
+template <typename T>
+struct Correction {
+    T scale, offset;
+};
+template <typename T>
+__device__ __forceinline__ T msa_correct(T m, T scale, T offset) {
+    T t = m * scale;
+    t = t - offset;
+    return t > T(0) ? t : T(0);
+}
+template <typename T, int DCMAX, bool CORRECTED = false>
+__device__ __forceinline__ void cn_msa(T (&v)[DCMAX], int deg, Correction<T> k = Correction<T>{T(1), T(0)}) {
     T min1 = real_traits<T>::inf(), min2 = real_traits<T>::inf();
     int arg1 = 0;
     bool parity = false;
@@ -49,6 +71,10 @@ __device__ __forceinline__ void cn_msa(T (&v)[DCMAX], int deg) {
             }
         }
     }
+    if constexpr (CORRECTED) {  // the two minima, not the deg messages: the correction commutes with min
+        min1 = msa_correct(min1, k.scale, k.offset);
+        min2 = msa_correct(min2, k.scale, k.offset);
+    }
 #pragma unroll
     for (int j = 0; j < DCMAX; ++j) {
         if (j < deg) {
@@ -58,6 +84,27 @@ __device__ __forceinline__ void cn_msa(T (&v)[DCMAX], int deg) {
         }
     }
 }
+// The pass kernels' LAST integer argument (k_cn: freeze, k_cn16: cpw).  A corrected min-sum instantiation carries (scale, offset) behind
+// it; every other instantiation sees the plain int, so its argument block -- and with it its kernel descriptor -- is what it always was.
+template <typename T>
+struct IntAndCorrection {
+    int value;
+    T scale, offset;
+};
+template <typename T, int ALG>
+struct last_int_arg {
+    using type = int;
+    static __host__ __device__ __forceinline__ int value(int a) { return a; }
+    static __host__ __device__ __forceinline__ Correction<T> correction(int) { return Correction<T>{T(1), T(0)}; }
+    static __host__ __forceinline__ int make(int v, double, double) { return v; }
+};
+template <typename T>
+struct last_int_arg<T, ALG_NMSA> {
+    using type = IntAndCorrection<T>;
+    static __host__ __device__ __forceinline__ int value(const type& a) { return a.value; }
+    static __host__ __device__ __forceinline__ Correction<T> correction(const type& a) { return Correction<T>{a.scale, a.offset}; }
+    static __host__ __forceinline__ type make(int v, double scale, double offset) { return type{v, (T)scale, (T)offset}; }
+};
 
 // ---- sum-product, fp64: the reference formula verbatim ---------------------------------------------
 // t = tanh(v/2); row product = sign * exp(sum(log|t|)); extrinsic = product / t_own; 2*atanh with +-1 -> +-inf.
@@ -268,11 +315,13 @@ __device__ __forceinline__ void cn_spa(float (&v)[DCMAX], int deg) {
 }
 
 template <typename T, int ALG, int DCMAX>
-__device__ __forceinline__ void cn_rule(T (&v)[DCMAX], int deg) {
-    if constexpr (ALG == 0) {
+__device__ __forceinline__ void cn_rule(T (&v)[DCMAX], int deg, Correction<T> k = Correction<T>{T(1), T(0)}) {
+    if constexpr (ALG == ALG_MSA) {
         cn_msa<T, DCMAX>(v, deg);
+    } else if constexpr (ALG == ALG_NMSA) {
+        cn_msa<T, DCMAX, true>(v, deg, k);
     } else {
-        static_assert(ALG == 1, "min-sum or sum-product (the erasure decoder is bit-sliced: ldpc_bec_planes.hpp)");
+        static_assert(ALG == ALG_SPA, "min-sum, corrected min-sum or sum-product (the erasure decoder is bit-sliced: ldpc_bec_planes.hpp)");
         cn_spa<DCMAX>(v, deg);
     }
 }

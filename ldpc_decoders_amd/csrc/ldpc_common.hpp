@@ -24,7 +24,11 @@
 
 namespace ldpc {
 
-enum Alg : int { ALG_MSA = 0, ALG_SPA = 1, ALG_BEC = 2 };
+enum Alg : int { ALG_MSA = 0, ALG_SPA = 1, ALG_BEC = 2, ALG_NMSA = 3 };  // ALG_NMSA: normalised / offset min-sum (ldpc_cn.hpp cn_msa<.., true>)
+// min-sum family: everything that is keyed on "the rule is compare / negate only" (register tuning, sign-bit shortcuts, table words) treats
+// the corrected rule as min-sum
+constexpr bool alg_is_minsum(int alg) { return alg == ALG_MSA || alg == ALG_NMSA; }
+constexpr int alg_family(int alg) { return alg == ALG_NMSA ? (int)ALG_MSA : alg; }
 enum DType : int { DT_F32 = 0, DT_F64 = 1, DT_F16 = 2 };  // DT_F16: fp16 STORAGE of the streaming messages, fp32 arithmetic and priors
 enum Backend : int { BK_AUTO = 0, BK_STREAM = 1, BK_FUSED = 2 };
 enum Channel : int { CH_BIAWGN = 0, CH_BSC = 1, CH_BEC = 2 };
@@ -116,6 +120,7 @@ enum BufKind : int {
 struct Decoder {
     Code* code = nullptr;
     int alg = ALG_MSA, dtype = DT_F32, backend = BK_AUTO;
+    double corr_scale = 1.0, corr_offset = 0.0;  // ALG_NMSA: c2v = sign * max(scale * min - offset, 0) (ldpc_decoder_set_correction); read at every launch
     // streaming workspace: set[0] holds the state when a decode begins, every frame repack moves it to the other set
     TileSet set[2];
     DevBuf c2v16;      // fp16 storage: check -> variable lines, rebuilt by every check pass (not part of a set: a repack does not move them)

@@ -65,7 +65,9 @@ int upload_vec(const std::vector<T>& h, T** d) {
 const std::vector<ShapeEntry>& all_shapes() {
     static const std::vector<ShapeEntry> v = [] {
         std::vector<ShapeEntry> out;
-        for (auto fn : {fused_shapes_f32_dc6, fused_shapes_f32_dcx, fused_shapes_f64_dc6, fused_shapes_f64_dcx, fused_shapes_bec}) {
+        // (the corrected min-sum tables come last: the indices of the shapes that were there before them do not move)
+        for (auto fn : {fused_shapes_f32_dc6, fused_shapes_f32_dcx, fused_shapes_f64_dc6, fused_shapes_f64_dcx, fused_shapes_bec, fused_shapes_nmsa_f32_dc6,
+                        fused_shapes_nmsa_f32_dcx, fused_shapes_nmsa_f64_dc6, fused_shapes_nmsa_f64_dcx}) {
             int cnt = 0;
             const ShapeEntry* p = fn(&cnt);
             out.insert(out.end(), p, p + cnt);
@@ -688,6 +690,16 @@ static int fused_launch(Decoder* d, FusedArgs& a, bool sim, int64_t B, int32_t m
     // exact-in-fp32 mode: the guarded variant of the kernel, its grid constants and the violation counter
     const int grid_k = LDPC_FLAG_PRIOR_GRID_OF(flags);
     const void* kern = sim ? shape.kernel_sim : shape.kernel;
+    if (d->alg == ALG_NMSA) {
+        if (grid_k >= 0) {
+            set_error("prior grid: corrected min-sum (LDPC_ALG_NMSA) has no exact-in-fp32 mode (a scale takes values off the grid)");
+            return LDPC_E_UNSUPPORTED;
+        }
+        a.corr_scale_d = d->corr_scale;  // (shares its bytes with the grid constants, which these kernels never read)
+        a.corr_offset_d = d->corr_offset;
+        a.corr_scale = (float)d->corr_scale;
+        a.corr_offset = (float)d->corr_offset;
+    }
     if (grid_k >= 0) {
         if (shape.esz == 8) {
             // fp64 arithmetic needs no guard; the Monte-Carlo kernels of the fp64 / erasure decoders draw their noise unquantised

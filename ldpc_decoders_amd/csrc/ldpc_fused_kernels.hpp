@@ -67,6 +67,12 @@ const ShapeEntry* fused_shapes_f32_dcx(int* count);
 const ShapeEntry* fused_shapes_f64_dc6(int* count);
 const ShapeEntry* fused_shapes_f64_dcx(int* count);
 const ShapeEntry* fused_shapes_bec(int* count);  // bit-sliced erasure decoder (ldpc_bec_kernels.hpp)
+// corrected min-sum (ALG_NMSA): one sibling of every min-sum shape above, in the same order -- a decoder never changes shape because the
+// correction is on
+const ShapeEntry* fused_shapes_nmsa_f32_dc6(int* count);
+const ShapeEntry* fused_shapes_nmsa_f32_dcx(int* count);
+const ShapeEntry* fused_shapes_nmsa_f64_dc6(int* count);
+const ShapeEntry* fused_shapes_nmsa_f64_dcx(int* count);
 
 namespace {
 
@@ -207,8 +213,18 @@ struct FusedArgs {
     unsigned long long round_stride;
     // exact-in-fp32 mode: priors are rounded to multiples of 1 / grid_scale (SIM: in the kernel; decode: by the channel kernel); a frame
     // in which some |v2c|, |marginal| reaches grid_limit -- beyond it an fp32 sum of grid multiples may round -- is counted in grid_viol
-    float grid_scale, grid_inv, grid_limit;
-    unsigned long long* grid_viol;  // [0] frames beyond the guard since the last reset, [1 .. GRID_REDO_CAP] their global indices (redo list)
+    // Corrected min-sum (ALG_NMSA) refuses the exact-in-fp32 mode, and no other kernel reads its (scale, offset): the two share these 24
+    // bytes, so the argument block of every kernel that existed before the corrected ones is what it was (size, offsets, descriptor).
+    union {
+        struct {
+            float grid_scale, grid_inv, grid_limit;
+            unsigned long long* grid_viol;  // [0] frames beyond the guard since the last reset, [1 .. GRID_REDO_CAP] their global indices (redo list)
+        };
+        struct {
+            double corr_scale_d, corr_offset_d;  // fp64 kernels: |c2v| = max(fl(fl(scale * min) - offset), 0), ldpc_cn.hpp
+            float corr_scale, corr_offset;       // fp32 kernels: the same values rounded to float once on the host
+        };
+    };
 };
 constexpr int GRID_REDO_CAP = 4095;
 
@@ -223,6 +239,7 @@ constexpr int GRID_REDO_CAP = 4095;
 // in the sweep instead.  Counts found by compiling each shape over a grid of values (tools/kernel_resources.py; the CPU test
 // tests/test_host_cpu.py::test_simulate_kernels_do_not_spill pins the result): the smallest counts with no spilled register.
 constexpr int sim_opaque_cn(int alg, int nw, int vrx_arg_) {
+    alg = alg_family(alg);  // corrected min-sum: the min-sum settings (two more scalars, no more vector registers)
     const int vrx = wide_rounds(vrx_arg_);
     // two-wave irregular min-sum on the shape with pair rounds (34 instead of 40 variable-phase gathers): 4 + 4 packed words, two spilled
     // registers -- 2.84 ms per 65 536 frames at 1.0 dB against 3.03 (15 + 8, the two-width shape's setting), 2.85 (0 + 0, 2 + 2), 2.91 (6 + 6),
@@ -234,6 +251,7 @@ constexpr int sim_opaque_cn(int alg, int nw, int vrx_arg_) {
     return 15;                                            // irregular shapes (wide variable rounds)
 }
 constexpr int sim_opaque_vn(int alg, int nw, int vrx_arg_) {
+    alg = alg_family(alg);
     const int vrx = wide_rounds(vrx_arg_);
     if (nw == 2 && pair_rounds(vrx_arg_) > 0) return alg == ALG_MSA ? 4 : 8;
     if (nw > 4) return alg == ALG_SPA ? 15 : 0;
@@ -307,7 +325,7 @@ __device__ __forceinline__ void fused_bp_body(const FusedArgs& A) {
 #pragma unroll
     for (int i = 0; i < VNW; ++i) vn_idx[i] = A.vn_tab[(w * VNW + i) * 64 + lane];
     // variable index of each owned slot (-1: padding): resident in registers where the budget allows, else re-read per frame
-    constexpr bool VMAP_RESIDENT = !SIM && !BIG && ((NW == 1) || (ALG == ALG_MSA));
+    constexpr bool VMAP_RESIDENT = !SIM && !BIG && ((NW == 1) || (alg_is_minsum(ALG)));
     int vmap_reg[VMAP_RESIDENT ? VRW : 1];
     if constexpr (VMAP_RESIDENT) {
 #pragma unroll
@@ -334,7 +352,7 @@ __device__ __forceinline__ void fused_bp_body(const FusedArgs& A) {
     // private segment (13 scratch_load_dword on an otherwise idle vector-memory pipe instead of 47 unpack instructions): 17.86 ms against
     // 18.70 (one-instruction unpack, no spill) and 19.10 (shift + add unpack, no spill) per 32 768 frames, profiles/r03C_spill_or_unpack.txt.
     // The GUARDED min-sum kernel keeps most table words packed (grid_opaque_cn) and does take the one-instruction unpack: +10 % (round 6).
-    constexpr bool MAD = BIG && (GRID || !(ALG == ALG_MSA && SIM));
+    constexpr bool MAD = BIG && (GRID || !(alg_is_minsum(ALG) && SIM));
     const bool own_last = !(SYS && w == NW - 1);  // with a system row, wave NW-1 never writes its last marginal row
     // the sign of an outgoing message is merged with ONE v_and_or_b32 (inline asm; the compiler emits v_and_b32 + v_or_b32 for the same
     // expression in this kernel): the IEEE sign bit lives in a scalar register
@@ -590,7 +608,7 @@ __device__ __forceinline__ void fused_bp_body(const FusedArgs& A) {
             // The sweep is one software-pipelined stream of LDS traffic: the gathers of check round r+1 (variable
             // group g+1) are issued before round r (group g) is computed, so a wave always has a full round of
             // ds_reads in flight while it does arithmetic.
-            constexpr int VG = BIG ? 1 : ((ALG == ALG_MSA && NW == 1) ? 4 : 2);  // variable rounds per pipeline stage (register budget)
+            constexpr int VG = BIG ? 1 : ((alg_is_minsum(ALG) && NW == 1) ? 4 : 2);  // variable rounds per pipeline stage (register budget)
             constexpr int NVG = (VRN + VG - 1) / VG;
             for (;;) {
                 if (max_iter > 0 && it >= max_iter) break;
@@ -647,8 +665,8 @@ __device__ __forceinline__ void fused_bp_body(const FusedArgs& A) {
                     }
                     // leave-one-out reduction of |v|: minimum (min-sum) or join of 1 - tanh(|v|/2) (sum-product, ldpc_cn.hpp)
                     float pre[DC], suf[DC];
-                    float preo[ALG == ALG_MSA ? 1 : DC], sufo[ALG == ALG_MSA ? 1 : DC];  // odd parts (sum-product only)
-                    if constexpr (ALG == ALG_MSA && DC == 6) {
+                    float preo[alg_is_minsum(ALG) ? 1 : DC], sufo[alg_is_minsum(ALG) ? 1 : DC];  // odd parts (sum-product only)
+                    if constexpr (alg_is_minsum(ALG) && DC == 6) {
                         // 11 minimum instructions for the six leave-one-out minima (v_min3_f32 where three inputs meet)
                         const float s3 = fminf(a[4], a[5]), s2 = fminf(fminf(a[3], a[4]), a[5]), s1 = fminf(a[2], s2);
                         const float p2 = fminf(a[0], a[1]), p3 = fminf(fminf(a[0], a[1]), a[2]);
@@ -658,7 +676,7 @@ __device__ __forceinline__ void fused_bp_body(const FusedArgs& A) {
                         pre[3] = fminf(p3, s3);                suf[3] = pre[3];
                         pre[4] = fminf(fminf(p3, a[3]), a[5]); suf[4] = pre[4];
                         pre[5] = fminf(fminf(p3, a[3]), a[4]); suf[5] = pre[5];
-                    } else if constexpr (ALG == ALG_MSA) {  // prefix / suffix minima, 3 DC - 6 instructions (no +inf seeds: fminf(inf, x) is not foldable)
+                    } else if constexpr (alg_is_minsum(ALG)) {  // prefix / suffix minima, 3 DC - 6 instructions (no +inf seeds: fminf(inf, x) is not foldable)
                         static_assert(DC >= 3, "prefix / suffix network");
                         pre[1] = a[0];
 #pragma unroll
@@ -690,10 +708,21 @@ __device__ __forceinline__ void fused_bp_body(const FusedArgs& A) {
                             spa_eo_push(suf[j], sufo[j], a[j + 1]);
                         }
                     }
+                    // corrected min-sum: the DC outputs of the minimum network (correcting its DC inputs instead -- the same values, the map
+                    // commutes with min -- keeps six more registers alive: |v| is a free source modifier, a corrected |v| is not; the two-wave
+                    // n = 1200 Monte-Carlo kernel spilled six registers that way).  +inf stays +inf.  Done here, not in the store loop below:
+                    // that lambda is shared with every other rule and stays as it is
+                    if constexpr (ALG == ALG_NMSA) {
+#pragma unroll
+                        for (int j = 0; j < DC; ++j) {
+                            pre[j] = msa_correct(fminf(pre[j], suf[j]), A.corr_scale, A.corr_offset);
+                            suf[j] = pre[j];
+                        }
+                    }
                     static_for<0, DC>([&](auto J_) {
                         constexpr int j = decltype(J_)::value;
                         float mag;
-                        if constexpr (ALG == ALG_MSA) mag = fminf(pre[j], suf[j]);
+                        if constexpr (alg_is_minsum(ALG)) mag = fminf(pre[j], suf[j]);
                         else if constexpr (DC == 6) mag = pre[j];
                         else mag = spa2_llr_of_eo(spa2_join(spa_f2{pre[j], preo[j]}, spa_f2{suf[j], sufo[j]}));
                         // GRID, rows that may hold padding positions: the outgoing magnitudes themselves are watched (the incoming |v2c|
@@ -744,7 +773,7 @@ __device__ __forceinline__ void fused_bp_body(const FusedArgs& A) {
                     }
                     if (q < VRW - 1 || own_last) lds_st_tid<q * 256>(m1);
                     // decision: (m1 < 0); for min-sum the sign bit itself (m1 is never -0.0 and never NaN for finite priors)
-                    if constexpr (ALG == ALG_MSA) xr = __builtin_amdgcn_alignbit(xr, __float_as_uint(m1), 31);  // (xr << 1) | sign: rows come in ascending q
+                    if constexpr (alg_is_minsum(ALG)) xr = __builtin_amdgcn_alignbit(xr, __float_as_uint(m1), 31);  // (xr << 1) | sign: rows come in ascending q
                     else xb |= (m1 < 0.0f) ? (1u << q) : 0u;
                 };
                 if constexpr (VRX > 0) {  // wide rounds of irregular codes: DVX gathers per variable, one round per stage
@@ -792,7 +821,7 @@ __device__ __forceinline__ void fused_bp_body(const FusedArgs& A) {
                         }
                     });
                 });
-                if constexpr (ALG == ALG_MSA) xb = __brev(xr) >> (32 - VRW);  // bit q = row q again
+                if constexpr (alg_is_minsum(ALG)) xb = __brev(xr) >> (32 - VRW);  // bit q = row q again
                 if constexpr (NW > 1) wg_barrier(); else __builtin_amdgcn_wave_barrier();
                 ++it;
             }
@@ -871,6 +900,7 @@ __global__ LDPC_FUSED_BP_BOUNDS void k_fused_bp_grid(const FusedArgs A) {
 // fp64 belief propagation on the LDS: the reference's own arithmetic (src/bpa.py:17-63 computes in float64).
 //   ALG_MSA  min-sum (src/bpa.py:86-102): only add/sub/compare -> hard decisions and iteration counts bit-identical to the
 //            reference on identical priors -- at LDS speed instead of HBM speed.
+//   ALG_NMSA corrected min-sum (ldpc_cn.hpp): ALG_MSA with |c2v| = max(scale * min - offset, 0); same shapes, same register tuning.
 //   ALG_SPA  sum-product, the reference formula verbatim (src/bpa.py:66-75, src/math_utils.py:47-60: tanh, exp-sum-log product,
 //            divide, atanh, +-1 -> +-inf; inf - inf -> NaN -> decision 0) through cn_spa<double> of ldpc_cn.hpp, i.e. the very
 //            same device code as the streaming kernel: bit-identical to it.  The row sum of log|tanh| is order dependent, so
@@ -884,7 +914,7 @@ __global__ LDPC_FUSED_BP_BOUNDS void k_fused_bp_grid(const FusedArgs A) {
 // priors) and error counting in the kernel -- priors and decisions never exist in HBM.
 template <int ALG, int DC, int DV, int CRW, int VRW, int NW, bool SIM, int VRXA, int DVX>
 __global__ __launch_bounds__(64 * NW, NW == 4 ? 4 : 2) void k_fused_f64(const FusedArgs A) {
-    static_assert(ALG == ALG_MSA || ALG == ALG_SPA, "LLR decoders");
+    static_assert(ALG == ALG_MSA || ALG == ALG_SPA || ALG == ALG_NMSA, "LLR decoders");
     constexpr int VRX = wide_rounds(VRXA), VR2 = pair_rounds(VRXA);  // as in fused_bp_body
     static_assert(VR2 == 0 || (VRX > 0 && DV > 2 && VRX + VR2 <= VRW), "pair rounds belong to the irregular shapes");
     constexpr int VR = VRW * NW, NPAD = VR * 64;
@@ -1133,7 +1163,7 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 4 : 2) void k_fused_f64(const Fu
                     double v[DC];
 #pragma unroll
                     for (int j = 0; j < DC; ++j) v[j] = mg[cur][j] - c2v_old[r][j];
-                    if constexpr (ALG == ALG_MSA) {
+                    if constexpr (alg_is_minsum(ALG)) {
                         double a[DC];
                         uint32_t vx = 0, mx = 0;  // XOR of the sign words (high dwords); v is never -0.0 (marginals start from +0.0 sums)
 #pragma unroll
@@ -1173,6 +1203,10 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 4 : 2) void k_fused_f64(const Fu
 #pragma unroll
                             for (int j = 1; j < DC - 1; ++j) mag[j] = fmin(pre[j], suf[j]);
                         }
+                        if constexpr (ALG == ALG_NMSA) {  // corrected min-sum: the outputs of the minimum network (see fused_bp_body)
+#pragma unroll
+                            for (int j = 0; j < DC; ++j) mag[j] = msa_correct(mag[j], A.corr_scale_d, A.corr_offset_d);
+                        }
 #pragma unroll
                         for (int j = 0; j < DC; ++j) {
                             const uint32_t sgn = (vx ^ (uint32_t)__double2hiint(v[j])) & 0x80000000u;
@@ -1200,12 +1234,12 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 4 : 2) void k_fused_f64(const Fu
                 };
                 check_rows(std::integral_constant<int, CRW>{});
                 // narrow variable rounds, VG of them per pipeline stage (see the variable phase below)
-                constexpr int VG = ALG == ALG_MSA ? 3 : 1;
+                constexpr int VG = alg_is_minsum(ALG) ? 3 : 1;
                 constexpr int NVG = (VRN + VG - 1) / VG;
-                constexpr bool EARLY_GATHERS = NW > 1 && VRX == 0 && ALG == ALG_MSA;
+                constexpr bool EARLY_GATHERS = NW > 1 && VRX == 0 && alg_is_minsum(ALG);
                 double cv[2][VG][DV];
                 bool unsat;
-                const bool mine_unsat = ALG == ALG_MSA ? (__ballot((synd & 0x80000000u) != 0u) != 0) : (synd_mask != 0);
+                const bool mine_unsat = alg_is_minsum(ALG) ? (__ballot((synd & 0x80000000u) != 0u) != 0) : (synd_mask != 0);
                 if constexpr (EARLY_GATHERS) {
                     post_verdict(mine_unsat);
                     const uint32_t vw = load_verdict();
@@ -1229,7 +1263,7 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 4 : 2) void k_fused_f64(const Fu
                     const double m1 = prior[q] + sn;
                     if (q < VRW - 1 || own_last) lds_st64<q * 512>(marg_vaddr, m1);
                     // (m1 < 0).  Min-sum: the sign bit itself -- m1 is never -0.0 (sums start from +0.0) nor NaN for finite priors
-                    if constexpr (ALG == ALG_MSA) xr = __builtin_amdgcn_alignbit(xr, (uint32_t)__double2hiint(m1), 31);
+                    if constexpr (alg_is_minsum(ALG)) xr = __builtin_amdgcn_alignbit(xr, (uint32_t)__double2hiint(m1), 31);
                     else xb |= (m1 < 0.0) ? (1u << q) : 0u;
                 };
                 if constexpr (VRX > 0) {  // wide rounds: DVX gathers per variable (missing edges read the zero double)
@@ -1280,7 +1314,7 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 4 : 2) void k_fused_f64(const Fu
                         }
                     });
                 });
-                if constexpr (ALG == ALG_MSA) xb = __brev(xr) >> (32 - VRW);
+                if constexpr (alg_is_minsum(ALG)) xb = __brev(xr) >> (32 - VRW);
                 phase_barrier();
                 ++it;
             }

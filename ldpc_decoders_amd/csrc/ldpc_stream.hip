@@ -184,8 +184,9 @@ template <typename T, int ALG, int DCMAX, int FIXED_DC, int UNR, bool GATHER = f
 __global__ __launch_bounds__(256) void k_cn(const int32_t* __restrict__ row_ptr, const int32_t* __restrict__ edge_var,
                                             T* __restrict__ c2v, const T* __restrict__ src,
                                             const u64* __restrict__ live, int m, int n, int64_t E, int tiles, int chunks,
-                                            int cpw, int first, int xcd_aware, int freeze, const T* __restrict__ c2v_in = nullptr,
-                                            const int32_t* __restrict__ srcmap = nullptr) {
+                                            int cpw, int first, int xcd_aware, typename last_int_arg<T, ALG>::type freeze_arg,
+                                            const T* __restrict__ c2v_in = nullptr, const int32_t* __restrict__ srcmap = nullptr) {
+    const int freeze = last_int_arg<T, ALG>::value(freeze_arg);  // (corrected min-sum: scale and offset ride behind it, ldpc_cn.hpp)
     const int lane = threadIdx.x;
     int tile, chunk;
     if (!task_of(tiles, chunks, xcd_aware, &tile, &chunk)) return;
@@ -258,7 +259,7 @@ __global__ __launch_bounds__(256) void k_cn(const int32_t* __restrict__ row_ptr,
 #pragma unroll
                     for (int j = 0; j < DCMAX; ++j) v[u][j] = v2c_of<T, ALG>(v[u][j], o[u][j]);
                 }
-                cn_rule<T, ALG, DCMAX>(v[u], deg[u]);
+                cn_rule<T, ALG, DCMAX>(v[u], deg[u], last_int_arg<T, ALG>::correction(freeze_arg));
 #pragma unroll
                 for (int j = 0; j < DCMAX; ++j) {
                     if (j < deg[u]) msg_st<CN_NTS>(ct + (int64_t)(k0[u] + j) * 64, v[u][j]);
@@ -679,6 +680,7 @@ constexpr int unroll_for(int row_bytes) {
 struct Geometry {
     int tiles, cn_chunks, cpw, vn_chunks, vpw, xcd_aware;
     int freeze = 0;  // lanes of departed frames do not compute or store (soft-output decodes)
+    double corr_scale = 1.0, corr_offset = 0.0;  // corrected min-sum (Decoder::corr_scale / corr_offset at the time of the call)
 };
 
 // The two passes.  GATHER (c2v_in / prior_out + srcmap): the sweep that carries a folded repack; those forms are built for the node
@@ -691,7 +693,8 @@ void dispatch_cn(const Code* c, T* c2v, const T* src, const u64* live, const Geo
         constexpr int DCMAX = decltype(dcm)::value, UNR = unroll_for(2 * DCMAX * (int)sizeof(T));  // old message + marginal line per edge
         if constexpr (!GATHER || DCMAX <= 8)
             hipLaunchKernelGGL((k_cn<T, ALG, DCMAX, decltype(fdc)::value, UNR, GATHER>), dim3(task_blocks(g.tiles, g.cn_chunks, g.xcd_aware)), dim3(64, 4), 0, st,
-                               c->d_row_ptr, c->d_edge_var, c2v, src, live, c->m, c->n, c->E, g.tiles, g.cn_chunks, g.cpw, first, g.xcd_aware, g.freeze, c2v_in, srcmap);
+                               c->d_row_ptr, c->d_edge_var, c2v, src, live, c->m, c->n, c->E, g.tiles, g.cn_chunks, g.cpw, first, g.xcd_aware,
+                               last_int_arg<T, ALG>::make(g.freeze, g.corr_scale, g.corr_offset), c2v_in, srcmap);
     });
 }
 template <typename T, int ALG, bool GATHER = false>
@@ -699,8 +702,9 @@ void dispatch_vn(const Code* c, const T* c2v, const T* prior, T* marg, const u64
                  const int32_t* srcmap = nullptr) {
     var_class<true>(c, [&](auto dvm, auto fdv) {
         constexpr int DVMAX = decltype(dvm)::value, UNR = unroll_for((DVMAX + 1) * (int)sizeof(T));
+        // (the variable pass does not depend on the check rule: corrected min-sum launches the min-sum instantiations)
         if constexpr (!GATHER || DVMAX <= 8)
-            hipLaunchKernelGGL((k_vn<T, ALG, DVMAX, UNR, decltype(fdv)::value, GATHER>), dim3(task_blocks(g.tiles, g.vn_chunks, g.xcd_aware)), dim3(64, 4), 0, st,
+            hipLaunchKernelGGL((k_vn<T, alg_family(ALG), DVMAX, UNR, decltype(fdv)::value, GATHER>), dim3(task_blocks(g.tiles, g.vn_chunks, g.xcd_aware)), dim3(64, 4), 0, st,
                                c->d_col_ptr, c->d_col_edge, c2v, prior, marg, live, xbits, c->n, c->E, g.tiles, g.vn_chunks, g.vpw, g.xcd_aware, g.freeze, prior_out, srcmap);
     });
 }
@@ -776,6 +780,8 @@ int run(Decoder* d, const DecodeCall& k, const SimSource* sim = nullptr) {
     Geometry g;
     g.tiles = tiles;
     g.freeze = k.soft != nullptr ? 1 : 0;
+    g.corr_scale = d->corr_scale;
+    g.corr_offset = d->corr_offset;
     // Nodes per wave.  The marginal lines a check pass gathers are re-used dv times; the fewer tiles are in flight at once, the
     // more of those re-reads hit on chip -- so a tile is cut into MANY short wave tasks (tile-major task order).  Measured on one
     // MI355X (sweep of 32 768 frames of the (3,6) n = 64 800 shape, profiles/r03_stream_chunking.txt): 64 checks per wave 20.9 ms,
@@ -1008,7 +1014,10 @@ __global__ __launch_bounds__(256) void k_biawgn_tile16(SimSource s, int64_t B, i
 template <int ALG, int DCMAX, int FIXED_DC, int UNR, bool FIRST>
 __global__ __launch_bounds__(256) void k_cn16(const int32_t* __restrict__ row_ptr, const int32_t* __restrict__ edge_var, const int32_t* __restrict__ edge_vpos,
                                               __half2* __restrict__ c2v, const __half2* __restrict__ v2c, const float2* __restrict__ prior_t,
-                                              const u64* __restrict__ live, int m, int n, int64_t E, int pairs, int tiles, int chunks, int cpw) {
+                                              const u64* __restrict__ live, int m, int n, int64_t E, int pairs, int tiles, int chunks,
+                                              typename last_int_arg<float, ALG>::type cpw_arg) {
+    const int cpw = last_int_arg<float, ALG>::value(cpw_arg);  // (corrected min-sum: scale and offset ride behind it, ldpc_cn.hpp)
+    const Correction<float> corr = last_int_arg<float, ALG>::correction(cpw_arg);  // applied in fp32, before the message is rounded to half
     const int lane = threadIdx.x;
     int P, chunk;
     if (!task_of(pairs, chunks, 0, &P, &chunk)) return;
@@ -1046,8 +1055,8 @@ __global__ __launch_bounds__(256) void k_cn16(const int32_t* __restrict__ row_pt
         }
 #pragma unroll
         for (int u = 0; u < UNR; ++u) {
-            cn_rule<float, ALG, DCMAX>(vx[u], deg[u]);
-            cn_rule<float, ALG, DCMAX>(vy[u], deg[u]);
+            cn_rule<float, ALG, DCMAX>(vx[u], deg[u], corr);
+            cn_rule<float, ALG, DCMAX>(vy[u], deg[u], corr);
 #pragma unroll
             for (int j = 0; j < DCMAX; ++j)
                 if (j < deg[u]) msg16_st<ALG>(ct + (int64_t)(k0[u] + j) * 64, vx[u][j], vy[u][j]);
@@ -1314,12 +1323,13 @@ int run16(Decoder* d, const DecodeCall& k, const SimSource* sim) {
         check_class(c, [&](auto dcm, auto fdc) {
             constexpr int DCM = decltype(dcm)::value, FDC = decltype(fdc)::value, UNR = DCM <= 6 ? 2 : 1;
             const auto kern = it == 0 ? k_cn16<ALG, DCM, FDC, UNR, true> : k_cn16<ALG, DCM, FDC, UNR, false>;
-            hipLaunchKernelGGL(kern, cgrid, blk, 0, st, c->d_row_ptr, c->d_edge_var, edge_vpos, msg, v2c, prior, live, m, n, E, pairs, tiles, cn_chunks, cpw);
+            hipLaunchKernelGGL(kern, cgrid, blk, 0, st, c->d_row_ptr, c->d_edge_var, edge_vpos, msg, v2c, prior, live, m, n, E, pairs, tiles, cn_chunks,
+                               last_int_arg<float, ALG>::make(cpw, d->corr_scale, d->corr_offset));
         });
         LDPC_TRY(prof.mark(1));
         var_class<false>(c, [&](auto dvm, auto fdv) {
             constexpr int DVM = decltype(dvm)::value, UNR = DVM <= 4 ? 4 : (DVM == 8 ? 2 : 1);
-            hipLaunchKernelGGL((k_vn16<ALG, DVM, UNR, decltype(fdv)::value>), vgrid, blk, 0, st, c->d_col_ptr, c->d_col_edge, msg, v2c, prior, marg, live, xbits, n, E,
+            hipLaunchKernelGGL((k_vn16<alg_family(ALG), DVM, UNR, decltype(fdv)::value>), vgrid, blk, 0, st, c->d_col_ptr, c->d_col_edge, msg, v2c, prior, marg, live, xbits, n, E,
                                pairs, tiles, vn_chunks, vpw);
         });
         LDPC_TRY(prof.mark(2));
@@ -1338,11 +1348,13 @@ bool batch_fits(int64_t B) {
 
 template <typename T>
 int run_alg(Decoder* d, const DecodeCall& k, const SimSource* sim) {
+    if (d->alg == ALG_NMSA) return run<T, ALG_NMSA>(d, k, sim);
     return d->alg == ALG_MSA ? run<T, ALG_MSA>(d, k, sim) : run<T, ALG_SPA>(d, k, sim);
 }
 
 // LLR decoders: the driver of the decoder's storage type; with `sim` the priors are drawn into the tiles instead of loaded
 int run_llr(Decoder* d, const DecodeCall& k, const SimSource* sim) {
+    if (d->dtype == DT_F16 && d->alg == ALG_NMSA) return run16<ALG_NMSA>(d, k, sim);
     if (d->dtype == DT_F16) return d->alg == ALG_MSA ? run16<ALG_MSA>(d, k, sim) : run16<ALG_SPA>(d, k, sim);  // priors are fp32
     return d->dtype == DT_F64 ? run_alg<double>(d, k, sim) : run_alg<float>(d, k, sim);
 }

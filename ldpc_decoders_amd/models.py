@@ -7,6 +7,7 @@ upstream names (LP, ADMMA) resolve to a class that raises on construction.
 from . import bec, biawgn, bsc
 
 decoder_names = ["ML", "SPA", "MSA", "LP", "ADMM", "ADMMA"]  # src/utils.py:16
+extra_decoder_names = ["NMSA"]  # this build's own decoders (no upstream counterpart): corrected min-sum, bpa.NMSA
 
 
 def _unavailable(name):
