@@ -39,6 +39,25 @@ enum { LDPC_ALG_MSA = 0, LDPC_ALG_SPA = 1, LDPC_ALG_BEC = 2 };      /* decoder s
  * is bit-identical to LDPC_ALG_MSA.  Every dtype and backend, the same kernel shapes and layout plans as LDPC_ALG_MSA; accepted wherever
  * LDPC_ALG_MSA is, except LDPC_FLAG_PRIOR_GRID (LDPC_E_UNSUPPORTED on every backend: a scale takes values off the grid). */
 enum { LDPC_ALG_NMSA = 3 };
+/* Fixed-point min-sum: the decoder that is built in silicon -- q-bit channel values, q-bit saturating messages, a correction that stays on
+ * the integer grid.  No upstream counterpart: it modifies src/bpa.py:86-102 the way LDPC_ALG_NMSA does.  Parameters (decoder state,
+ * ldpc_decoder_set_fixed_point): bits q in 2..12 (default 6), frac_bits k in -8..8 (2), scale a multiple of 1/64 in (0, 1] (0.8125), offset
+ * an integer >= 0 in levels (0).  V = 2^(q-1) - 1.
+ *   1. Quantiser, the decoder's input stage:  level_v = clamp(rint(prior_v * 2^k), -V, +V), evaluated in the type the priors arrive in; the
+ *      multiply is exact, rint rounds half to even, +-inf becomes +-V.  The caller's buffer is const and is not modified; NaN priors are
+ *      outside the contract.  Everything below is in levels.
+ *   2. Check rule: with s_j the sign of src/bpa.py:86-102 (sgn(0) = +1) and m_j = min(V, min_{i != j} |v2c_i|),
+ *          c2v_j = s_j * max( floor(scale * m_j) - offset, 0 ).
+ *      A check of degree 1 sends max(floor(scale * V) - offset, 0), not +inf.  scale * m is exact in fp32 (64 scale <= 64, m <= 2047).
+ *   3. Everything else of BPA.decode (src/bpa.py:17-63) is unchanged: marginal = level + sum of c2v; v2c = marginal - c2v is stored
+ *      unsaturated and saturates at the next check's input (hardware whose APP registers hold ceil(log2(V (1 + dv_max))) + 1 bits);
+ *      syndrome exit, the iteration-0 check of y0 and marginal < 0 <=> bit 1 as upstream.  The soft output of ldpc_decode_soft is in levels.
+ *   4. Exactness: every value is an integer of magnitude <= V (1 + dv_max) < 2^24, every c2v <= 2047 (exact in fp16).  LDPC_DTYPE_F64, _F32
+ *      and _F16 decoders, streaming and LDS-resident backend, return identical decisions, iteration counts and (converted) soft outputs for
+ *      the same priors, provided those are exactly representable in fp32 -- and equal an all-integer model of the rule.
+ * Same kernel shapes and layout plans as LDPC_ALG_MSA; accepted wherever LDPC_ALG_MSA is, except LDPC_FLAG_PRIOR_GRID (LDPC_E_UNSUPPORTED: it
+ * would add nothing). */
+enum { LDPC_ALG_QMSA = 4 };
 enum { LDPC_DTYPE_F32 = 0, LDPC_DTYPE_F64 = 1,                       /* message arithmetic                             */
        LDPC_DTYPE_F16 = 2 };  /* fp16 STORAGE of the check messages on the streaming kernels, fp32 arithmetic, fp32 priors / channel output:
                                * a throughput mode for codes whose state lives in HBM (the E-sized traffic halves); held to a
@@ -141,6 +160,13 @@ int ldpc_decoder_kernel_name(ldpc_decoder_t dec, int simulate, char* buf, int64_
 int ldpc_decoder_set_correction(ldpc_decoder_t dec, double scale, double offset);
 /* The values in force (LDPC_E_ARG for a decoder of another algorithm).  No upstream counterpart (src/bpa.py:86-102 has neither). */
 int ldpc_decoder_get_correction(ldpc_decoder_t dec, double* scale, double* offset);
+/* Word length and correction of a fixed-point min-sum decoder (LDPC_ALG_QMSA, see there).  No upstream counterpart (src/bpa.py:86-102 has
+ * none of them).  2 <= bits <= 12, -8 <= frac_bits <= 8, scale a multiple of 1/64 with 0 < scale <= 1, offset >= 0 in levels; LDPC_E_ARG
+ * otherwise and for a decoder of another algorithm (ldpc_decoder_set_correction in turn refuses an LDPC_ALG_QMSA decoder).  After
+ * ldpc_decoder_create: 6, 2, 0.8125, 0.  Decoder state, read when a call is enqueued: a change takes effect from the next call. */
+int ldpc_decoder_set_fixed_point(ldpc_decoder_t dec, int bits, int frac_bits, double scale, int offset);
+/* The values in force (LDPC_E_ARG for a decoder of another algorithm).  No upstream counterpart (src/bpa.py:86-102). */
+int ldpc_decoder_get_fixed_point(ldpc_decoder_t dec, int* bits, int* frac_bits, double* scale, int* offset);
 
 /* Per-kernel timing for roofline reports: when enabled, decode calls bracket their dominant kernels with HIP events
  * recorded ON THE DECODE STREAM and accumulate elapsed milliseconds / launch counts per kernel class:

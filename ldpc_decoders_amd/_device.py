@@ -45,6 +45,18 @@ def check_correction(scale, offset):
     return scale, offset
 
 
+def check_fixed_point(bits, frac_bits, scale, offset):
+    """The range ``ldpc_decoder_set_fixed_point`` accepts -- 2 <= bits <= 12, -8 <= frac_bits <= 8, scale a multiple of 1/64 in (0, 1], an
+    integer offset >= 0 (in levels) -- checked before any device call.  -> (bits, frac_bits, scale, offset) as int, int, float, int."""
+    scale, off = float(scale), float(offset)
+    ok = float(bits) == int(bits) and float(frac_bits) == int(frac_bits) and 2 <= int(bits) <= 12 and -8 <= int(frac_bits) <= 8
+    ok = ok and 0.0 < scale <= 1.0 and scale * 64.0 == int(scale * 64.0) and 0.0 <= off < float("inf") and off == int(off)
+    if not ok:
+        raise ValueError("fixed-point min-sum needs 2 <= bits <= 12, -8 <= frac_bits <= 8, a scale on the 1/64 grid with 0 < scale <= 1 and an "
+                         "integer offset >= 0 (got bits=%r, frac_bits=%r, scale=%r, offset=%r)" % (bits, frac_bits, scale, offset))
+    return int(bits), int(frac_bits), scale, int(off)
+
+
 class CodeHandle:
     def __init__(self, code, device):
         lib = _lib.load()
@@ -102,6 +114,17 @@ class DecoderHandle:
         s, o = ctypes.c_double(0), ctypes.c_double(0)
         _lib.check(_lib.load().ldpc_decoder_get_correction(self.h, ctypes.byref(s), ctypes.byref(o)))
         return s.value, o.value
+
+    # ---- fixed-point min-sum (alg="QMSA"): q-bit levels, c2v = sign * max(floor(scale * min(m, V)) - offset, 0); decoder state, in force
+    # from the next call
+    def set_fixed_point(self, bits, frac_bits, scale, offset=0):
+        bits, frac_bits, scale, offset = check_fixed_point(bits, frac_bits, scale, offset)
+        _lib.check(_lib.load().ldpc_decoder_set_fixed_point(self.h, bits, frac_bits, scale, offset))
+
+    def fixed_point(self):
+        b, k, o, s = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0), ctypes.c_double(0)
+        _lib.check(_lib.load().ldpc_decoder_get_fixed_point(self.h, ctypes.byref(b), ctypes.byref(k), ctypes.byref(s), ctypes.byref(o)))
+        return b.value, k.value, s.value, o.value
 
     # ---- host (numpy) buffers
     def decode_host(self, priors, y0, max_iter, flags=0):

@@ -60,6 +60,15 @@ class NMSA:
                                   "to correct; use SPA / MSA there")
 
 
+class QMSA:
+    """Fixed-point min-sum has no meaning over the erasure channel either: the ternary decoder has no magnitudes to quantise."""
+    id_keys = ["max_iter", "msa_bits", "msa_frac_bits", "msa_scale", "msa_offset"]
+
+    def __init__(self, *a, **k):
+        raise NotImplementedError("decoder QMSA (fixed-point min-sum) does not exist over the bec: the erasure decoder has no magnitudes "
+                                  "to quantise; use SPA / MSA there")
+
+
 class ADMM:  # src/bec.py:38-45,58-62: LLR wrapper with +-1e8 for the known symbols, 0 for an erasure
     id_keys = admm.ADMM.id_keys
     channel = "bec"

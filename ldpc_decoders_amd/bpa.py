@@ -12,7 +12,7 @@ Extra constructor keywords (all optional):
 """
 import numpy as np
 
-from ._device import DecoderHandle, as_code, check_correction
+from ._device import DecoderHandle, as_code, check_correction, check_fixed_point
 
 
 class BPA:
@@ -100,3 +100,21 @@ class NMSA(BPA):
         self.msa_scale, self.msa_offset = check_correction(0.8125 if scale is None else scale, 0.0 if offset is None else offset)
         super().__init__(parity_mtx, **kwargs)
         self.handle.set_correction(self.msa_scale, self.msa_offset)
+
+
+class QMSA(BPA):
+    """Fixed-point min-sum (no upstream counterpart): the decoder as silicon builds it.  Priors are quantised to ``msa_bits``-bit levels,
+    ``clamp(rint(prior * 2**msa_frac_bits), -V, V)`` with ``V = 2**(msa_bits - 1) - 1``; every check message is
+    ``sign * max(floor(msa_scale * min(m, V)) - msa_offset, 0)`` (``msa_scale`` on the 1/64 grid, ``msa_offset`` an integer number of levels).
+    All values are small integers: every precision and backend returns the same decisions and iteration counts, those of an all-integer
+    model.  Same ``decode`` / ``decode_batch``, kernels and shapes as ``MSA``; soft outputs are in levels."""
+    alg = "QMSA"
+    id_keys = ["max_iter", "msa_bits", "msa_frac_bits", "msa_scale", "msa_offset"]
+
+    def __init__(self, parity_mtx, **kwargs):
+        given = [kwargs.get(k) for k in ("msa_bits", "msa_frac_bits", "msa_scale", "msa_offset")]
+        values = [d if v is None else v for v, d in zip(given, (6, 2, 0.8125, 0))]
+        # (checked before the decoder is created: a bad value never reaches the device)
+        self.msa_bits, self.msa_frac_bits, self.msa_scale, self.msa_offset = check_fixed_point(*values)
+        super().__init__(parity_mtx, **kwargs)
+        self.handle.set_fixed_point(self.msa_bits, self.msa_frac_bits, self.msa_scale, self.msa_offset)

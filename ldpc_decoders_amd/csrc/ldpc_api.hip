@@ -146,6 +146,10 @@ int grid_guard_available(const Decoder* d, int bk, uint32_t flags, const char* w
         set_error("%s: prior grid: corrected min-sum (LDPC_ALG_NMSA) has no exact-in-fp32 mode (a scale takes values off the grid)", who);
         return LDPC_E_UNSUPPORTED;
     }
+    if (LDPC_FLAG_PRIOR_GRID_OF(flags) >= 0 && d->alg == ALG_QMSA) {  // likewise
+        set_error("%s: prior grid: fixed-point min-sum (LDPC_ALG_QMSA) quantises its priors itself (ldpc_decoder_set_fixed_point)", who);
+        return LDPC_E_UNSUPPORTED;
+    }
     if (LDPC_FLAG_PRIOR_GRID_OF(flags) < 0 || d->dtype == DT_F64) return LDPC_OK;
     if (bk == BK_FUSED && d->alg == ALG_MSA) return LDPC_OK;
     set_error("%s: prior grid: the exactness guard lives in the LDS-resident fp32 min-sum kernels; this decoder runs on the streaming kernels", who);
@@ -300,7 +304,7 @@ int ldpc_code_info(ldpc_code_t h, int32_t* m, int32_t* n, int64_t* E, int32_t* m
 int ldpc_plan_layout(int32_t m, int32_t n, int64_t E, const int32_t* chk, const int32_t* var, int alg, int dtype, int64_t moves,
                      const char* out_dir, double* info4) {
     return guarded("ldpc_plan_layout", [&]() -> int {
-        if (!info4 || alg < 0 || alg > ALG_NMSA || dtype < 0 || dtype > 1) {
+        if (!info4 || alg < 0 || alg > ALG_QMSA || dtype < 0 || dtype > 1) {
             set_error("ldpc_plan_layout: bad arguments (alg=%d dtype=%d)", alg, dtype);
             return LDPC_E_ARG;
         }
@@ -312,7 +316,7 @@ int ldpc_plan_layout(int32_t m, int32_t n, int64_t E, const int32_t* chk, const 
 
 int ldpc_decoder_create(ldpc_code_t code, int alg, int dtype, int backend, ldpc_decoder_t* out) {
     return guarded("ldpc_decoder_create", [&]() -> int {
-        if (!code || !out || alg < 0 || alg > ALG_NMSA || dtype < 0 || dtype > 2 || (dtype == DT_F16 && (alg == ALG_BEC || backend == BK_FUSED)) ||
+        if (!code || !out || alg < 0 || alg > ALG_QMSA || dtype < 0 || dtype > 2 || (dtype == DT_F16 && (alg == ALG_BEC || backend == BK_FUSED)) ||
             backend < 0 || backend > 2) {
             set_error("ldpc_decoder_create: bad arguments (alg=%d dtype=%d backend=%d)", alg, dtype, backend);
             return LDPC_E_ARG;
@@ -395,6 +399,42 @@ int ldpc_decoder_get_correction(ldpc_decoder_t h, double* scale, double* offset)
         }
         *scale = d->corr_scale;
         *offset = d->corr_offset;
+        return LDPC_OK;
+    });
+}
+
+int ldpc_decoder_set_fixed_point(ldpc_decoder_t h, int bits, int frac_bits, double scale, int offset) {
+    return guarded("ldpc_decoder_set_fixed_point", [&]() -> int {
+        Decoder* d = (Decoder*)h;
+        if (!d || d->alg != ALG_QMSA) {
+            set_error("ldpc_decoder_set_fixed_point: a fixed-point min-sum decoder (LDPC_ALG_QMSA) is needed");
+            return LDPC_E_ARG;
+        }
+        // (written so that a NaN scale fails; 64 * scale is exact, so the grid test is)
+        if (bits < 2 || bits > 12 || frac_bits < -8 || frac_bits > 8 || !(scale > 0.0 && scale <= 1.0) || 64.0 * scale != std::floor(64.0 * scale) || offset < 0) {
+            set_error("ldpc_decoder_set_fixed_point: 2 <= bits <= 12, -8 <= frac_bits <= 8, scale a multiple of 1/64 in (0, 1] and offset >= 0 are needed "
+                      "(bits=%d frac_bits=%d scale=%g offset=%d)", bits, frac_bits, scale, offset);
+            return LDPC_E_ARG;
+        }
+        d->fx_bits = bits;
+        d->fx_frac = frac_bits;
+        d->fx_scale = scale;
+        d->fx_offset = offset;
+        return LDPC_OK;
+    });
+}
+
+int ldpc_decoder_get_fixed_point(ldpc_decoder_t h, int* bits, int* frac_bits, double* scale, int* offset) {
+    return guarded("ldpc_decoder_get_fixed_point", [&]() -> int {
+        Decoder* d = (Decoder*)h;
+        if (!d || !bits || !frac_bits || !scale || !offset || d->alg != ALG_QMSA) {
+            set_error("ldpc_decoder_get_fixed_point: a fixed-point min-sum decoder (LDPC_ALG_QMSA) and four result pointers are needed");
+            return LDPC_E_ARG;
+        }
+        *bits = d->fx_bits;
+        *frac_bits = d->fx_frac;
+        *scale = d->fx_scale;
+        *offset = d->fx_offset;
         return LDPC_OK;
     });
 }
@@ -904,8 +944,17 @@ static int simulate_impl(ldpc_decoder_t h, int channel, double param, int codewo
         set_error("ldpc_simulate: prior grid: corrected min-sum (LDPC_ALG_NMSA) has no exact-in-fp32 mode (a scale takes values off the grid)");
         return LDPC_E_UNSUPPORTED;
     }
+    if (grid_k >= 0 && d->alg == ALG_QMSA) {
+        set_error("ldpc_simulate: prior grid: fixed-point min-sum (LDPC_ALG_QMSA) quantises its priors itself (ldpc_decoder_set_fixed_point)");
+        return LDPC_E_UNSUPPORTED;
+    }
+    // Fixed-point min-sum over a BSC whose LLR is (close to) less than half a level: every prior quantises to level 0 and no longer carries the
+    // received bit, which the Monte-Carlo LDS kernels read off the prior's sign -- composed path below (the channel kernel hands y0 over)
+    const bool level0_bsc = d->alg == ALG_QMSA && channel == CH_BSC && param > 0.0 && param < 1.0 &&
+                            std::fabs(std::log((1.0 - param) / param)) * d->fx_step() < 0.75;
     // (fp64 decoders with a prior grid take the composed path below: quantised priors from the channel kernel, no guard needed)
-    if (d->backend != BK_STREAM && fused_simulate_supported(d, channel, param, hist_bins) && !(grid_k >= 0 && d->dtype == DT_F64 && d->alg != ALG_BEC))
+    if (d->backend != BK_STREAM && !level0_bsc && fused_simulate_supported(d, channel, param, hist_bins) &&
+        !(grid_k >= 0 && d->dtype == DT_F64 && d->alg != ALG_BEC))
         return fused_simulate(d, channel, param, codeword, seed, stream_id, frame0, B, max_iter, flags, hist_bins, counters, st);
     if (grid_k >= 0 && (d->dtype != DT_F64 || channel == CH_BEC)) {
         set_error("prior grid: the exactness guard lives in the LDS-resident fp32 min-sum kernels; this decoder runs on the streaming kernels");

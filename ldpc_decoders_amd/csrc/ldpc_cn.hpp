@@ -5,6 +5,7 @@
 //
 //   min-sum      reference src/bpa.py:86-102 (+ src/math_utils.py:10,38-43,78-94)
 //   corrected min-sum (normalised / offset; no upstream counterpart): the same with |c2v| = max(fl(fl(scale * min) - offset), 0)
+//   fixed-point min-sum (q-bit saturating messages; no upstream counterpart): the same on integer levels, |c2v| = max(floor(scale * min(m, V)) - offset, 0)
 //   sum-product  reference src/bpa.py:71-75  (+ src/math_utils.py:47-60)
 //   (erasure decoder, src/bec.py:100-112: bit-sliced, ldpc_bec_planes.hpp / ldpc_bec_kernels.hpp / ldpc_bec_stream.hip)
 #pragma once
@@ -52,8 +53,40 @@ __device__ __forceinline__ T msa_correct(T m, T scale, T offset) {
     t = t - offset;
     return t > T(0) ? t : T(0);
 }
-template <typename T, int DCMAX, bool CORRECTED = false>
-__device__ __forceinline__ void cn_msa(T (&v)[DCMAX], int deg, Correction<T> k = Correction<T>{T(1), T(0)}) {
+//
+// FIXED POINT (q-bit min-sum as decoders in silicon compute it; no upstream counterpart).  Every value is an integer number of LEVELS held
+// in T.  With V = 2^(q-1) - 1:
+//     level_v = clamp( rint(prior_v * 2^k), -V, +V )                               (quantise_prior: where the priors enter the decoder)
+//     |c2v_j| = max( floor(scale * min(m_j, V)) - offset, 0 ),   m_j = min_{i != j} |v_i|,   sign as above
+// scale a multiple of 1/64 in (0, 1], offset an integer >= 0.  64 scale <= 64 and min(m, V) <= 2047, so the product is exact in fp32 (and in
+// fp64): the floor sees the true value, and fp64, fp32 and fp16-storage decoders compute the same integers as an all-integer model.  The
+// incoming |v2c| is saturated (min(., V)), the stored v2c = marginal - c2v is not: hardware with wide enough APP registers.  A check whose
+// minimum is empty (degree 1; +inf from padding positions) sends floor(scale * V) - offset.  Clamp and floor are monotone: like the
+// correction above the map commutes with min and is applied to the two minima.
+// Evaluated as  med3( floor(scale * m) - offset, 0, cap )  with cap = max(floor(scale * V) - offset, 0) from the host: the saturation moved
+// behind the (monotone) scale / floor / offset -- one instruction less and the same value: for m <= V the product is exact and the two
+// forms are the same expression; for m > V (up to V (1 + dv_max), where the fp32 product may round) rounding is monotone, so fl(scale * m)
+// >= scale * V, which is representable, and the result is cap either way; +inf gives cap.
+__device__ __forceinline__ float msa_fixed(float m, float scale, float offset, float cap) {
+    return __builtin_amdgcn_fmed3f(__builtin_floorf(m * scale) - offset, 0.0f, cap);
+}
+__device__ __forceinline__ double msa_fixed(double m, double scale, double offset, double cap) {
+    double t = __builtin_floor(m * scale) - offset;
+    t = t < cap ? t : cap;
+    return t > 0.0 ? t : 0.0;
+}
+// the decoder's input stage: a multiply by a power of two (exact), round half to even, saturate; + 0 turns a level of -0 into +0 (the
+// LDS kernels read decisions and message signs off the IEEE sign bit)
+template <typename T>
+__device__ __forceinline__ T quantise_prior(T prior, T step, T vmax) {
+    T q = __builtin_elementwise_rint(prior * step);
+    q = q < vmax ? q : vmax;
+    q = q > -vmax ? q : -vmax;
+    return q + T(0);
+}
+enum MsaMode : int { MSA_PLAIN = 0, MSA_CORRECTED = 1, MSA_FIXED = 2 };
+template <typename T, int DCMAX, int MODE = MSA_PLAIN>
+__device__ __forceinline__ void cn_msa(T (&v)[DCMAX], int deg, Correction<T> k = Correction<T>{T(1), T(0)}, T cap = T(0)) {
     T min1 = real_traits<T>::inf(), min2 = real_traits<T>::inf();
     int arg1 = 0;
     bool parity = false;
@@ -71,9 +104,13 @@ __device__ __forceinline__ void cn_msa(T (&v)[DCMAX], int deg, Correction<T> k =
             }
         }
     }
-    if constexpr (CORRECTED) {  // the two minima, not the deg messages: the correction commutes with min
+    if constexpr (MODE == MSA_CORRECTED) {  // the two minima, not the deg messages: the correction commutes with min
         min1 = msa_correct(min1, k.scale, k.offset);
         min2 = msa_correct(min2, k.scale, k.offset);
+    }
+    if constexpr (MODE == MSA_FIXED) {  // likewise; an empty minimum (+inf) saturates
+        min1 = msa_fixed(min1, k.scale, k.offset, cap);
+        min2 = msa_fixed(min2, k.scale, k.offset, cap);
     }
 #pragma unroll
     for (int j = 0; j < DCMAX; ++j) {
@@ -85,7 +122,8 @@ __device__ __forceinline__ void cn_msa(T (&v)[DCMAX], int deg, Correction<T> k =
     }
 }
 // The pass kernels' LAST integer argument (k_cn: freeze, k_cn16: cpw).  A corrected min-sum instantiation carries (scale, offset) behind
-// it; every other instantiation sees the plain int, so its argument block -- and with it its kernel descriptor -- is what it always was.
+// it, a fixed-point one (scale, offset, cap); every other instantiation sees the plain int, so its argument block -- and with it its kernel
+// descriptor -- is what it always was.
 template <typename T>
 struct IntAndCorrection {
     int value;
@@ -96,14 +134,29 @@ struct last_int_arg {
     using type = int;
     static __host__ __device__ __forceinline__ int value(int a) { return a; }
     static __host__ __device__ __forceinline__ Correction<T> correction(int) { return Correction<T>{T(1), T(0)}; }
-    static __host__ __forceinline__ int make(int v, double, double) { return v; }
+    static __host__ __device__ __forceinline__ T cap(int) { return T(0); }
+    static __host__ __forceinline__ int make(int v, double, double, double = 0.0) { return v; }
 };
 template <typename T>
 struct last_int_arg<T, ALG_NMSA> {
     using type = IntAndCorrection<T>;
     static __host__ __device__ __forceinline__ int value(const type& a) { return a.value; }
     static __host__ __device__ __forceinline__ Correction<T> correction(const type& a) { return Correction<T>{a.scale, a.offset}; }
-    static __host__ __forceinline__ type make(int v, double scale, double offset) { return type{v, (T)scale, (T)offset}; }
+    static __host__ __device__ __forceinline__ T cap(const type&) { return T(0); }
+    static __host__ __forceinline__ type make(int v, double scale, double offset, double = 0.0) { return type{v, (T)scale, (T)offset}; }
+};
+template <typename T>
+struct IntAndFixedPoint {
+    int value;
+    T scale, offset, cap;  // cap = max(floor(scale * V) - offset, 0), msa_fixed
+};
+template <typename T>
+struct last_int_arg<T, ALG_QMSA> {
+    using type = IntAndFixedPoint<T>;
+    static __host__ __device__ __forceinline__ int value(const type& a) { return a.value; }
+    static __host__ __device__ __forceinline__ Correction<T> correction(const type& a) { return Correction<T>{a.scale, a.offset}; }
+    static __host__ __device__ __forceinline__ T cap(const type& a) { return a.cap; }
+    static __host__ __forceinline__ type make(int v, double scale, double offset, double cap) { return type{v, (T)scale, (T)offset, (T)cap}; }
 };
 
 // ---- sum-product, fp64: the reference formula verbatim ---------------------------------------------
@@ -315,13 +368,15 @@ __device__ __forceinline__ void cn_spa(float (&v)[DCMAX], int deg) {
 }
 
 template <typename T, int ALG, int DCMAX>
-__device__ __forceinline__ void cn_rule(T (&v)[DCMAX], int deg, Correction<T> k = Correction<T>{T(1), T(0)}) {
+__device__ __forceinline__ void cn_rule(T (&v)[DCMAX], int deg, Correction<T> k = Correction<T>{T(1), T(0)}, T cap = T(0)) {
     if constexpr (ALG == ALG_MSA) {
         cn_msa<T, DCMAX>(v, deg);
     } else if constexpr (ALG == ALG_NMSA) {
-        cn_msa<T, DCMAX, true>(v, deg, k);
+        cn_msa<T, DCMAX, MSA_CORRECTED>(v, deg, k);
+    } else if constexpr (ALG == ALG_QMSA) {
+        cn_msa<T, DCMAX, MSA_FIXED>(v, deg, k, cap);
     } else {
-        static_assert(ALG == ALG_SPA, "min-sum, corrected min-sum or sum-product (the erasure decoder is bit-sliced: ldpc_bec_planes.hpp)");
+        static_assert(ALG == ALG_SPA, "min-sum, corrected / fixed-point min-sum or sum-product (the erasure decoder is bit-sliced: ldpc_bec_planes.hpp)");
         cn_spa<DCMAX>(v, deg);
     }
 }

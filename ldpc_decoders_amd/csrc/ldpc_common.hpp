@@ -24,11 +24,15 @@
 
 namespace ldpc {
 
-enum Alg : int { ALG_MSA = 0, ALG_SPA = 1, ALG_BEC = 2, ALG_NMSA = 3 };  // ALG_NMSA: normalised / offset min-sum (ldpc_cn.hpp cn_msa<.., true>)
+enum Alg : int {
+    ALG_MSA = 0, ALG_SPA = 1, ALG_BEC = 2,
+    ALG_NMSA = 3,  // normalised / offset min-sum (ldpc_cn.hpp cn_msa<.., MSA_CORRECTED>)
+    ALG_QMSA = 4   // fixed-point min-sum: q-bit saturating messages on the integer grid (ldpc_cn.hpp cn_msa<.., MSA_FIXED>, quantise_prior)
+};
 // min-sum family: everything that is keyed on "the rule is compare / negate only" (register tuning, sign-bit shortcuts, table words) treats
 // the corrected rule as min-sum
-constexpr bool alg_is_minsum(int alg) { return alg == ALG_MSA || alg == ALG_NMSA; }
-constexpr int alg_family(int alg) { return alg == ALG_NMSA ? (int)ALG_MSA : alg; }
+constexpr bool alg_is_minsum(int alg) { return alg == ALG_MSA || alg == ALG_NMSA || alg == ALG_QMSA; }
+constexpr int alg_family(int alg) { return (alg == ALG_NMSA || alg == ALG_QMSA) ? (int)ALG_MSA : alg; }
 enum DType : int { DT_F32 = 0, DT_F64 = 1, DT_F16 = 2 };  // DT_F16: fp16 STORAGE of the streaming messages, fp32 arithmetic and priors
 enum Backend : int { BK_AUTO = 0, BK_STREAM = 1, BK_FUSED = 2 };
 enum Channel : int { CH_BIAWGN = 0, CH_BSC = 1, CH_BEC = 2 };
@@ -121,6 +125,17 @@ struct Decoder {
     Code* code = nullptr;
     int alg = ALG_MSA, dtype = DT_F32, backend = BK_AUTO;
     double corr_scale = 1.0, corr_offset = 0.0;  // ALG_NMSA: c2v = sign * max(scale * min - offset, 0) (ldpc_decoder_set_correction); read at every launch
+    // ALG_QMSA (ldpc_decoder_set_fixed_point; read at every launch): priors -> clamp(rint(prior * 2^fx_frac), -V, V), V = 2^(fx_bits - 1) - 1;
+    // c2v = sign * max(floor(fx_scale * min(m, V)) - fx_offset, 0)
+    int fx_bits = 6, fx_frac = 2, fx_offset = 0;
+    double fx_scale = 0.8125;
+    double fx_vmax() const { return (double)((1 << (fx_bits - 1)) - 1); }
+    double fx_offset_eff() const { return fx_offset > 4096 ? 4096.0 : (double)fx_offset; }  // beyond V <= 2047 every message is 0 already
+    double fx_cap() const {  // what a saturated minimum sends: max(floor(scale * V) - offset, 0)
+        const double c = (double)(long long)(fx_scale * fx_vmax()) - fx_offset_eff();
+        return c > 0.0 ? c : 0.0;
+    }
+    double fx_step() const { return fx_frac >= 0 ? (double)(1 << fx_frac) : 1.0 / (double)(1 << -fx_frac); }
     // streaming workspace: set[0] holds the state when a decode begins, every frame repack moves it to the other set
     TileSet set[2];
     DevBuf c2v16;      // fp16 storage: check -> variable lines, rebuilt by every check pass (not part of a set: a repack does not move them)

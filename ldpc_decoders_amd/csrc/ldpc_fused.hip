@@ -11,6 +11,7 @@
 
 #include <algorithm>
 #include <cstdlib>
+#include <cstring>
 #include <string>
 #include <numeric>
 
@@ -67,7 +68,8 @@ const std::vector<ShapeEntry>& all_shapes() {
         std::vector<ShapeEntry> out;
         // (the corrected min-sum tables come last: the indices of the shapes that were there before them do not move)
         for (auto fn : {fused_shapes_f32_dc6, fused_shapes_f32_dcx, fused_shapes_f64_dc6, fused_shapes_f64_dcx, fused_shapes_bec, fused_shapes_nmsa_f32_dc6,
-                        fused_shapes_nmsa_f32_dcx, fused_shapes_nmsa_f64_dc6, fused_shapes_nmsa_f64_dcx}) {
+                        fused_shapes_nmsa_f32_dcx, fused_shapes_nmsa_f64_dc6, fused_shapes_nmsa_f64_dcx, fused_shapes_qmsa_f32_dc6,
+                        fused_shapes_qmsa_f32_dcx, fused_shapes_qmsa_f64_dc6, fused_shapes_qmsa_f64_dcx}) {
             int cnt = 0;
             const ShapeEntry* p = fn(&cnt);
             out.insert(out.end(), p, p + cnt);
@@ -699,6 +701,26 @@ static int fused_launch(Decoder* d, FusedArgs& a, bool sim, int64_t B, int32_t m
         a.corr_offset_d = d->corr_offset;
         a.corr_scale = (float)d->corr_scale;
         a.corr_offset = (float)d->corr_offset;
+    }
+    if (d->alg == ALG_QMSA) {
+        if (grid_k >= 0) {
+            set_error("prior grid: fixed-point min-sum (LDPC_ALG_QMSA) quantises its priors itself (ldpc_decoder_set_fixed_point)");
+            return LDPC_E_UNSUPPORTED;
+        }
+        // (share their bytes with the grid constants, which these kernels never read)
+        const double fx[5] = {d->fx_scale, d->fx_offset_eff(), d->fx_cap(), d->fx_step(), d->fx_vmax()};  // FX_SCALE .. FX_VMAX
+        for (int i = 0; i < 5; ++i) {
+            const float f = (float)fx[i];
+            uint64_t w64;
+            uint32_t w32;
+            std::memcpy(&w64, &fx[i], 8);
+            std::memcpy(&w32, &f, 4);
+            if ((double)f != fx[i] || (uint32_t)w64 != 0u) {  // cannot happen for values ldpc_decoder_set_fixed_point accepts
+                set_error("fixed-point min-sum: constant %d (%g) is not exact in fp32", i, fx[i]);
+                return LDPC_E_ARG;
+            }
+            a.fx_word[i] = shape.esz == 8 ? (uint32_t)(w64 >> 32) : w32;
+        }
     }
     if (grid_k >= 0) {
         if (shape.esz == 8) {

@@ -73,6 +73,11 @@ const ShapeEntry* fused_shapes_nmsa_f32_dc6(int* count);
 const ShapeEntry* fused_shapes_nmsa_f32_dcx(int* count);
 const ShapeEntry* fused_shapes_nmsa_f64_dc6(int* count);
 const ShapeEntry* fused_shapes_nmsa_f64_dcx(int* count);
+// fixed-point min-sum (ALG_QMSA): likewise, one sibling of every min-sum shape in the same order
+const ShapeEntry* fused_shapes_qmsa_f32_dc6(int* count);
+const ShapeEntry* fused_shapes_qmsa_f32_dcx(int* count);
+const ShapeEntry* fused_shapes_qmsa_f64_dc6(int* count);
+const ShapeEntry* fused_shapes_qmsa_f64_dcx(int* count);
 
 namespace {
 
@@ -224,9 +229,17 @@ struct FusedArgs {
             double corr_scale_d, corr_offset_d;  // fp64 kernels: |c2v| = max(fl(fl(scale * min) - offset), 0), ldpc_cn.hpp
             float corr_scale, corr_offset;       // fp32 kernels: the same values rounded to float once on the host
         };
+        // Fixed-point min-sum (ALG_QMSA) refuses the exact-in-fp32 mode as well and shares the same bytes: scale, offset and cap of the rule
+        // (ldpc_cn.hpp msa_fixed), step = 2^frac_bits and V of the quantiser (quantise_prior), see FX_*.  All five are small integers or
+        // multiples of 1/64, exact in fp32: the fp32 kernels get their IEEE single words, the fp64 kernels the HIGH words of the doubles
+        // (the low words are zero) -- the constants then stay in scalar registers in both, never converted in the vector ALU.
+        uint32_t fx_word[5];
     };
 };
 constexpr int GRID_REDO_CAP = 4095;
+enum { FX_SCALE = 0, FX_OFFSET = 1, FX_CAP = 2, FX_STEP = 3, FX_VMAX = 4 };
+__device__ __forceinline__ float fx_f32(const FusedArgs& A, int i) { return __uint_as_float(A.fx_word[i]); }
+__device__ __forceinline__ double fx_f64(const FusedArgs& A, int i) { return __hiloint2double((int)A.fx_word[i], 0); }
 
 // Monte-Carlo counters of a workgroup (SIM kernels) in ONE register: lanes [0, hist_bins) hold the histogram of executed sweeps,
 // lanes 60..63 tot / wec / bec / iter_sum (src/main.py:41-45) as 32-bit partial sums, added to the global 64-bit counters every
@@ -517,6 +530,7 @@ __device__ __forceinline__ void fused_bp_body(const FusedArgs& A) {
                     for (int t = 0; t < 4; ++t) {
                         pri4[t] = -(A.sim_k * (A.sim_mean + A.sim_sigma * z[t]));
                         if constexpr (GRID) pri4[t] = __builtin_rintf(pri4[t] * A.grid_scale) * A.grid_inv;  // both scalings are exact (powers of two)
+                        if constexpr (ALG == ALG_QMSA) pri4[t] = quantise_prior(pri4[t], fx_f32(A, FX_STEP), fx_f32(A, FX_VMAX));  // the decoder's input stage: LLR -> level
                         if constexpr (ALG == ALG_SPA) pri4[t] *= SPA2_LOG2E;  // sum-product runs in the base-2 LLR domain (ldpc_cn.hpp)
                     }
                 } else {  // CH_BSC: same integer threshold and the same LLR expression as k_discrete
@@ -524,6 +538,8 @@ __device__ __forceinline__ void fused_bp_body(const FusedArgs& A) {
                     for (int t = 0; t < 4; ++t) {
                         const int y = A.codeword ^ ((u64)ph.w[t] < A.bsc_thr ? 1 : 0);
                         pri4[t] = (GRID ? __builtin_rintf(A.bsc_llr * A.grid_scale) * A.grid_inv : A.bsc_llr) * (float)(1 - 2 * y);
+                        // (fixed-point: the host keeps an LLR below one level away from this kernel -- level 0 would lose the received bit)
+                        if constexpr (ALG == ALG_QMSA) pri4[t] = quantise_prior(pri4[t], fx_f32(A, FX_STEP), fx_f32(A, FX_VMAX));
                         if constexpr (ALG == ALG_SPA) pri4[t] *= SPA2_LOG2E;
                     }
                 }
@@ -545,6 +561,12 @@ __device__ __forceinline__ void fused_bp_body(const FusedArgs& A) {
                 prior[q] = v >= 0 ? pf[v] : 0.0f;
                 if constexpr (ALG == ALG_SPA) prior[q] *= SPA2_LOG2E;  // base-2 LLR domain (ldpc_cn.hpp); the soft output is scaled back
             }
+        }
+        if constexpr (ALG == ALG_QMSA && !SIM) {
+            // the decoder's input stage: priors -> integer levels (ldpc_cn.hpp quantise_prior), once per frame (the Monte-Carlo kernels do
+            // it on the LLR itself, above)
+#pragma unroll
+            for (int q = 0; q < VRW; ++q) prior[q] = quantise_prior(prior[q], fx_f32(A, FX_STEP), fx_f32(A, FX_VMAX));
         }
         if constexpr (VRX > 0) {
             // the padding slot of short check rows is a variable known with certainty: +inf LLR (bit 0) -- it never wins a minimum, adds
@@ -716,6 +738,13 @@ __device__ __forceinline__ void fused_bp_body(const FusedArgs& A) {
 #pragma unroll
                         for (int j = 0; j < DC; ++j) {
                             pre[j] = msa_correct(fminf(pre[j], suf[j]), A.corr_scale, A.corr_offset);
+                            suf[j] = pre[j];
+                        }
+                    }
+                    if constexpr (ALG == ALG_QMSA) {  // fixed-point min-sum: likewise on the outputs; +inf (an empty minimum) saturates at V
+#pragma unroll
+                        for (int j = 0; j < DC; ++j) {
+                            pre[j] = msa_fixed(fminf(pre[j], suf[j]), fx_f32(A, FX_SCALE), fx_f32(A, FX_OFFSET), fx_f32(A, FX_CAP));
                             suf[j] = pre[j];
                         }
                     }
@@ -901,6 +930,7 @@ __global__ LDPC_FUSED_BP_BOUNDS void k_fused_bp_grid(const FusedArgs A) {
 //   ALG_MSA  min-sum (src/bpa.py:86-102): only add/sub/compare -> hard decisions and iteration counts bit-identical to the
 //            reference on identical priors -- at LDS speed instead of HBM speed.
 //   ALG_NMSA corrected min-sum (ldpc_cn.hpp): ALG_MSA with |c2v| = max(scale * min - offset, 0); same shapes, same register tuning.
+//   ALG_QMSA fixed-point min-sum (ldpc_cn.hpp): priors quantised to levels as they enter, |c2v| = max(floor(scale * min(m, V)) - offset, 0).
 //   ALG_SPA  sum-product, the reference formula verbatim (src/bpa.py:66-75, src/math_utils.py:47-60: tanh, exp-sum-log product,
 //            divide, atanh, +-1 -> +-inf; inf - inf -> NaN -> decision 0) through cn_spa<double> of ldpc_cn.hpp, i.e. the very
 //            same device code as the streaming kernel: bit-identical to it.  The row sum of log|tanh| is order dependent, so
@@ -914,7 +944,7 @@ __global__ LDPC_FUSED_BP_BOUNDS void k_fused_bp_grid(const FusedArgs A) {
 // priors) and error counting in the kernel -- priors and decisions never exist in HBM.
 template <int ALG, int DC, int DV, int CRW, int VRW, int NW, bool SIM, int VRXA, int DVX>
 __global__ __launch_bounds__(64 * NW, NW == 4 ? 4 : 2) void k_fused_f64(const FusedArgs A) {
-    static_assert(ALG == ALG_MSA || ALG == ALG_SPA || ALG == ALG_NMSA, "LLR decoders");
+    static_assert(ALG == ALG_MSA || ALG == ALG_SPA || ALG == ALG_NMSA || ALG == ALG_QMSA, "LLR decoders");
     constexpr int VRX = wide_rounds(VRXA), VR2 = pair_rounds(VRXA);  // as in fused_bp_body
     static_assert(VR2 == 0 || (VRX > 0 && DV > 2 && VRX + VR2 <= VRW), "pair rounds belong to the irregular shapes");
     constexpr int VR = VRW * NW, NPAD = VR * 64;
@@ -1069,11 +1099,16 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 4 : 2) void k_fused_f64(const Fu
                     box_muller<double>(ph.w[2], ph.w[3], z[2], z[3]);
 #pragma unroll
                     for (int t = 0; t < 4; ++t) pri4[t] = -(A.sim_k_d * (A.sim_mean_d + A.sim_sigma_d * z[t]));
+                    if constexpr (ALG == ALG_QMSA) {  // the decoder's input stage: LLR -> level (see fused_bp_body)
+#pragma unroll
+                        for (int t = 0; t < 4; ++t) pri4[t] = quantise_prior(pri4[t], fx_f64(A, FX_STEP), fx_f64(A, FX_VMAX));
+                    }
                 } else {  // BSC: same integer threshold and the same LLR expression as k_discrete
 #pragma unroll
                     for (int t = 0; t < 4; ++t) {
                         const int y = A.codeword ^ ((u64)ph.w[t] < A.bsc_thr ? 1 : 0);
                         pri4[t] = A.bsc_llr_d * (double)(1 - 2 * y);
+                        if constexpr (ALG == ALG_QMSA) pri4[t] = quantise_prior(pri4[t], fx_f64(A, FX_STEP), fx_f64(A, FX_VMAX));
                     }
                 }
 #pragma unroll
@@ -1090,6 +1125,11 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 4 : 2) void k_fused_f64(const Fu
             const double* pf = priors + fr * n;
 #pragma unroll
             for (int q = 0; q < VRW; ++q) prior[q] = vmap_at(q) >= 0 ? pf[vmap_at(q)] : (((dummy >> q) & 1u) ? __builtin_huge_val() : 0.0);
+        }
+        if constexpr (ALG == ALG_QMSA && !SIM) {  // the decoder's input stage: priors -> integer levels (see fused_bp_body); the +inf padding slot stays
+#pragma unroll
+            for (int q = 0; q < VRW; ++q)
+                if (!((dummy >> q) & 1u)) prior[q] = quantise_prior(prior[q], fx_f64(A, FX_STEP), fx_f64(A, FX_VMAX));
         }
 #pragma unroll
         for (int r = 0; r < CRW; ++r)
@@ -1206,6 +1246,10 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 4 : 2) void k_fused_f64(const Fu
                         if constexpr (ALG == ALG_NMSA) {  // corrected min-sum: the outputs of the minimum network (see fused_bp_body)
 #pragma unroll
                             for (int j = 0; j < DC; ++j) mag[j] = msa_correct(mag[j], A.corr_scale_d, A.corr_offset_d);
+                        }
+                        if constexpr (ALG == ALG_QMSA) {  // fixed-point min-sum: likewise; +inf (an empty minimum) saturates at V
+#pragma unroll
+                            for (int j = 0; j < DC; ++j) mag[j] = msa_fixed(mag[j], fx_f64(A, FX_SCALE), fx_f64(A, FX_OFFSET), fx_f64(A, FX_CAP));
                         }
 #pragma unroll
                         for (int j = 0; j < DC; ++j) {

@@ -160,6 +160,19 @@ __global__ __launch_bounds__(256) void k_biawgn_tile(SimSource s, int64_t B, int
     }
 }
 
+// Fixed-point min-sum (ALG_QMSA): the decoder's input stage, in place on the prior tiles of the decoder's workspace (never the caller's
+// buffer) -- level = clamp(rint(prior * 2^k), -V, +V), ldpc_cn.hpp quantise_prior.  One element per thread; `count` covers whole tiles
+// (lanes beyond the batch hold zeros or unread noise).  The fp16-storage mode passes its float2 pair-tiles as 2 * count floats.
+template <typename T>
+__global__ __launch_bounds__(256) void k_quantise_tile(T* __restrict__ prior_t, int64_t count, T step, T vmax) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < count) prior_t[i] = quantise_prior(prior_t[i], step, vmax);
+}
+template <typename T>
+void launch_quantise(const Decoder* d, T* prior_t, int64_t count, hipStream_t st) {
+    hipLaunchKernelGGL((k_quantise_tile<T>), dim3((unsigned)((count + 255) / 256)), dim3(256), 0, st, prior_t, count, (T)d->fx_step(), (T)d->fx_vmax());
+}
+
 __global__ void k_init_live(u64* __restrict__ live, int64_t B, int tiles) {
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= tiles) return;
@@ -259,7 +272,7 @@ __global__ __launch_bounds__(256) void k_cn(const int32_t* __restrict__ row_ptr,
 #pragma unroll
                     for (int j = 0; j < DCMAX; ++j) v[u][j] = v2c_of<T, ALG>(v[u][j], o[u][j]);
                 }
-                cn_rule<T, ALG, DCMAX>(v[u], deg[u], last_int_arg<T, ALG>::correction(freeze_arg));
+                cn_rule<T, ALG, DCMAX>(v[u], deg[u], last_int_arg<T, ALG>::correction(freeze_arg), last_int_arg<T, ALG>::cap(freeze_arg));
 #pragma unroll
                 for (int j = 0; j < DCMAX; ++j) {
                     if (j < deg[u]) msg_st<CN_NTS>(ct + (int64_t)(k0[u] + j) * 64, v[u][j]);
@@ -681,6 +694,7 @@ struct Geometry {
     int tiles, cn_chunks, cpw, vn_chunks, vpw, xcd_aware;
     int freeze = 0;  // lanes of departed frames do not compute or store (soft-output decodes)
     double corr_scale = 1.0, corr_offset = 0.0;  // corrected min-sum (Decoder::corr_scale / corr_offset at the time of the call)
+    double cap = 0.0;                            // fixed-point min-sum: corr_scale / corr_offset hold Decoder::fx_scale / fx_offset, cap its saturation (msa_fixed)
 };
 
 // The two passes.  GATHER (c2v_in / prior_out + srcmap): the sweep that carries a folded repack; those forms are built for the node
@@ -694,7 +708,7 @@ void dispatch_cn(const Code* c, T* c2v, const T* src, const u64* live, const Geo
         if constexpr (!GATHER || DCMAX <= 8)
             hipLaunchKernelGGL((k_cn<T, ALG, DCMAX, decltype(fdc)::value, UNR, GATHER>), dim3(task_blocks(g.tiles, g.cn_chunks, g.xcd_aware)), dim3(64, 4), 0, st,
                                c->d_row_ptr, c->d_edge_var, c2v, src, live, c->m, c->n, c->E, g.tiles, g.cn_chunks, g.cpw, first, g.xcd_aware,
-                               last_int_arg<T, ALG>::make(g.freeze, g.corr_scale, g.corr_offset), c2v_in, srcmap);
+                               last_int_arg<T, ALG>::make(g.freeze, g.corr_scale, g.corr_offset, g.cap), c2v_in, srcmap);
     });
 }
 template <typename T, int ALG, bool GATHER = false>
@@ -780,8 +794,9 @@ int run(Decoder* d, const DecodeCall& k, const SimSource* sim = nullptr) {
     Geometry g;
     g.tiles = tiles;
     g.freeze = k.soft != nullptr ? 1 : 0;
-    g.corr_scale = d->corr_scale;
-    g.corr_offset = d->corr_offset;
+    g.corr_scale = ALG == ALG_QMSA ? d->fx_scale : d->corr_scale;
+    g.corr_offset = ALG == ALG_QMSA ? d->fx_offset_eff() : d->corr_offset;
+    g.cap = d->fx_cap();
     // Nodes per wave.  The marginal lines a check pass gathers are re-used dv times; the fewer tiles are in flight at once, the
     // more of those re-reads hit on chip -- so a tile is cut into MANY short wave tasks (tile-major task order).  Measured on one
     // MI355X (sweep of 32 768 frames of the (3,6) n = 64 800 shape, profiles/r03_stream_chunking.txt): 64 checks per wave 20.9 ms,
@@ -813,6 +828,7 @@ int run(Decoder* d, const DecodeCall& k, const SimSource* sim = nullptr) {
     }
     if (!sim)
         hipLaunchKernelGGL((k_load_tile<T>), dim3((n + 63) / 64, tiles), dim3(256), 0, st, (const T*)k.priors, y0, B, n, prior, xbits);
+    if constexpr (ALG == ALG_QMSA) launch_quantise<T>(d, prior, (int64_t)tiles * n * 64, st);  // priors -> levels, in the workspace
     hipLaunchKernelGGL(k_init_live, dim3((tiles + 255) / 256), dim3(256), 0, st, live, B, tiles);
 
     const int cap = max_iter > 0 ? max_iter : 100000;  // max_iter <= 0 == unlimited upstream (src/bpa.py:28); bounded here
@@ -1018,6 +1034,7 @@ __global__ __launch_bounds__(256) void k_cn16(const int32_t* __restrict__ row_pt
                                               typename last_int_arg<float, ALG>::type cpw_arg) {
     const int cpw = last_int_arg<float, ALG>::value(cpw_arg);  // (corrected min-sum: scale and offset ride behind it, ldpc_cn.hpp)
     const Correction<float> corr = last_int_arg<float, ALG>::correction(cpw_arg);  // applied in fp32, before the message is rounded to half
+    const float cap = last_int_arg<float, ALG>::cap(cpw_arg);                      // (fixed-point min-sum: every message is an integer <= 2047, exact in half)
     const int lane = threadIdx.x;
     int P, chunk;
     if (!task_of(pairs, chunks, 0, &P, &chunk)) return;
@@ -1055,8 +1072,8 @@ __global__ __launch_bounds__(256) void k_cn16(const int32_t* __restrict__ row_pt
         }
 #pragma unroll
         for (int u = 0; u < UNR; ++u) {
-            cn_rule<float, ALG, DCMAX>(vx[u], deg[u], corr);
-            cn_rule<float, ALG, DCMAX>(vy[u], deg[u], corr);
+            cn_rule<float, ALG, DCMAX>(vx[u], deg[u], corr, cap);
+            cn_rule<float, ALG, DCMAX>(vy[u], deg[u], corr, cap);
 #pragma unroll
             for (int j = 0; j < DCMAX; ++j)
                 if (j < deg[u]) msg16_st<ALG>(ct + (int64_t)(k0[u] + j) * 64, vx[u][j], vy[u][j]);
@@ -1275,6 +1292,7 @@ int run16(Decoder* d, const DecodeCall& k, const SimSource* sim) {
     } else {
         hipLaunchKernelGGL(k_load_tile16, dim3((n + 63) / 64, pairs), dim3(256), 0, st, (const float*)k.priors, y0, B, n, prior, xbits);
     }
+    if constexpr (ALG == ALG_QMSA) launch_quantise<float>(d, reinterpret_cast<float*>(prior), (int64_t)pairs * n * 128, st);  // priors -> levels
     hipLaunchKernelGGL(k_init_live, dim3((tiles + 255) / 256), dim3(256), 0, st, live, B, tiles);
     int repacks = 0;
     const int cpw = 4, vpw = 16;
@@ -1324,7 +1342,8 @@ int run16(Decoder* d, const DecodeCall& k, const SimSource* sim) {
             constexpr int DCM = decltype(dcm)::value, FDC = decltype(fdc)::value, UNR = DCM <= 6 ? 2 : 1;
             const auto kern = it == 0 ? k_cn16<ALG, DCM, FDC, UNR, true> : k_cn16<ALG, DCM, FDC, UNR, false>;
             hipLaunchKernelGGL(kern, cgrid, blk, 0, st, c->d_row_ptr, c->d_edge_var, edge_vpos, msg, v2c, prior, live, m, n, E, pairs, tiles, cn_chunks,
-                               last_int_arg<float, ALG>::make(cpw, d->corr_scale, d->corr_offset));
+                               last_int_arg<float, ALG>::make(cpw, ALG == ALG_QMSA ? d->fx_scale : d->corr_scale,
+                                                              ALG == ALG_QMSA ? d->fx_offset_eff() : d->corr_offset, d->fx_cap()));
         });
         LDPC_TRY(prof.mark(1));
         var_class<false>(c, [&](auto dvm, auto fdv) {
@@ -1349,12 +1368,14 @@ bool batch_fits(int64_t B) {
 template <typename T>
 int run_alg(Decoder* d, const DecodeCall& k, const SimSource* sim) {
     if (d->alg == ALG_NMSA) return run<T, ALG_NMSA>(d, k, sim);
+    if (d->alg == ALG_QMSA) return run<T, ALG_QMSA>(d, k, sim);
     return d->alg == ALG_MSA ? run<T, ALG_MSA>(d, k, sim) : run<T, ALG_SPA>(d, k, sim);
 }
 
 // LLR decoders: the driver of the decoder's storage type; with `sim` the priors are drawn into the tiles instead of loaded
 int run_llr(Decoder* d, const DecodeCall& k, const SimSource* sim) {
     if (d->dtype == DT_F16 && d->alg == ALG_NMSA) return run16<ALG_NMSA>(d, k, sim);
+    if (d->dtype == DT_F16 && d->alg == ALG_QMSA) return run16<ALG_QMSA>(d, k, sim);
     if (d->dtype == DT_F16) return d->alg == ALG_MSA ? run16<ALG_MSA>(d, k, sim) : run16<ALG_SPA>(d, k, sim);  // priors are fp32
     return d->dtype == DT_F64 ? run_alg<double>(d, k, sim) : run_alg<float>(d, k, sim);
 }
