@@ -319,6 +319,50 @@ int ldpc_bec_ml_decode(ldpc_bec_ml_t h, const uint8_t* y_dev, int64_t B, uint64_
 int ldpc_bec_ml_simulate(ldpc_bec_ml_t h, double param, int codeword, uint64_t seed, uint64_t stream_id, uint64_t frame0, int64_t B,
                          int64_t* counters_dev, void* stream);
 
+/* ---- Ordered-statistics post-processing (BP+OSD) of the LLR decoders -------------------------------------------
+ * No upstream counterpart: it adds to BPA.decode (src/bpa.py:17-63), which returns a word that is no codeword when the sweeps run out.
+ * OSD re-decodes exactly those frames from BP's soft output.  Per frame, deterministic (no random draws), for post[n] (the LLRs that
+ * order the bits) and prior[n] (the channel LLRs that score candidates), both of one type T in {float, double}; order in {0, 1};
+ * depth >= 0:
+ *   1. Pass-through.  h_v = (post_v < 0).  If H h = 0 the frame is not touched: the word is h, pick = -1, cost = -1.0.
+ *   2. Order.  rho_v = |post_v| rounded to fp32 (nearest-even; NaN -> 0; magnitudes below 2^-126 are outside the contract).  The key of
+ *      variable v is (uint64(bits(rho_v)) << 32) | v; the keys are unique, the ascending sort is a total order: pi(p) = the variable at
+ *      sorted position p, least reliable first, ties broken by the variable index.
+ *   3. Eliminate.  H with its columns in the order pi is brought to reduced row echelon form over GF(2), columns left to right; the
+ *      pivot of a column is any unused row with a 1 there (the reduced form does not depend on that choice).  The positions with a
+ *      pivot number rank(H); the others, f_0 < f_1 < ..., are free.
+ *   4. Candidates.  Candidate 0 takes the free positions from h and each pivot position from its row (the XOR of the row's free bits):
+ *      the unique codeword that agrees with h on the most reliable information set.  order == 1: candidate t, 1 <= t <= min(depth, number
+ *      of free positions), is the same with free position f_(t-1) flipped.
+ *   5. Score and pick.  g_v = (prior_v < 0), w_v = (double)|prior_v| (NaN -> 0).  cost(x) = the fp64 sum, from +0.0, over p = 0 .. n-1 in
+ *      that order, of w_pi(p) wherever x_pi(p) != g_pi(p) (plain adds).  The smallest cost wins, on equal cost the smallest t.  Outputs:
+ *      the word, pick = t, cost.
+ * One wave per failed frame, the frame's whole system in the LDS of one CU: create fails with LDPC_E_ARG unless
+ *   4 * osd_lds_words(m, n) <= 163840  and  m <= 4096,   osd_lds_words = 2 NP + S * RP + 4 n + 5 S,
+ * NP = the power of two >= n (the sort keys, 64 bits each), S = ceil(n / 32), RP = 64 ceil(m / 64) (the matrix, S words per row), 4 n for
+ * pi, its inverse, the pivot row of every position and the list of free positions, 5 S for the bit masks in position order.  Handles are
+ * not thread-safe (one workspace). */
+typedef struct ldpc_osd_s* ldpc_osd_t;
+int ldpc_osd_create(ldpc_code_t code, ldpc_osd_t* out);
+int ldpc_osd_destroy(ldpc_osd_t h);
+/* Steps 1-5 for B frames.  dtype: LDPC_DTYPE_F32 / _F64 = the type of post_dev and prior_dev [B, n]; out_bits_dev [B, W] uint32 in the
+ * layout of ldpc_decode_bits; pick_dev [B] int32; cost_dev [B] double or NULL.  order outside {0, 1} or depth < 0: LDPC_E_ARG. */
+int ldpc_osd_solve(ldpc_osd_t h, int dtype, const void* post_dev, const void* prior_dev, int64_t B, int32_t order, int64_t depth,
+                   uint32_t* out_bits_dev, int32_t* pick_dev, double* cost_dev, void* stream);
+/* BPA.decode (src/bpa.py:17-63) by `dec`, then OSD of the frames it left without a codeword: ldpc_decode_soft in chunks of <= 2^17 frames
+ * (post = the marginals of the last sweep; a frame that left at the iteration-0 check of y0 never swept: post = its priors), solve,
+ * unpack.  `dec` is any fp32 or fp64 LDPC_ALG_MSA / SPA / NMSA / QMSA decoder of the same code (an fp16 or LDPC_ALG_BEC decoder:
+ * LDPC_E_UNSUPPORTED; a decoder of another code: LDPC_E_ARG); priors_dev / y0_dev / max_iter / flags as ldpc_decode.  xhat_dev [B, n] uint8,
+ * iters_dev [B] = BP's sweeps, pick_dev [B]. */
+int ldpc_osd_decode(ldpc_osd_t h, ldpc_decoder_t dec, const void* priors_dev, const uint8_t* y0_dev, int64_t B, int32_t max_iter,
+                    uint32_t flags, int32_t order, int64_t depth, uint8_t* xhat_dev, int32_t* iters_dev, int32_t* pick_dev, void* stream);
+/* ldpc_channel + ldpc_osd_decode + ldpc_count_errors_bits for frames [frame0, frame0+B) of the all-`codeword` word -- the body of
+ * `while wec < min_wec` (src/main.py:37-45) as ldpc_simulate is.  ITER_SUM and the histogram come from BP's iteration counts.  LDPC_CH_BIAWGN
+ * and LDPC_CH_BSC; codeword 0 or 1; 1 is refused (LDPC_E_ARG) when a check has odd degree, as in ldpc_bec_ml_simulate. */
+int ldpc_osd_simulate(ldpc_osd_t h, ldpc_decoder_t dec, int channel, double param, int codeword, uint64_t seed, uint64_t stream_id,
+                      uint64_t frame0, int64_t B, int32_t max_iter, uint32_t flags, int32_t order, int64_t depth, int32_t hist_bins,
+                      int64_t* counters_dev, void* stream);
+
 /* ---- ADMM LP decoding ------------------------------------------------------------------------------------------
  * Replaces admm.ADMM (src/admm.py:9-77) together with its native projection (src/parity_polytope/projection.cpp:30-275, bound
  * upstream through ctypes in exact.py:12-53).  Check degrees up to 16. */

@@ -603,6 +603,97 @@ class BecMlHandle:
             _lib.check(lib.ldpc_count_errors_words(xhat.data_ptr(), sent.data_ptr(), None, nb, n, 0, counters.data_ptr(), st))
 
 
+class OsdHandle:
+    """Ordered-statistics post-processing of an LLR decoder (``ldpc_osd_*``): the frames BP leaves without a codeword are decoded again
+    from its soft output, one wave per frame.  ``bp`` is the ``DecoderHandle`` (fp32 / fp64 MSA, SPA, NMSA or QMSA, same code) that runs in
+    front; ``order`` in {0, 1} and ``depth`` >= 0 are read at every call."""
+
+    def __init__(self, bp, order=0, depth=64):
+        lib = _lib.load()
+        self.bp, self.code, self.code_handle = bp, bp.code, bp.code_handle
+        self.device, self.precision = bp.code_handle.device, bp.precision
+        self.order, self.depth = int(order), int(depth)
+        h = ctypes.c_void_p()
+        _lib.check(lib.ldpc_osd_create(self.code_handle.h, ctypes.byref(h)))
+        self.h = h
+
+    def __del__(self):
+        try:
+            if getattr(self, "h", None):
+                _lib.load().ldpc_osd_destroy(self.h)
+                self.h = None
+        except Exception:
+            pass
+
+    def solve(self, post, prior, order=None, depth=None, want_cost=True):
+        """``ldpc_osd_solve``: post / prior contiguous CUDA tensors [B, n] of one dtype (float32 or float64) -> (words int32 [B, ceil(n/32)]
+        in the layout of ``decode_device_bits``, pick int32 [B], cost float64 [B] or None)."""
+        import torch
+
+        n = self.code.n
+        for t in (post, prior):
+            if not t.is_cuda or not t.is_contiguous() or t.dim() != 2 or t.shape[1] != n or t.dtype not in (torch.float32, torch.float64):
+                raise ValueError("post and prior must be contiguous CUDA float32 / float64 tensors [B, %d]" % n)
+        if post.dtype != prior.dtype or post.shape != prior.shape:
+            raise ValueError("post and prior must have one dtype and one shape")
+        B = post.shape[0]
+        bits = torch.empty((B, (n + 31) // 32), dtype=torch.int32, device=post.device)
+        pick = torch.empty((B,), dtype=torch.int32, device=post.device)
+        cost = torch.empty((B,), dtype=torch.float64, device=post.device) if want_cost else None
+        if B:
+            st = torch.cuda.current_stream(post.device).cuda_stream
+            _lib.check(_lib.load().ldpc_osd_solve(self.h, _lib.DTYPE["f64" if post.dtype == torch.float64 else "f32"], post.data_ptr(),
+                                                  prior.data_ptr(), B, int(self.order if order is None else order),
+                                                  int(self.depth if depth is None else depth), bits.data_ptr(), pick.data_ptr(),
+                                                  None if cost is None else cost.data_ptr(), st))
+        return bits, pick, cost
+
+    def decode_device(self, priors, y0, max_iter, flags=0, order=None, depth=None, bp=None):
+        """``ldpc_osd_decode``: BP by ``bp`` (default: the handle's own decoder), then OSD -> (xhat uint8 [B, n], BP's iters int32 [B],
+        pick int32 [B]: -1 where BP's word was a codeword and is returned as it is)."""
+        import torch
+
+        n, B = self.code.n, priors.shape[0]
+        bp = self.bp if bp is None else bp
+        xhat = torch.empty((B, n), dtype=torch.uint8, device=priors.device)
+        iters = torch.empty((B,), dtype=torch.int32, device=priors.device)
+        pick = torch.empty((B,), dtype=torch.int32, device=priors.device)
+        if not priors.is_cuda or not priors.is_contiguous() or priors.dim() != 2 or priors.shape[1] != n:
+            raise ValueError("priors must be a contiguous CUDA tensor [B, %d]" % n)
+        if y0 is not None and (y0.dtype != torch.uint8 or not y0.is_contiguous() or not y0.is_cuda):
+            raise ValueError("y0 must be a contiguous CUDA uint8 tensor")
+        if B:
+            st = torch.cuda.current_stream(priors.device).cuda_stream
+            _lib.check(_lib.load().ldpc_osd_decode(self.h, bp.h, priors.data_ptr(), None if y0 is None else y0.data_ptr(), B, int(max_iter), flags,
+                                                   int(self.order if order is None else order), int(self.depth if depth is None else depth),
+                                                   xhat.data_ptr(), iters.data_ptr(), pick.data_ptr(), st))
+        return xhat, iters, pick
+
+    def simulate(self, channel, param, codeword, seed, stream_id, frame0, B, max_iter, counters, flags=0, hist_bins=0):
+        """Same call shape as DecoderHandle.simulate: channel -> LLR -> BP -> OSD -> count on the device; ITER_SUM and the histogram are
+        BP's.  ``codeword == -1``: random codewords from the systematic encoder (``Code.encoder()``) through ``ldpc_channel_sent``."""
+        import torch
+
+        if channel not in ("biawgn", "bsc"):
+            raise ValueError("ordered-statistics post-processing works on the LLR channels (biawgn, bsc); the bec has ML")
+        if B <= 0:
+            return
+        lib = _lib.load()
+        st = torch.cuda.current_stream(counters.device).cuda_stream
+        if int(codeword) != -1:
+            _lib.check(lib.ldpc_osd_simulate(self.h, self.bp.h, _lib.CHANNEL[channel], float(param), int(codeword), int(seed), int(stream_id),
+                                             int(frame0), int(B), int(max_iter), flags, self.order, self.depth, hist_bins, counters.data_ptr(), st))
+            return
+        n, enc = self.code.n, self.code.encoder().handle(self.device)
+        step = 1 << 17
+        for b0 in range(0, int(B), step):
+            nb = min(step, int(B) - b0)
+            sent = enc.encode_random(seed, stream_id, int(frame0) + b0, nb)
+            pri, y = self.bp.channel_sent_device(channel, param, sent, seed, stream_id, int(frame0) + b0)
+            xhat, iters, _ = self.decode_device(pri, y, max_iter, flags)
+            _lib.check(lib.ldpc_count_errors_words(xhat.data_ptr(), sent.data_ptr(), iters.data_ptr(), nb, n, hist_bins, counters.data_ptr(), st))
+
+
 class AdmmHandle:
     """ADMM LP decoder workspace on one GPU (``ldpc_admm_*``)."""
 

@@ -94,6 +94,12 @@ SIGNATURES = {
     "ldpc_bec_ml_solve": (_c.c_int, [_P, _P, _P, _c.c_int64, _c.c_uint64, _c.c_uint64, _c.c_uint64, _P, _P, _P]),
     "ldpc_bec_ml_decode": (_c.c_int, [_P, _P, _c.c_int64, _c.c_uint64, _c.c_uint64, _c.c_uint64, _P, _P, _P]),
     "ldpc_bec_ml_simulate": (_c.c_int, [_P, _c.c_double, _c.c_int, _c.c_uint64, _c.c_uint64, _c.c_uint64, _c.c_int64, _P, _P]),
+    "ldpc_osd_create": (_c.c_int, [_P, _c.POINTER(_P)]),
+    "ldpc_osd_destroy": (_c.c_int, [_P]),
+    "ldpc_osd_solve": (_c.c_int, [_P, _c.c_int, _P, _P, _c.c_int64, _c.c_int32, _c.c_int64, _P, _P, _P, _P]),
+    "ldpc_osd_decode": (_c.c_int, [_P, _P, _P, _P, _c.c_int64, _c.c_int32, _c.c_uint32, _c.c_int32, _c.c_int64, _P, _P, _P, _P]),
+    "ldpc_osd_simulate": (_c.c_int, [_P, _P, _c.c_int, _c.c_double, _c.c_int, _c.c_uint64, _c.c_uint64, _c.c_uint64, _c.c_int64, _c.c_int32,
+                                     _c.c_uint32, _c.c_int32, _c.c_int64, _c.c_int32, _P, _P]),
     "ldpc_admm_create": (_c.c_int, [_P, _c.POINTER(_P)]),
     "ldpc_admm_destroy": (_c.c_int, [_P]),
     "ldpc_admm_last_repacks": (_c.c_int, [_P, _c.POINTER(_c.c_int)]),

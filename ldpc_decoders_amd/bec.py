@@ -69,6 +69,15 @@ class QMSA:
                                   "to quantise; use SPA / MSA there")
 
 
+class OSD:
+    """Ordered-statistics post-processing orders soft values; over the erasure channel ``ML`` (elimination of the erased bits) is exact."""
+    id_keys = ["max_iter", "msa_scale", "msa_offset", "osd_order", "osd_depth"]
+
+    def __init__(self, *a, **k):
+        raise NotImplementedError("decoder OSD (BP + ordered-statistics post-processing) does not exist over the bec: use ML there, the "
+                                  "elimination decoder is exact")
+
+
 class ADMM:  # src/bec.py:38-45,58-62: LLR wrapper with +-1e8 for the known symbols, 0 for an erasure
     id_keys = admm.ADMM.id_keys
     channel = "bec"

@@ -61,6 +61,13 @@ class QMSA(LLR):  # fixed-point min-sum (q-bit saturating messages): no upstream
         super().__init__(snr_in_db, bpa.QMSA(_code, **kwargs))
 
 
+class OSD(LLR):  # BP + ordered-statistics post-processing: no upstream counterpart, wrapped like NMSA
+    id_keys = bpa.OSD.id_keys
+
+    def __init__(self, snr_in_db, _code, **kwargs):
+        super().__init__(snr_in_db, bpa.OSD(_code, **kwargs))
+
+
 class ADMM(LLR):  # src/biawgn.py:52-56
     id_keys = admm.ADMM.id_keys
 

@@ -12,7 +12,7 @@ Extra constructor keywords (all optional):
 """
 import numpy as np
 
-from ._device import DecoderHandle, as_code, check_correction, check_fixed_point
+from ._device import DecoderHandle, OsdHandle, as_code, check_correction, check_fixed_point
 
 
 class BPA:
@@ -118,3 +118,90 @@ class QMSA(BPA):
         self.msa_bits, self.msa_frac_bits, self.msa_scale, self.msa_offset = check_fixed_point(*values)
         super().__init__(parity_mtx, **kwargs)
         self.handle.set_fixed_point(self.msa_bits, self.msa_frac_bits, self.msa_scale, self.msa_offset)
+
+
+OSD_LDS_BYTES = 160 * 1024  # one CU's LDS: a frame's sort keys, matrix and permutations must fit
+OSD_MAX_ROWS = 4096
+
+
+def osd_lds_bytes(m, n):
+    """LDS one frame of the ordered-statistics post-processor takes: the rule of ldpc_osd_create (osd_lds_words, csrc/ldpc_osd.hpp)."""
+    NP, S, RP = 1, (n + 31) // 32, -(-m // 64) * 64
+    while NP < n:
+        NP <<= 1
+    return 4 * (2 * NP + S * RP + 4 * n + 5 * S)
+
+
+def check_osd_size(code):
+    """ValueError unless a frame of ``code`` fits one CU's LDS (checked before the library is loaded)."""
+    if osd_lds_bytes(code.m, code.n) > OSD_LDS_BYTES or -(-code.m // 64) * 64 > OSD_MAX_ROWS:
+        raise ValueError("ordered-statistics post-processing: a frame of a %d x %d code needs %d bytes of LDS (sort keys, matrix, "
+                         "permutations), above the limit of one CU's 160 KiB (at most %d checks)"
+                         % (code.m, code.n, osd_lds_bytes(code.m, code.n), OSD_MAX_ROWS))
+
+
+class OSD:
+    """Belief propagation followed by ordered-statistics decoding of the frames it leaves without a codeword (no upstream counterpart; it
+    adds to ``BPA.decode``, src/bpa.py:17-63).  ``osd_bp`` in {MSA, SPA, NMSA, QMSA} names the decoder in front (its own keywords apply),
+    ``osd_order`` in {0, 1}, ``osd_depth`` >= 0 the number of single flips order 1 tries.  The output is always a codeword.  ``decode`` /
+    ``decode_batch`` as ``BPA``; ``last_pick`` holds per frame -1 (BP's word, untouched) or the winning candidate.  The contract:
+    include/ldpc_hip.h (ldpc_osd_*), DESIGN.md section 17."""
+    id_keys = ["max_iter", "msa_scale", "msa_offset", "osd_order", "osd_depth"]
+
+    def __init__(self, parity_mtx, **kwargs):
+        self.max_iter = kwargs["max_iter"]
+        self.code = as_code(parity_mtx)
+        check_osd_size(self.code)
+        order, depth = kwargs.get("osd_order"), kwargs.get("osd_depth")
+        self.osd_order, self.osd_depth = 0 if order is None else int(order), 64 if depth is None else int(depth)
+        if self.osd_order not in (0, 1) or self.osd_depth < 0:
+            raise ValueError("osd_order must be 0 or 1 and osd_depth >= 0 (got %r, %r)" % (order, depth))
+        self.osd_bp = kwargs.get("osd_bp") or "NMSA"
+        front = {"MSA": MSA, "SPA": SPA, "NMSA": NMSA, "QMSA": QMSA}.get(self.osd_bp)
+        if front is None:
+            raise ValueError("osd_bp must be one of MSA, SPA, NMSA, QMSA (got %r)" % (self.osd_bp,))
+        self.precision = kwargs.get("precision") or "f64"
+        if self.precision not in ("f32", "f64"):
+            raise ValueError("ordered-statistics post-processing needs the soft output of an f32 or f64 decoder (got precision %r)" % self.precision)
+        self.bp = front(self.code, **kwargs)
+        self.handle = OsdHandle(self.bp.handle, self.osd_order, self.osd_depth)
+        self.last_iters = self.last_pick = None
+
+    @property
+    def parity_mtx(self):
+        return self.code.parity_mtx
+
+    def _host(self, y0, priors):
+        import torch
+
+        dev = "cuda:%d" % self.handle.device
+        pri = torch.from_numpy(np.ascontiguousarray(np.atleast_2d(priors), dtype=self.bp.handle.np_dtype)).to(dev)
+        if pri.shape[1] != self.code.n:
+            raise ValueError("frames must have n=%d entries" % self.code.n)
+        yd = None if y0 is None else torch.from_numpy(np.ascontiguousarray(np.atleast_2d(y0), dtype=np.uint8)).to(dev)
+        xhat, iters, pick = self.handle.decode_device(pri, yd, self.max_iter)
+        return xhat.cpu().numpy(), iters.cpu().numpy(), pick.cpu().numpy()
+
+    def decode(self, y, priors):
+        y = np.asarray(y)
+        y0, host_ok = self.bp._iter0_word(y)
+        if host_ok is not None and host_ok[0]:  # passes the iteration-0 test of src/bpa.py:28-29: the received word is a codeword
+            self.last_iters, self.last_pick = np.zeros(1, dtype=np.int32), np.full(1, -1, dtype=np.int32)
+            return y
+        xhat, self.last_iters, self.last_pick = self._host(y0, np.asarray(priors))
+        if self.last_iters[0] == 0 and y0 is not None:
+            return y  # left at the iteration-0 check: upstream returns the received object itself
+        return xhat[0].astype(np.int64)
+
+    def decode_batch(self, y, priors):
+        """[B,n] frames -> (x_hat uint8 [B,n], BP's iters int32 [B]).  numpy in -> numpy out; CUDA tensors in -> CUDA tensors out."""
+        if hasattr(priors, "is_cuda"):
+            xhat, self.last_iters, self.last_pick = self.handle.decode_device(priors, y, self.max_iter)
+            return xhat, self.last_iters
+        y0 = None
+        if y is not None:
+            y0, host_ok = self.bp._iter0_word(y)
+            if host_ok is not None and host_ok.any():
+                raise ValueError("integer-valued non-binary received words are only supported one frame at a time")
+        xhat, self.last_iters, self.last_pick = self._host(y0, priors)
+        return xhat, self.last_iters

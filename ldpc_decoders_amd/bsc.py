@@ -63,6 +63,13 @@ class QMSA(LLR):  # fixed-point min-sum (q-bit saturating messages): no upstream
         super().__init__(p, bpa.QMSA(_code, **kwargs))
 
 
+class OSD(LLR):  # BP + ordered-statistics post-processing: no upstream counterpart, wrapped like NMSA
+    id_keys = bpa.OSD.id_keys
+
+    def __init__(self, p, _code, **kwargs):
+        super().__init__(p, bpa.OSD(_code, **kwargs))
+
+
 class ADMM(LLR):  # src/bsc.py:49-53
     id_keys = admm.ADMM.id_keys
 

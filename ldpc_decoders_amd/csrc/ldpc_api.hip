@@ -13,6 +13,7 @@
 #include "ldpc_common.hpp"
 #include "ldpc_bec_ml.hpp"
 #include "ldpc_encode.hpp"
+#include "ldpc_osd.hpp"
 
 namespace ldpc {
 
@@ -1123,6 +1124,67 @@ int ldpc_bec_ml_simulate(ldpc_bec_ml_t h, double param, int codeword, uint64_t s
             return LDPC_E_ARG;
         }
         return bec_ml_simulate((BecMl*)h, param, codeword, seed, stream_id, frame0, B, counters_dev, (hipStream_t)stream);
+    });
+}
+
+// ---- ordered-statistics post-processing of the LLR decoders (ldpc_osd.hip) ----
+// adds to BPA.decode (src/bpa.py:17-63; no upstream counterpart)
+int ldpc_osd_create(ldpc_code_t code, ldpc_osd_t* out) {
+    return guarded("ldpc_osd_create", [&]() -> int {
+        if (!code || !out) {
+            set_error("ldpc_osd_create: bad arguments");
+            return LDPC_E_ARG;
+        }
+        Osd* h = nullptr;
+        LDPC_TRY(osd_create((Code*)code, &h));
+        *out = (ldpc_osd_t)h;
+        return LDPC_OK;
+    });
+}
+
+// adds to BPA.decode (src/bpa.py:17-63; no upstream counterpart)
+int ldpc_osd_destroy(ldpc_osd_t h) {
+    return guarded("ldpc_osd_destroy", [&]() -> int {
+        osd_destroy((Osd*)h);
+        return LDPC_OK;
+    });
+}
+
+// adds to BPA.decode (src/bpa.py:17-63; no upstream counterpart): the post-processing of given soft values
+int ldpc_osd_solve(ldpc_osd_t h, int dtype, const void* post_dev, const void* prior_dev, int64_t B, int32_t order, int64_t depth,
+                   uint32_t* out_bits_dev, int32_t* pick_dev, double* cost_dev, void* stream) {
+    return guarded("ldpc_osd_solve", [&]() -> int {
+        if (!h || !post_dev || !prior_dev || !out_bits_dev || !pick_dev || B < 0) {
+            set_error("ldpc_osd_solve: bad arguments");
+            return LDPC_E_ARG;
+        }
+        return osd_solve((Osd*)h, dtype, post_dev, prior_dev, B, order, depth, out_bits_dev, pick_dev, cost_dev, (hipStream_t)stream);
+    });
+}
+
+// adds to BPA.decode (src/bpa.py:17-63; no upstream counterpart): BP, then the frames it left without a codeword
+int ldpc_osd_decode(ldpc_osd_t h, ldpc_decoder_t dec, const void* priors_dev, const uint8_t* y0_dev, int64_t B, int32_t max_iter, uint32_t flags,
+                    int32_t order, int64_t depth, uint8_t* xhat_dev, int32_t* iters_dev, int32_t* pick_dev, void* stream) {
+    return guarded("ldpc_osd_decode", [&]() -> int {
+        if (!h || !dec || !priors_dev || !xhat_dev || !iters_dev || !pick_dev || B < 0) {
+            set_error("ldpc_osd_decode: bad arguments");
+            return LDPC_E_ARG;
+        }
+        return osd_decode((Osd*)h, dec, priors_dev, y0_dev, B, max_iter, flags, order, depth, xhat_dev, iters_dev, pick_dev, (hipStream_t)stream);
+    });
+}
+
+// adds to BPA.decode (src/bpa.py:17-63; no upstream counterpart) inside the loop of main.test (src/main.py:37-45)
+int ldpc_osd_simulate(ldpc_osd_t h, ldpc_decoder_t dec, int channel, double param, int codeword, uint64_t seed, uint64_t stream_id, uint64_t frame0,
+                      int64_t B, int32_t max_iter, uint32_t flags, int32_t order, int64_t depth, int32_t hist_bins, int64_t* counters_dev,
+                      void* stream) {
+    return guarded("ldpc_osd_simulate", [&]() -> int {
+        if (!h || !dec || !counters_dev || B < 0 || hist_bins < 0) {
+            set_error("ldpc_osd_simulate: bad arguments");
+            return LDPC_E_ARG;
+        }
+        return osd_simulate((Osd*)h, dec, channel, param, codeword, seed, stream_id, frame0, B, max_iter, flags, order, depth, hist_bins,
+                            counters_dev, (hipStream_t)stream);
     });
 }
 
