@@ -58,6 +58,33 @@ enum { LDPC_ALG_NMSA = 3 };
  * Same kernel shapes and layout plans as LDPC_ALG_MSA; accepted wherever LDPC_ALG_MSA is, except LDPC_FLAG_PRIOR_GRID (LDPC_E_UNSUPPORTED: it
  * would add nothing). */
 enum { LDPC_ALG_QMSA = 4 };
+/* Layered (serial-C) corrected min-sum.  No upstream counterpart: BPA.decode (src/bpa.py:17-63) runs the flooding schedule -- every check
+ * of a sweep sees the marginals the PREVIOUS sweep left.  Here the checks are processed in groups (layers), and every layer already sees
+ * the marginals the layer before it left behind; a frame converges in roughly half the sweeps.  Per frame, in the decoder's arithmetic
+ * T (fp64 or fp32):
+ *   1. Layers.  layer_of_check[m] holds non-negative ints; two checks of one layer share no variable.  Default (greedy, on the host at
+ *      create): for c = 0 .. m-1 in order, layer(c) is the smallest l >= 0 such that no check c' < c with layer(c') = l shares a variable
+ *      with c.  Processing order: ascending (layer, check index); the checks of a layer are independent, so the result equals processing
+ *      the checks one by one in that order.  ldpc_decoder_set_layers / _get_layers.
+ *   2. Init.  marg_v = prior_v, every c2v = +0.  x_hat = y0 if given (the iteration-0 rule of src/bpa.py:20,29), else undefined until the
+ *      first sweep.  Exits exactly as BPA.decode: before each sweep, stop if sweeps >= max_iter (max_iter <= 0: unbounded, capped at
+ *      100000), or if H x_hat = 0 -- checked from sweep 1 on, at sweep 0 only when y0 is given.  iters = sweeps executed.
+ *   3. One sweep.  For every check c in processing order, with its edges j = 0 .. dc-1 in H's row-major order:
+ *          v_j   = marg[var_j] - c2v_j                              (one subtraction)
+ *          s_j   = product of the signs of the other v_i, sgn(x) = -1 iff x < 0 (+-0 counts as +);  m_j = min_{i != j} |v_i|
+ *          c2v_j = s_j * max( fl( fl(scale * m_j) - offset ), 0 )   (the rule of LDPC_ALG_NMSA: two roundings, never an FMA)
+ *          marg[var_j] = v_j + c2v_j                                (one addition)
+ *      After the last layer: x_hat_v = (marg_v < 0).
+ *   4. Outputs.  A variable of degree 0 keeps marg = prior.  A frame that has left keeps its word and, with ldpc_decode_soft, the
+ *      marginals of its last executed sweep (0 where it never swept).
+ *   5. Correction.  scale and offset through ldpc_decoder_set_correction / _get_correction; after create (1, 0); ranges as LDPC_ALG_NMSA.
+ *   6. Refusals.  LDPC_E_UNSUPPORTED: LDPC_BACKEND_FUSED, LDPC_DTYPE_F16, LDPC_FLAG_PRIOR_GRID, and a code with a check of degree < 2
+ *      (its message is +inf: inf - inf at the second sweep).  LDPC_BACKEND_AUTO resolves to the streaming kernels;
+ *      ldpc_decoder_kernel_name gives "", ldpc_decoder_fused_info reports 0 wavefronts.
+ * Every value has one defined operation order: fp64 and fp32 results (decisions, iteration counts, soft outputs) are those of a
+ * restatement in IEEE arithmetic, bit for bit, whatever the tiling, batch size, poll cadence or frame repacks.  Accepted by every entry
+ * point that accepts LDPC_ALG_NMSA, with its shapes and flags. */
+enum { LDPC_ALG_LMSA = 5 };
 enum { LDPC_DTYPE_F32 = 0, LDPC_DTYPE_F64 = 1,                       /* message arithmetic                             */
        LDPC_DTYPE_F16 = 2 };  /* fp16 STORAGE of the check messages on the streaming kernels, fp32 arithmetic, fp32 priors / channel output:
                                * a throughput mode for codes whose state lives in HBM (the E-sized traffic halves); held to a
@@ -154,7 +181,7 @@ int ldpc_plan_layout(int32_t m, int32_t n, int64_t E, const int32_t* edge_chk, c
  * (profiles/roofline_counters.json).  Empty string: the decoder runs on the streaming kernels.  No upstream counterpart. */
 int ldpc_decoder_kernel_name(ldpc_decoder_t dec, int simulate, char* buf, int64_t len);
 
-/* Scale and offset of a corrected min-sum decoder (LDPC_ALG_NMSA).  No upstream counterpart: the rule they modify is src/bpa.py:86-102
+/* Scale and offset of a corrected min-sum decoder (LDPC_ALG_NMSA, LDPC_ALG_LMSA).  No upstream counterpart: the rule they modify is src/bpa.py:86-102
  * (see LDPC_ALG_NMSA above).  0 < scale <= 1, offset >= 0, both finite; LDPC_E_ARG otherwise and for a decoder of another algorithm.
  * After ldpc_decoder_create: 1, 0.  Decoder state, read when a call is enqueued: a change takes effect from the next call. */
 int ldpc_decoder_set_correction(ldpc_decoder_t dec, double scale, double offset);
@@ -167,11 +194,21 @@ int ldpc_decoder_get_correction(ldpc_decoder_t dec, double* scale, double* offse
 int ldpc_decoder_set_fixed_point(ldpc_decoder_t dec, int bits, int frac_bits, double scale, int offset);
 /* The values in force (LDPC_E_ARG for a decoder of another algorithm).  No upstream counterpart (src/bpa.py:86-102). */
 int ldpc_decoder_get_fixed_point(ldpc_decoder_t dec, int* bits, int* frac_bits, double* scale, int* offset);
+/* Layering of a layered min-sum decoder (LDPC_ALG_LMSA, see there; no upstream counterpart).  layer_of_check_host[m]: the layer of every
+ * check; NULL restores the greedy layering of ldpc_decoder_create.  LDPC_E_ARG for a decoder of another algorithm, m != the code's number
+ * of checks, a negative entry, or two checks of one layer that share a variable; a refused call leaves the previous layering in force
+ * and the decoder usable.  Decoder state: in force from the next call.  The call waits for the whole device (hipDeviceSynchronize: a
+ * decode of this decoder still in flight on any stream reads the old list), so it must not be made while a stream is being captured. */
+int ldpc_decoder_set_layers(ldpc_decoder_t dec, const int32_t* layer_of_check_host, int32_t m);
+/* The layering in force: *nlayers = number of distinct layers; layer_of_check_host_or_NULL[m], if given, receives the layer of every
+ * check.  LDPC_E_ARG for a decoder of another algorithm.  No upstream counterpart. */
+int ldpc_decoder_get_layers(ldpc_decoder_t dec, int32_t* nlayers, int32_t* layer_of_check_host_or_NULL);
 
 /* Per-kernel timing for roofline reports: when enabled, decode calls bracket their dominant kernels with HIP events
  * recorded ON THE DECODE STREAM and accumulate elapsed milliseconds / launch counts per kernel class:
  * [0] streaming check pass, [1] streaming variable pass, [2] fused decode kernel, [3] a whole streaming decode, first to last
  * enqueued kernel (the two passes + tile load, syndrome, repack and unpack kernels: [3] - [0] - [1] is what the side kernels cost).
+ * LDPC_ALG_LMSA: [0] the layer passes of a sweep (one launch per layer), [1] its decision pass, [3] the whole decode.
  * Enabling it makes every decode call end with a stream synchronise. */
 int ldpc_decoder_profile(ldpc_decoder_t dec, int enable);
 int ldpc_decoder_profile_read(ldpc_decoder_t dec, double* ms4, int64_t* launches4, int reset);
@@ -351,7 +388,7 @@ int ldpc_osd_solve(ldpc_osd_t h, int dtype, const void* post_dev, const void* pr
                    uint32_t* out_bits_dev, int32_t* pick_dev, double* cost_dev, void* stream);
 /* BPA.decode (src/bpa.py:17-63) by `dec`, then OSD of the frames it left without a codeword: ldpc_decode_soft in chunks of <= 2^17 frames
  * (post = the marginals of the last sweep; a frame that left at the iteration-0 check of y0 never swept: post = its priors), solve,
- * unpack.  `dec` is any fp32 or fp64 LDPC_ALG_MSA / SPA / NMSA / QMSA decoder of the same code (an fp16 or LDPC_ALG_BEC decoder:
+ * unpack.  `dec` is any fp32 or fp64 LDPC_ALG_MSA / SPA / NMSA / QMSA / LMSA decoder of the same code (an fp16 or LDPC_ALG_BEC decoder:
  * LDPC_E_UNSUPPORTED; a decoder of another code: LDPC_E_ARG); priors_dev / y0_dev / max_iter / flags as ldpc_decode.  xhat_dev [B, n] uint8,
  * iters_dev [B] = BP's sweeps, pick_dev [B]. */
 int ldpc_osd_decode(ldpc_osd_t h, ldpc_decoder_t dec, const void* priors_dev, const uint8_t* y0_dev, int64_t B, int32_t max_iter,

@@ -57,6 +57,19 @@ def check_fixed_point(bits, frac_bits, scale, offset):
     return int(bits), int(frac_bits), scale, int(off)
 
 
+def check_layers(code, layers):
+    """What ``ldpc_decoder_set_layers`` accepts -- one non-negative integer per check, no two checks of a layer on one variable -- checked
+    before any device call.  -> the layering as an int64 array."""
+    lay = np.asarray(layers)
+    if lay.ndim != 1 or lay.size != code.m or lay.dtype.kind not in "iu" or (lay < 0).any() or (lay >= 2 ** 31).any():
+        raise ValueError("a layering is one non-negative integer per check (%d checks)" % code.m)
+    lay = lay.astype(np.int64)
+    key = np.asarray(code.edge_var, dtype=np.int64) * (int(lay.max()) + 1) + lay[np.asarray(code.edge_chk)]
+    if np.unique(key).size != key.size:
+        raise ValueError("two checks of one layer share a variable")
+    return lay
+
+
 class CodeHandle:
     def __init__(self, code, device):
         lib = _lib.load()
@@ -125,6 +138,21 @@ class DecoderHandle:
         b, k, o, s = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0), ctypes.c_double(0)
         _lib.check(_lib.load().ldpc_decoder_get_fixed_point(self.h, ctypes.byref(b), ctypes.byref(k), ctypes.byref(s), ctypes.byref(o)))
         return b.value, k.value, s.value, o.value
+
+    # ---- layered min-sum (alg="LMSA"): the layer of every check; decoder state, in force from the next call
+    def set_layers(self, layers=None):
+        """``layers``: one non-negative int per check (two checks of one layer share no variable), or None for the greedy layering."""
+        if layers is None:
+            _lib.check(_lib.load().ldpc_decoder_set_layers(self.h, None, 0))
+            return
+        lay = np.ascontiguousarray(check_layers(self.code, layers), dtype=np.int32)
+        _lib.check(_lib.load().ldpc_decoder_set_layers(self.h, lay.ctypes.data, lay.size))
+
+    def layers(self):
+        """-> (number of layers, layer of every check as int32 [m])"""
+        nl, lay = ctypes.c_int32(0), np.empty(self.code.m, dtype=np.int32)
+        _lib.check(_lib.load().ldpc_decoder_get_layers(self.h, ctypes.byref(nl), lay.ctypes.data))
+        return nl.value, lay
 
     # ---- host (numpy) buffers
     def decode_host(self, priors, y0, max_iter, flags=0):

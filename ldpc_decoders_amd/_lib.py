@@ -11,7 +11,8 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("LDPC_LIB_PATH") or os.path.join(_HERE, "csrc", "libldpc_hip.so")  # override: A/B builds of the same ABI
 
 ALG = {"MSA": 0, "SPA": 1, "BEC": 2, "NMSA": 3,  # NMSA: corrected (normalised / offset) min-sum, LDPC_ALG_NMSA
-       "QMSA": 4}                                # QMSA: fixed-point min-sum (q-bit saturating messages), LDPC_ALG_QMSA
+       "QMSA": 4,                                # QMSA: fixed-point min-sum (q-bit saturating messages), LDPC_ALG_QMSA
+       "LMSA": 5}                                # LMSA: layered corrected min-sum on the streaming kernels, LDPC_ALG_LMSA
 DTYPE = {"f32": 0, "f64": 1, "f16": 2}  # f16: fp16 storage of the streaming messages, fp32 arithmetic / priors (decoders only)
 IO_DTYPE = {"f32": 0, "f64": 1, "f16": 0}  # what the channel kernels write / the decoders read for each decoder precision
 BACKEND = {"auto": 0, "stream": 1, "fused": 2}
@@ -63,6 +64,8 @@ SIGNATURES = {
     "ldpc_decoder_get_correction": (_c.c_int, [_P, _c.POINTER(_c.c_double), _c.POINTER(_c.c_double)]),
     "ldpc_decoder_set_fixed_point": (_c.c_int, [_P, _c.c_int, _c.c_int, _c.c_double, _c.c_int]),
     "ldpc_decoder_get_fixed_point": (_c.c_int, [_P, _c.POINTER(_c.c_int), _c.POINTER(_c.c_int), _c.POINTER(_c.c_double), _c.POINTER(_c.c_int)]),
+    "ldpc_decoder_set_layers": (_c.c_int, [_P, _P, _c.c_int32]),
+    "ldpc_decoder_get_layers": (_c.c_int, [_P, _c.POINTER(_c.c_int32), _P]),
     "ldpc_decode": (_c.c_int, [_P, _P, _P, _c.c_int64, _c.c_int32, _c.c_uint32, _P, _P, _P]),
     "ldpc_decode_bits": (_c.c_int, [_P, _P, _P, _c.c_int64, _c.c_int32, _c.c_uint32, _P, _P, _P, _P]),
     "ldpc_decode_host_bits": (_c.c_int, [_P, _P, _P, _c.c_int64, _c.c_int32, _c.c_uint32, _P, _P, _P]),

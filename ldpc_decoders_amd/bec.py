@@ -60,6 +60,15 @@ class NMSA:
                                   "to correct; use SPA / MSA there")
 
 
+class LMSA:
+    """Layered min-sum is corrected min-sum on another schedule: it has no meaning over the erasure channel either."""
+    id_keys = ["max_iter", "msa_scale", "msa_offset"]
+
+    def __init__(self, *a, **k):
+        raise NotImplementedError("decoder LMSA (layered corrected min-sum) does not exist over the bec: the erasure decoder has no "
+                                  "magnitudes to correct; use SPA / MSA there")
+
+
 class QMSA:
     """Fixed-point min-sum has no meaning over the erasure channel either: the ternary decoder has no magnitudes to quantise."""
     id_keys = ["max_iter", "msa_bits", "msa_frac_bits", "msa_scale", "msa_offset"]

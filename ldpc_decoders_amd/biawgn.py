@@ -54,6 +54,13 @@ class NMSA(LLR):  # corrected (normalised / offset) min-sum: no upstream counter
         super().__init__(snr_in_db, bpa.NMSA(_code, **kwargs))
 
 
+class LMSA(LLR):  # layered corrected min-sum on the streaming kernels: no upstream counterpart, wrapped like NMSA
+    id_keys = bpa.LMSA.id_keys
+
+    def __init__(self, snr_in_db, _code, **kwargs):
+        super().__init__(snr_in_db, bpa.LMSA(_code, **kwargs))
+
+
 class QMSA(LLR):  # fixed-point min-sum (q-bit saturating messages): no upstream counterpart, wrapped like MSA
     id_keys = bpa.QMSA.id_keys
 

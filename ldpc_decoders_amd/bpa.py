@@ -12,7 +12,7 @@ Extra constructor keywords (all optional):
 """
 import numpy as np
 
-from ._device import DecoderHandle, OsdHandle, as_code, check_correction, check_fixed_point
+from ._device import DecoderHandle, OsdHandle, as_code, check_correction, check_fixed_point, check_layers
 
 
 class BPA:
@@ -102,6 +102,36 @@ class NMSA(BPA):
         self.handle.set_correction(self.msa_scale, self.msa_offset)
 
 
+class LMSA(BPA):
+    """Layered (serial-C) corrected min-sum (no upstream counterpart): the check rule of ``NMSA``, but the checks are processed layer by
+    layer and every layer already sees the marginals the one before it left -- about half the sweeps of the flooding schedule.  ``layers``:
+    the layer of every check (two checks of a layer share no variable); None: greedy, every check takes the first layer it fits.  Runs on
+    the streaming kernels in f32 / f64; ``decode`` / ``decode_batch`` as ``NMSA``.  The contract: include/ldpc_hip.h (LDPC_ALG_LMSA)."""
+    alg = "LMSA"
+    id_keys = ["max_iter", "msa_scale", "msa_offset"]
+
+    def __init__(self, parity_mtx, **kwargs):
+        scale, offset, layers = kwargs.get("msa_scale"), kwargs.get("msa_offset"), kwargs.get("layers")
+        # (checked before the decoder is created: a bad value never reaches the device)
+        self.msa_scale, self.msa_offset = check_correction(0.8125 if scale is None else scale, 0.0 if offset is None else offset)
+        code = as_code(parity_mtx)
+        if layers is not None:
+            layers = check_layers(code, layers)
+        if np.bincount(np.asarray(code.edge_chk), minlength=code.m).min() < 2:
+            raise ValueError("layered min-sum needs every check to have at least two variables")
+        if kwargs.get("precision") == "f16" or kwargs.get("backend") == "fused":
+            raise ValueError("layered min-sum runs on the streaming kernels in f32 or f64")
+        super().__init__(code, **kwargs)
+        self.handle.set_correction(self.msa_scale, self.msa_offset)
+        if layers is not None:
+            self.handle.set_layers(layers)
+
+    @property
+    def layers(self):
+        """The layer of every check, as the library holds it (``ldpc_decoder_get_layers``)."""
+        return self.handle.layers()[1]
+
+
 class QMSA(BPA):
     """Fixed-point min-sum (no upstream counterpart): the decoder as silicon builds it.  Priors are quantised to ``msa_bits``-bit levels,
     ``clamp(rint(prior * 2**msa_frac_bits), -V, V)`` with ``V = 2**(msa_bits - 1) - 1``; every check message is
@@ -142,7 +172,7 @@ def check_osd_size(code):
 
 class OSD:
     """Belief propagation followed by ordered-statistics decoding of the frames it leaves without a codeword (no upstream counterpart; it
-    adds to ``BPA.decode``, src/bpa.py:17-63).  ``osd_bp`` in {MSA, SPA, NMSA, QMSA} names the decoder in front (its own keywords apply),
+    adds to ``BPA.decode``, src/bpa.py:17-63).  ``osd_bp`` in {MSA, SPA, NMSA, QMSA, LMSA} names the decoder in front (its own keywords apply),
     ``osd_order`` in {0, 1}, ``osd_depth`` >= 0 the number of single flips order 1 tries.  The output is always a codeword.  ``decode`` /
     ``decode_batch`` as ``BPA``; ``last_pick`` holds per frame -1 (BP's word, untouched) or the winning candidate.  The contract:
     include/ldpc_hip.h (ldpc_osd_*), DESIGN.md section 17."""
@@ -157,12 +187,14 @@ class OSD:
         if self.osd_order not in (0, 1) or self.osd_depth < 0:
             raise ValueError("osd_order must be 0 or 1 and osd_depth >= 0 (got %r, %r)" % (order, depth))
         self.osd_bp = kwargs.get("osd_bp") or "NMSA"
-        front = {"MSA": MSA, "SPA": SPA, "NMSA": NMSA, "QMSA": QMSA}.get(self.osd_bp)
+        front = {"MSA": MSA, "SPA": SPA, "NMSA": NMSA, "QMSA": QMSA, "LMSA": LMSA}.get(self.osd_bp)
         if front is None:
-            raise ValueError("osd_bp must be one of MSA, SPA, NMSA, QMSA (got %r)" % (self.osd_bp,))
+            raise ValueError("osd_bp must be one of MSA, SPA, NMSA, QMSA, LMSA (got %r)" % (self.osd_bp,))
         self.precision = kwargs.get("precision") or "f64"
         if self.precision not in ("f32", "f64"):
             raise ValueError("ordered-statistics post-processing needs the soft output of an f32 or f64 decoder (got precision %r)" % self.precision)
+        # (every keyword goes on to the decoder in front.  ``layers`` then means a layering of the checks to LMSA: a caller that forwards
+        # command-line arguments must drop the ADMMA flag of that name first, as main.py does)
         self.bp = front(self.code, **kwargs)
         self.handle = OsdHandle(self.bp.handle, self.osd_order, self.osd_depth)
         self.last_iters = self.last_pick = None

@@ -56,6 +56,13 @@ class NMSA(LLR):  # corrected (normalised / offset) min-sum: no upstream counter
         super().__init__(p, bpa.NMSA(_code, **kwargs))
 
 
+class LMSA(LLR):  # layered corrected min-sum on the streaming kernels: no upstream counterpart, wrapped like NMSA
+    id_keys = bpa.LMSA.id_keys
+
+    def __init__(self, p, _code, **kwargs):
+        super().__init__(p, bpa.LMSA(_code, **kwargs))
+
+
 class QMSA(LLR):  # fixed-point min-sum (q-bit saturating messages): no upstream counterpart, wrapped like MSA
     id_keys = bpa.QMSA.id_keys
 

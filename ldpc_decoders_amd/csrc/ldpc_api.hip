@@ -1,4 +1,5 @@
 // extern "C" surface of libldpc_hip.so (declared in include/ldpc_hip.h).
+#include <algorithm>
 #include <array>
 #include <cmath>
 #include <cstring>
@@ -151,6 +152,10 @@ int grid_guard_available(const Decoder* d, int bk, uint32_t flags, const char* w
         set_error("%s: prior grid: fixed-point min-sum (LDPC_ALG_QMSA) quantises its priors itself (ldpc_decoder_set_fixed_point)", who);
         return LDPC_E_UNSUPPORTED;
     }
+    if (LDPC_FLAG_PRIOR_GRID_OF(flags) >= 0 && d->alg == ALG_LMSA) {  // likewise
+        set_error("%s: prior grid: layered min-sum (LDPC_ALG_LMSA) has no exact-in-fp32 mode (a scale takes values off the grid)", who);
+        return LDPC_E_UNSUPPORTED;
+    }
     if (LDPC_FLAG_PRIOR_GRID_OF(flags) < 0 || d->dtype == DT_F64) return LDPC_OK;
     if (bk == BK_FUSED && d->alg == ALG_MSA) return LDPC_OK;
     set_error("%s: prior grid: the exactness guard lives in the LDS-resident fp32 min-sum kernels; this decoder runs on the streaming kernels", who);
@@ -166,7 +171,73 @@ int pick_backend(Decoder* d) {
     }
     return BK_STREAM;
 }
+
+// The layering of an LDPC_ALG_LMSA decoder, checked on the host, then mirrored on the device.  A refused layering changes nothing.  The
+// device list always has m entries (reserved once, at create), so the only step that can fail behind the host check is the copy itself;
+// should it fail, the greedy layering is put back on both sides or, failing that too, the decoder is left without one (layer_start
+// empty: every decode then runs zero layer passes) -- host and device never disagree.
+int install_layers(Decoder* d, const int32_t* layer_of_check) {
+    std::vector<int32_t> of_check, sorted, start;
+    LDPC_TRY(layering_build(d->code, layer_of_check, &of_check, &sorted, &start));
+    LDPC_HIP_TRY(hipSetDevice(d->code->device));
+    LDPC_TRY(d->layer_order.reserve(sorted.size() * sizeof(int32_t)));
+    LDPC_HIP_TRY(hipDeviceSynchronize());  // a decode in flight, on whichever stream, still reads the list (documented in the header)
+    if (hipMemcpy(d->layer_order.p, sorted.data(), sorted.size() * sizeof(int32_t), hipMemcpyHostToDevice) != hipSuccess) {
+        set_error("layering: copying the processing order to the device failed");
+        d->layer_start.clear();
+        if (layer_of_check) (void)install_layers(d, nullptr);
+        set_error("layering: copying the processing order to the device failed; the greedy layering is in force");
+        return LDPC_E_HIP;
+    }
+    d->layer_of_check.swap(of_check);
+    d->layer_start.swap(start);
+    return LDPC_OK;
+}
 }  // namespace
+
+int layering_build(const Code* c, const int32_t* layer_of_check, std::vector<int32_t>* of_check, std::vector<int32_t>* sorted,
+                   std::vector<int32_t>* start) {
+    const int32_t m = c->m;
+    std::vector<int32_t> lay((size_t)m);
+    std::vector<std::vector<int32_t>> used((size_t)c->n);  // layers that already hold a check of the variable
+    for (int32_t cc = 0; cc < m; ++cc) {
+        const int32_t k0 = c->row_ptr[cc], k1 = c->row_ptr[cc + 1];
+        int32_t l = 0;
+        if (layer_of_check) {
+            l = layer_of_check[cc];
+            if (l < 0) {
+                set_error("layering: check %d has the negative layer %d", cc, l);
+                return LDPC_E_ARG;
+            }
+            for (int32_t k = k0; k < k1; ++k)
+                for (int32_t u : used[(size_t)c->edge_var[k]])
+                    if (u == l) {
+                        set_error("layering: check %d shares variable %d with an earlier check of its layer %d", cc, c->edge_var[k], l);
+                        return LDPC_E_ARG;
+                    }
+        } else {  // greedy: the smallest layer none of whose checks shares a variable with this one
+            for (;; ++l) {
+                bool clash = false;
+                for (int32_t k = k0; k < k1 && !clash; ++k)
+                    for (int32_t u : used[(size_t)c->edge_var[k]]) clash = clash || u == l;
+                if (!clash) break;
+            }
+        }
+        lay[(size_t)cc] = l;
+        for (int32_t k = k0; k < k1; ++k) used[(size_t)c->edge_var[k]].push_back(l);
+    }
+    std::vector<int32_t> ord((size_t)m);
+    for (int32_t cc = 0; cc < m; ++cc) ord[(size_t)cc] = cc;
+    std::stable_sort(ord.begin(), ord.end(), [&](int32_t a, int32_t b) { return lay[(size_t)a] < lay[(size_t)b]; });  // ascending (layer, index)
+    std::vector<int32_t> st;
+    for (int32_t i = 0; i < m; ++i)
+        if (i == 0 || lay[(size_t)ord[(size_t)i]] != lay[(size_t)ord[(size_t)i - 1]]) st.push_back(i);
+    st.push_back(m);
+    of_check->swap(lay);
+    sorted->swap(ord);
+    start->swap(st);
+    return LDPC_OK;
+}
 
 int code_build_host(int32_t m, int32_t n, int64_t E, const int32_t* chk, const int32_t* var, Code* c) {
     if (!chk || !var || m <= 0 || n <= 0 || E <= 0 || E > (int64_t)1 << 30) {
@@ -317,10 +388,15 @@ int ldpc_plan_layout(int32_t m, int32_t n, int64_t E, const int32_t* chk, const 
 
 int ldpc_decoder_create(ldpc_code_t code, int alg, int dtype, int backend, ldpc_decoder_t* out) {
     return guarded("ldpc_decoder_create", [&]() -> int {
-        if (!code || !out || alg < 0 || alg > ALG_QMSA || dtype < 0 || dtype > 2 || (dtype == DT_F16 && (alg == ALG_BEC || backend == BK_FUSED)) ||
-            backend < 0 || backend > 2) {
+        if (!code || !out || alg < 0 || alg > ALG_LMSA || dtype < 0 || dtype > 2 ||
+            (alg != ALG_LMSA && dtype == DT_F16 && (alg == ALG_BEC || backend == BK_FUSED)) || backend < 0 || backend > 2) {
             set_error("ldpc_decoder_create: bad arguments (alg=%d dtype=%d backend=%d)", alg, dtype, backend);
             return LDPC_E_ARG;
+        }
+        if (alg == ALG_LMSA && (dtype == DT_F16 || backend == BK_FUSED || ((Code*)code)->min_dc < 2)) {
+            set_error("ldpc_decoder_create: layered min-sum (LDPC_ALG_LMSA) runs on the streaming kernels in fp32 or fp64, on codes whose checks "
+                      "all have degree >= 2 (dtype=%d backend=%d smallest check degree=%d)", dtype, backend, ((Code*)code)->min_dc);
+            return LDPC_E_UNSUPPORTED;
         }
         Decoder* d = new (std::nothrow) Decoder();
         if (!d) return LDPC_E_NOMEM;
@@ -351,6 +427,18 @@ int ldpc_decoder_create(ldpc_code_t code, int alg, int dtype, int backend, ldpc_
             ldpc_decoder_destroy((ldpc_decoder_t)d);
             return LDPC_E_UNSUPPORTED;
         }
+        if (alg == ALG_LMSA) {
+            try {
+                rc = install_layers(d, nullptr);  // greedy
+            } catch (...) {
+                ldpc_decoder_destroy((ldpc_decoder_t)d);
+                throw;
+            }
+            if (rc) {
+                ldpc_decoder_destroy((ldpc_decoder_t)d);
+                return rc;
+            }
+        }
         *out = (ldpc_decoder_t)d;
         return LDPC_OK;
     });
@@ -376,8 +464,8 @@ int ldpc_decoder_destroy(ldpc_decoder_t h) {
 int ldpc_decoder_set_correction(ldpc_decoder_t h, double scale, double offset) {
     return guarded("ldpc_decoder_set_correction", [&]() -> int {
         Decoder* d = (Decoder*)h;
-        if (!d || d->alg != ALG_NMSA) {
-            set_error("ldpc_decoder_set_correction: a corrected min-sum decoder (LDPC_ALG_NMSA) is needed");
+        if (!d || (d->alg != ALG_NMSA && d->alg != ALG_LMSA)) {
+            set_error("ldpc_decoder_set_correction: a corrected min-sum decoder (LDPC_ALG_NMSA, LDPC_ALG_LMSA) is needed");
             return LDPC_E_ARG;
         }
         // (written so that a NaN fails every test)
@@ -394,8 +482,8 @@ int ldpc_decoder_set_correction(ldpc_decoder_t h, double scale, double offset) {
 int ldpc_decoder_get_correction(ldpc_decoder_t h, double* scale, double* offset) {
     return guarded("ldpc_decoder_get_correction", [&]() -> int {
         Decoder* d = (Decoder*)h;
-        if (!d || !scale || !offset || d->alg != ALG_NMSA) {
-            set_error("ldpc_decoder_get_correction: a corrected min-sum decoder (LDPC_ALG_NMSA) and two result pointers are needed");
+        if (!d || !scale || !offset || (d->alg != ALG_NMSA && d->alg != ALG_LMSA)) {
+            set_error("ldpc_decoder_get_correction: a corrected min-sum decoder (LDPC_ALG_NMSA, LDPC_ALG_LMSA) and two result pointers are needed");
             return LDPC_E_ARG;
         }
         *scale = d->corr_scale;
@@ -436,6 +524,34 @@ int ldpc_decoder_get_fixed_point(ldpc_decoder_t h, int* bits, int* frac_bits, do
         *frac_bits = d->fx_frac;
         *scale = d->fx_scale;
         *offset = d->fx_offset;
+        return LDPC_OK;
+    });
+}
+
+int ldpc_decoder_set_layers(ldpc_decoder_t h, const int32_t* layer_of_check_host, int32_t m) {
+    return guarded("ldpc_decoder_set_layers", [&]() -> int {
+        Decoder* d = (Decoder*)h;
+        if (!d || d->alg != ALG_LMSA) {
+            set_error("ldpc_decoder_set_layers: a layered min-sum decoder (LDPC_ALG_LMSA) is needed");
+            return LDPC_E_ARG;
+        }
+        if (layer_of_check_host && m != d->code->m) {
+            set_error("ldpc_decoder_set_layers: %d entries for a code of %d checks", m, d->code->m);
+            return LDPC_E_ARG;
+        }
+        return install_layers(d, layer_of_check_host);
+    });
+}
+
+int ldpc_decoder_get_layers(ldpc_decoder_t h, int32_t* nlayers, int32_t* layer_of_check_host) {
+    return guarded("ldpc_decoder_get_layers", [&]() -> int {
+        Decoder* d = (Decoder*)h;
+        if (!d || !nlayers || d->alg != ALG_LMSA) {
+            set_error("ldpc_decoder_get_layers: a layered min-sum decoder (LDPC_ALG_LMSA) and a result pointer are needed");
+            return LDPC_E_ARG;
+        }
+        *nlayers = (int32_t)d->layer_start.size() - 1;
+        if (layer_of_check_host) std::copy(d->layer_of_check.begin(), d->layer_of_check.end(), layer_of_check_host);
         return LDPC_OK;
     });
 }
@@ -947,6 +1063,10 @@ static int simulate_impl(ldpc_decoder_t h, int channel, double param, int codewo
     }
     if (grid_k >= 0 && d->alg == ALG_QMSA) {
         set_error("ldpc_simulate: prior grid: fixed-point min-sum (LDPC_ALG_QMSA) quantises its priors itself (ldpc_decoder_set_fixed_point)");
+        return LDPC_E_UNSUPPORTED;
+    }
+    if (grid_k >= 0 && d->alg == ALG_LMSA) {
+        set_error("ldpc_simulate: prior grid: layered min-sum (LDPC_ALG_LMSA) has no exact-in-fp32 mode (a scale takes values off the grid)");
         return LDPC_E_UNSUPPORTED;
     }
     // Fixed-point min-sum over a BSC whose LLR is (close to) less than half a level: every prior quantises to level 0 and no longer carries the

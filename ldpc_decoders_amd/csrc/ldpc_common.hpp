@@ -27,7 +27,8 @@ namespace ldpc {
 enum Alg : int {
     ALG_MSA = 0, ALG_SPA = 1, ALG_BEC = 2,
     ALG_NMSA = 3,  // normalised / offset min-sum (ldpc_cn.hpp cn_msa<.., MSA_CORRECTED>)
-    ALG_QMSA = 4   // fixed-point min-sum: q-bit saturating messages on the integer grid (ldpc_cn.hpp cn_msa<.., MSA_FIXED>, quantise_prior)
+    ALG_QMSA = 4,  // fixed-point min-sum: q-bit saturating messages on the integer grid (ldpc_cn.hpp cn_msa<.., MSA_FIXED>, quantise_prior)
+    ALG_LMSA = 5   // layered (serial-C) corrected min-sum on the streaming kernels (ldpc_stream.hip k_layer; the rule is ALG_NMSA's)
 };
 // min-sum family: everything that is keyed on "the rule is compare / negate only" (register tuning, sign-bit shortcuts, table words) treats
 // the corrected rule as min-sum
@@ -124,7 +125,7 @@ enum BufKind : int {
 struct Decoder {
     Code* code = nullptr;
     int alg = ALG_MSA, dtype = DT_F32, backend = BK_AUTO;
-    double corr_scale = 1.0, corr_offset = 0.0;  // ALG_NMSA: c2v = sign * max(scale * min - offset, 0) (ldpc_decoder_set_correction); read at every launch
+    double corr_scale = 1.0, corr_offset = 0.0;  // ALG_NMSA, ALG_LMSA: c2v = sign * max(scale * min - offset, 0) (ldpc_decoder_set_correction); read at every launch
     // ALG_QMSA (ldpc_decoder_set_fixed_point; read at every launch): priors -> clamp(rint(prior * 2^fx_frac), -V, V), V = 2^(fx_bits - 1) - 1;
     // c2v = sign * max(floor(fx_scale * min(m, V)) - fx_offset, 0)
     int fx_bits = 6, fx_frac = 2, fx_offset = 0;
@@ -136,6 +137,10 @@ struct Decoder {
         return c > 0.0 ? c : 0.0;
     }
     double fx_step() const { return fx_frac >= 0 ? (double)(1 << fx_frac) : 1.0 / (double)(1 << -fx_frac); }
+    // ALG_LMSA (ldpc_decoder_set_layers; greedy at create): layer of every check as the caller numbered it; on the device the checks
+    // sorted by (layer, index) -- the processing order -- and on the host where each layer begins in that list ([nlayers + 1])
+    std::vector<int32_t> layer_of_check, layer_start;
+    DevBuf layer_order;
     // streaming workspace: set[0] holds the state when a decode begins, every frame repack moves it to the other set
     TileSet set[2];
     DevBuf c2v16;      // fp16 storage: check -> variable lines, rebuilt by every check pass (not part of a set: a repack does not move them)
@@ -153,7 +158,7 @@ struct Decoder {
         for (TileSet& s : set)
             for (DevBuf* b : {&s.edge, &s.node, &s.prior, &s.planes, &s.live, &s.fmap}) f(*b, BUF_STATE);
         for (DevBuf* b : {&c2v16, &rmap}) f(*b, BUF_STATE);
-        for (DevBuf* b : {&rbase, &flags, &graph_tab, &gridviol}) f(*b, BUF_SHARED);
+        for (DevBuf* b : {&rbase, &flags, &graph_tab, &gridviol, &layer_order}) f(*b, BUF_SHARED);
         for (DevBuf* b : {&h_in, &h_y0, &h_out, &h_iters, &h_bits, &h_era, &sim_errs}) f(*b, BUF_STAGING);
     }
     // fused backend
@@ -169,7 +174,7 @@ struct Decoder {
     // optional per-kernel timing with HIP events recorded on the decode stream (bench.py roofline leg)
     bool profile = false;
     std::vector<hipEvent_t> ev_pool;
-    double prof_ms[4] = {0, 0, 0, 0};     // [0] check pass, [1] variable pass, [2] fused decode kernel, [3] whole streaming decode
+    double prof_ms[4] = {0, 0, 0, 0};     // [0] check pass (ALG_LMSA: layer passes), [1] variable pass (ALG_LMSA: decision pass), [2] fused decode kernel, [3] whole streaming decode
     int64_t prof_launches[4] = {0, 0, 0, 0};
     // statistics of the last decode call
     int last_sweeps = 0;
@@ -189,6 +194,12 @@ int prof_collect(Decoder* d, const std::vector<ProfSpan>& spans);
 
 // ---- backends (each returns an LDPC_* code) -------------------------------------------------------
 int stream_decode(Decoder* d, const DecodeCall& k);
+
+// ALG_LMSA, host only: the layering `layer_of_check` ([m]; null: greedy -- every check takes the smallest layer none of whose checks
+// shares a variable with it) checked and sorted into `of_check` / `sorted` (what Decoder::layer_order mirrors) / `start`.  LDPC_E_ARG, outputs untouched,
+// for a negative entry or two checks of one layer that share a variable.
+int layering_build(const Code* c, const int32_t* layer_of_check, std::vector<int32_t>* of_check, std::vector<int32_t>* sorted,
+                   std::vector<int32_t>* start);
 
 // bit-sliced erasure decoder on the streaming kernels (ldpc_bec_stream.hip)
 int becs_stream_decode(Decoder* d, const DecodeCall& k);

@@ -341,7 +341,7 @@ int check_decoder(const char* who, const Osd* h, const Decoder* d) {
         return LDPC_E_ARG;
     }
     if (d->alg == ALG_BEC || d->dtype == DT_F16) {
-        set_error("%s: needs the soft output of an fp32 or fp64 LDPC_ALG_MSA / SPA / NMSA / QMSA decoder (the erasure decoder has none, fp16 "
+        set_error("%s: needs the soft output of an fp32 or fp64 LDPC_ALG_MSA / SPA / NMSA / QMSA / LMSA decoder (the erasure decoder has none, fp16 "
                   "storage keeps none in the decoder's type)", who);
         return LDPC_E_UNSUPPORTED;
     }

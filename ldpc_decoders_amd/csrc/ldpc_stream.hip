@@ -20,6 +20,9 @@
 // re-reads hit on chip, against the s(4E + n) of SURVEY.md section 8(d) (v2c written and read back); bench.py prices the kernels
 // with the section-8(d) ALGORITHMIC bytes and reports the PMC traffic beside it.
 //
+// Layered min-sum (ALG_LMSA, no upstream counterpart) keeps the same c2v / marg state but no prior tiles and updates the marginals in place:
+// one layer pass per layer of checks (k_layer) and a decision pass (k_decide) instead of the two passes above -- s(4E + n) bytes per frame-sweep.
+//
 // Reference semantics reproduced (file:line relative to thadikari/ldpc_decoders):
 //   flooding loop, max_iter and syndrome exits, x_hat = (marginal < 0) ...... src/bpa.py:17-63
 //   iteration-0 check of the received word (BSC) ............................ src/bpa.py:20,29
@@ -374,6 +377,120 @@ __global__ __launch_bounds__(256) void k_vn(const int32_t* __restrict__ col_ptr,
 }
 
 // ---------------------------------------------------------------------------------------------------
+// Layered min-sum (ALG_LMSA; the contract is in include/ldpc_hip.h).  The state is the flooding state -- c2v[tile][E][64] and
+// marg[tile][n][64], lane == frame -- but the marginals are updated IN PLACE, check by check: v = marg - c2v_old, the corrected min-sum
+// rule on the row, c2v = the new message, marg = v + c2v.  The checks of one LAYER share no variable, so they touch disjoint marginal rows
+// and run in any order and in parallel: one launch per layer, the launches ordered on the stream.  A wave takes (tile, run of the layer's
+// checks) out of `order`, the checks sorted by (layer, index); `c0` .. `c1` is the layer's range in that list.  UNR checks are in flight
+// together (all of one layer, hence independent).  Per edge: one marginal row and one message row read, one each written.  FIRST: the
+// first sweep, where every old message is +0 and x - (+0) == x bit for bit: nothing is read.  `freeze` as in k_cn: a soft-output decode
+// keeps the marginals of a frame that has left.
+template <typename T, int DCMAX, int FIXED_DC, int UNR, bool FIRST>
+__global__ __launch_bounds__(256) void k_layer(const int32_t* __restrict__ row_ptr, const int32_t* __restrict__ edge_var,
+                                               const int32_t* __restrict__ order, T* c2v, T* marg, const u64* __restrict__ live, int m, int n,
+                                               int64_t E, int tiles, int chunks, int cpw, int c0, int c1, int xcd_aware, int freeze, T scale,
+                                               T offset) {
+    const int lane = threadIdx.x;
+    int tile, chunk;
+    if (!task_of(tiles, chunks, xcd_aware, &tile, &chunk)) return;
+    const u64 lv = live[tile];
+    if (lv == 0) return;
+    const bool on = freeze ? (bool)((lv >> lane) & 1ull) : true;
+    if (!on) return;  // (no wave-wide operation below)
+    // irregular rows: as in k_cn, where most rows are nearly DCMAX long every line is fetched unconditionally (a short row re-reads its
+    // last edge) -- a branch per line keeps the loads of a group of checks from being issued together
+    // (degree classes up to 8, the ensembles this form was measured on; both forms in one kernel cost the wide classes their registers)
+    const bool dense = FIXED_DC > 0 || (DCMAX <= 8 && E * 4 >= (int64_t)m * DCMAX * 3);  // (wave-uniform)
+    T* ct = c2v + (int64_t)tile * E * 64 + lane;
+    T* mt = marg + (int64_t)tile * n * 64 + lane;
+    const int i_end = min(c1, c0 + (chunk + 1) * cpw);
+    for (int i = c0 + chunk * cpw; i < i_end; i += UNR) {
+        T v[UNR][DCMAX], w[UNR][DCMAX];
+        int k0[UNR], deg[UNR];
+#pragma unroll
+        for (int u = 0; u < UNR; ++u) {
+            if (i + u < i_end) {
+                const int cc = order[i + u];
+                k0[u] = FIXED_DC > 0 ? cc * FIXED_DC : row_ptr[cc];
+                deg[u] = FIXED_DC > 0 ? FIXED_DC : row_ptr[cc + 1] - k0[u];
+            } else {
+                k0[u] = 0;
+                deg[u] = 0;
+            }
+        }
+        if (dense) {
+#pragma unroll
+            for (int u = 0; u < UNR; ++u) {
+#pragma unroll
+                for (int j = 0; j < DCMAX; ++j) {
+                    const int kk = FIXED_DC > 0 ? k0[u] + j : (deg[u] > 0 ? k0[u] + (j < deg[u] ? j : deg[u] - 1) : 0);
+                    v[u][j] = mt[(int64_t)edge_var[kk] * 64];
+                    if constexpr (!FIRST) w[u][j] = msg_ld<CN_NTL>(ct + (int64_t)kk * 64);
+                }
+            }
+        } else {
+#pragma unroll
+            for (int u = 0; u < UNR; ++u) {
+#pragma unroll
+                for (int j = 0; j < DCMAX; ++j) {
+                    if (j < deg[u]) {
+                        v[u][j] = mt[(int64_t)edge_var[k0[u] + j] * 64];
+                        if constexpr (!FIRST) w[u][j] = msg_ld<CN_NTL>(ct + (int64_t)(k0[u] + j) * 64);
+                    }
+                }
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < UNR; ++u) {
+#pragma unroll
+            for (int j = 0; j < DCMAX; ++j) {
+                if constexpr (!FIRST) v[u][j] = v[u][j] - w[u][j];
+                w[u][j] = v[u][j];
+            }
+            cn_msa<T, DCMAX, MSA_CORRECTED>(w[u], deg[u], Correction<T>{scale, offset});
+#pragma unroll
+            for (int j = 0; j < DCMAX; ++j) {
+                if (j < deg[u]) {
+                    msg_st<CN_NTS>(ct + (int64_t)(k0[u] + j) * 64, w[u][j]);
+                    mt[(int64_t)edge_var[k0[u] + j] * 64] = v[u][j] + w[u][j];
+                }
+            }
+        }
+    }
+}
+
+// Decision pass of the layered decoder: marginals -> decision bit planes, behind the last layer of a sweep.  The words keep the bits of the
+// frames that have left (as k_vn's do).
+template <typename T>
+__global__ __launch_bounds__(256) void k_decide(const T* __restrict__ marg, const u64* __restrict__ live, u64* __restrict__ xbits, int n, int tiles,
+                                                int chunks, int vpw, int xcd_aware) {
+    const int lane = threadIdx.x;
+    int tile, chunk;
+    if (!task_of(tiles, chunks, xcd_aware, &tile, &chunk)) return;
+    const u64 lv = live[tile];
+    if (lv == 0) return;
+    const T* mt = marg + (int64_t)tile * n * 64 + lane;
+    u64* xb = xbits + plane_at(tile, 0, n);  // word of variable v at xb[8 * v]
+    const int v_end = min(n, (chunk + 1) * vpw);
+    for (int v = chunk * vpw; v < v_end; ++v) {
+        const u64 one = __ballot(mt[(int64_t)v * 64] < T(0));  // NaN marginal -> 0, as k_vn
+        u64 merged = one;
+        if (lv != ~0ull) merged = (uniform_ld64(xb + 8 * v) & ~lv) | (one & lv);
+        if (lane == 0) xb[8 * v] = merged;
+    }
+}
+
+// soft output of the layered decoder: the marginal tiles start as the priors, so a frame that never swept (iters == 0: it left at the
+// iteration-0 check) reports 0 as it does everywhere else
+template <typename T>
+__global__ void k_soft_out_swept(const T* __restrict__ soft_t, const int32_t* __restrict__ iters, T* __restrict__ out, int64_t B, int n) {
+    const int tile = blockIdx.y, lane = threadIdx.x & 63;
+    const int v = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int64_t fr = (int64_t)tile * 64 + lane;
+    if (v < n && fr < B) out[fr * n + v] = iters[fr] > 0 ? soft_t[((int64_t)tile * n + v) * 64 + lane] : T(0);
+}
+
+// ---------------------------------------------------------------------------------------------------
 // Syndrome of the current hard decisions; frames whose syndrome is zero leave (iters = sweeps run so far).
 // Two kernels: k_syndrome_part -- a block takes a GROUP of eight tiles and a chunk of the checks; a thread fetches, per edge of its
 // check, the one 64-byte sector that holds the decision words of the variable for all eight tiles (per-tile 8-byte gathers made this
@@ -441,7 +558,8 @@ __global__ __launch_bounds__(64) void k_syndrome_fin(u64* __restrict__ unsat_acc
 // frame; lanes that share a source tile share the 256-byte line, so a line of a source tile is fetched once per destination tile
 // that draws from it.  The decisions of every frame of the old tiles are written out before (k_unpack), the moved frames
 // overwrite theirs at the end.
-template <typename T>
+// (PRIOR false: the layered decoder keeps no prior tiles)
+template <typename T, bool PRIOR = true>
 __global__ __launch_bounds__(256) void k_repack(const T* __restrict__ msg_src, T* __restrict__ msg_dst, const T* __restrict__ marg_src,
                                                 T* __restrict__ marg_dst, const T* __restrict__ prior_src, T* __restrict__ prior_dst,
                                                 const u64* __restrict__ xb_src, u64* __restrict__ xb_dst,
@@ -465,7 +583,7 @@ __global__ __launch_bounds__(256) void k_repack(const T* __restrict__ msg_src, T
             md[r * 64] = has ? ms[r * 64] : T(0);
         } else {
             const int64_t v = r - E;
-            prior_dst[dof + v * 64] = has ? prior_src[so + v * 64] : T(0);
+            if constexpr (PRIOR) prior_dst[dof + v * 64] = has ? prior_src[so + v * 64] : T(0);
             marg_dst[dof + v * 64] = has ? marg_src[so + v * 64] : T(0);
             const u64 w = has ? xb_src[plane_at(st, v, n)] : 0ull;
             const u64 plane = __ballot(has && ((w >> sl) & 1ull));
@@ -723,6 +841,28 @@ void dispatch_vn(const Code* c, const T* c2v, const T* prior, T* marg, const u64
     });
 }
 
+// The layered sweep (ALG_LMSA): one layer pass per layer, in order on the stream, then the decision pass.  Degree classes of dispatch_cn.
+template <typename T>
+void dispatch_layers(const Decoder* d, T* c2v, T* marg, const u64* live, const Geometry& g, bool first, hipStream_t st) {
+    const Code* c = d->code;
+    check_class(c, [&](auto dcm, auto fdc) {
+        constexpr int DCMAX = decltype(dcm)::value, FDC = decltype(fdc)::value, UNR = unroll_for(2 * DCMAX * (int)sizeof(T));
+        const auto kern = first ? k_layer<T, DCMAX, FDC, UNR, true> : k_layer<T, DCMAX, FDC, UNR, false>;
+        for (size_t l = 0; l + 1 < d->layer_start.size(); ++l) {
+            const int c0 = d->layer_start[l], c1 = d->layer_start[l + 1];
+            const int chunks = (c1 - c0 + g.cpw - 1) / g.cpw;
+            hipLaunchKernelGGL(kern, dim3(task_blocks(g.tiles, chunks, g.xcd_aware)), dim3(64, 4), 0, st, c->d_row_ptr, c->d_edge_var,
+                               (const int32_t*)d->layer_order.p, c2v, marg, live, c->m, c->n, c->E, g.tiles, chunks, g.cpw, c0, c1, g.xcd_aware, g.freeze,
+                               (T)g.corr_scale, (T)g.corr_offset);
+        }
+    });
+}
+template <typename T>
+void dispatch_decide(const Code* c, const T* marg, const u64* live, u64* xbits, const Geometry& g, hipStream_t st) {
+    hipLaunchKernelGGL((k_decide<T>), dim3(task_blocks(g.tiles, g.vn_chunks, g.xcd_aware)), dim3(64, 4), 0, st, marg, live, xbits, c->n, g.tiles, g.vn_chunks, g.vpw,
+                       g.xcd_aware);
+}
+
 int env_int(const char* name, int dflt) {
     const char* e = std::getenv(name);
     return e && *e ? atoi(e) : dflt;
@@ -748,6 +888,8 @@ int run(Decoder* d, const DecodeCall& k, const SimSource* sim = nullptr) {
     const hipStream_t st = k.stream;
     const int tiles = (int)((B + 63) / 64);
     if (!degrees_supported(c)) return LDPC_E_UNSUPPORTED;
+    // layered min-sum: the marginal tiles start as the priors and are updated in place -- no prior tiles, no variable pass
+    constexpr bool LAYERED = ALG == ALG_LMSA;
     const bool early = !(k.flags & FLAG_NO_EARLY_EXIT);
     RepackPolicy repack(early && k.soft == nullptr && tiles >= 2);
 
@@ -755,7 +897,7 @@ int run(Decoder* d, const DecodeCall& k, const SimSource* sim = nullptr) {
     TileSet* const set = d->set;
     LDPC_TRY(set[0].edge.reserve((size_t)tiles * E * 64 * sizeof(T)));
     LDPC_TRY(set[0].node.reserve((size_t)tiles * n * 64 * sizeof(T)));
-    LDPC_TRY(set[0].prior.reserve((size_t)tiles * n * 64 * sizeof(T)));
+    if (!LAYERED) LDPC_TRY(set[0].prior.reserve((size_t)tiles * n * 64 * sizeof(T)));
     LDPC_TRY(set[0].planes.reserve(plane_words(tiles, n) * 8));
     LDPC_TRY(set[0].live.reserve((size_t)tiles * 8));
     LDPC_TRY(d->flags.reserve((size_t)tiles * 16 + 64 + POLL_RING * 16));
@@ -763,14 +905,15 @@ int run(Decoder* d, const DecodeCall& k, const SimSource* sim = nullptr) {
         // second state set: the first repack fires at <= fill * 64 live frames per tile, later ones only shrink
         const size_t nt = (size_t)(repack.fill * tiles) + 2;
         if (set[1].edge.reserve(nt * E * 64 * sizeof(T)) || set[1].node.reserve(nt * n * 64 * sizeof(T)) ||
-            set[1].prior.reserve(nt * n * 64 * sizeof(T)) || set[1].planes.reserve(plane_words((int)nt, n) * 8) || set[1].live.reserve(nt * 8) ||
+            (!LAYERED && set[1].prior.reserve(nt * n * 64 * sizeof(T))) || set[1].planes.reserve(plane_words((int)nt, n) * 8) || set[1].live.reserve(nt * 8) ||
             set[1].fmap.reserve(nt * 64 * sizeof(int32_t)) || set[0].fmap.reserve(nt * 64 * sizeof(int32_t)) ||
             d->rbase.reserve(((size_t)tiles + 1) * sizeof(int32_t)) || d->rmap.reserve(nt * 64 * sizeof(int32_t)))
             repack.on = false;  // no room for a second set: decode without repacking
     }
     // the repack folded into the sweep behind it (k_repack_map + GATHER passes) where those passes are built; LDPC_STREAM_REPACK_FOLD=0: the
     // separate copy kernel (k_repack), kept for the degrees beyond and as the A/B reference
-    const bool fold_repack = gather_passes_built(c) && env_int("LDPC_STREAM_REPACK_FOLD", 1) != 0;
+    // (the layered decoder has no GATHER passes: its repack is the copy kernel, without the priors)
+    const bool fold_repack = !LAYERED && gather_passes_built(c) && env_int("LDPC_STREAM_REPACK_FOLD", 1) != 0;
     int cur = 0;  // which set holds the state; the pointers below are re-read from it after a flip
     T *msg, *marg, *prior;
     u64 *xbits, *live;
@@ -821,13 +964,13 @@ int run(Decoder* d, const DecodeCall& k, const SimSource* sim = nullptr) {
     LDPC_HIP_TRY(hipMemsetAsync(xbits, 0, plane_words(tiles, n) * 8, st));
     LDPC_HIP_TRY(hipMemsetAsync(tflags, 0, (size_t)tiles * 16 + 64 + POLL_RING * 16, st));
     LDPC_HIP_TRY(hipMemsetAsync(iters, 0, (size_t)B * sizeof(int32_t), st));
-    if (k.soft) LDPC_HIP_TRY(hipMemsetAsync(marg, 0, (size_t)tiles * n * 64 * sizeof(T), st));  // frames that never sweep report 0
+    if (k.soft && !LAYERED) LDPC_HIP_TRY(hipMemsetAsync(marg, 0, (size_t)tiles * n * 64 * sizeof(T), st));  // frames that never sweep report 0
     if (sim) {  // device Monte-Carlo over BI-AWGN: the noise goes straight into the tile layout
         const int bpf = (n + 3) / 4, bpw = 16;
-        hipLaunchKernelGGL((k_biawgn_tile<T>), dim3(((bpf + bpw - 1) / bpw + 3) / 4, tiles), dim3(64, 4), 0, st, *sim, B, n, bpf, bpw, prior);
+        hipLaunchKernelGGL((k_biawgn_tile<T>), dim3(((bpf + bpw - 1) / bpw + 3) / 4, tiles), dim3(64, 4), 0, st, *sim, B, n, bpf, bpw, LAYERED ? marg : prior);
     }
     if (!sim)
-        hipLaunchKernelGGL((k_load_tile<T>), dim3((n + 63) / 64, tiles), dim3(256), 0, st, (const T*)k.priors, y0, B, n, prior, xbits);
+        hipLaunchKernelGGL((k_load_tile<T>), dim3((n + 63) / 64, tiles), dim3(256), 0, st, (const T*)k.priors, y0, B, n, LAYERED ? marg : prior, xbits);
     if constexpr (ALG == ALG_QMSA) launch_quantise<T>(d, prior, (int64_t)tiles * n * 64, st);  // priors -> levels, in the workspace
     hipLaunchKernelGGL(k_init_live, dim3((tiles + 255) / 256), dim3(256), 0, st, live, B, tiles);
 
@@ -893,7 +1036,7 @@ int run(Decoder* d, const DecodeCall& k, const SimSource* sim = nullptr) {
                         } else {
                             const int rows_per_wave = 128;
                             const int chunks = (int)((E + n + rows_per_wave - 1) / rows_per_wave);
-                            hipLaunchKernelGGL((k_repack<T>), dim3((chunks + 3) / 4, nt), dim3(64, 4), 0, st, msg, (T*)to.edge.p, marg, (T*)to.node.p, prior,
+                            hipLaunchKernelGGL((k_repack<T, !LAYERED>), dim3((chunks + 3) / 4, nt), dim3(64, 4), 0, st, msg, (T*)to.edge.p, marg, (T*)to.node.p, prior,
                                                (T*)to.prior.p, xbits, (u64*)to.planes.p, live, (u64*)to.live.p, (const int32_t*)d->rbase.p, fmap,
                                                (int32_t*)to.fmap.p, cur_tiles, n, E, rows_per_wave);
                         }
@@ -909,7 +1052,11 @@ int run(Decoder* d, const DecodeCall& k, const SimSource* sim = nullptr) {
             }
         }
         LDPC_TRY(prof.mark(0));
-        if (gather_msg) {  // the sweep that carries a repack: state read from the old set through the map, written densely into the new one
+        if constexpr (LAYERED) {
+            dispatch_layers<T>(d, msg, marg, live, g, it == 0, st);
+            LDPC_TRY(prof.mark(1));
+            dispatch_decide<T>(c, marg, live, xbits, g, st);
+        } else if (gather_msg) {  // the sweep that carries a repack: state read from the old set through the map, written densely into the new one
             // (never the first sweep, never a soft-output decode: first == 0 and g.freeze == 0)
             dispatch_cn<T, ALG, true>(c, msg, gather_marg, live, g, 0, st, gather_msg, (const int32_t*)d->rmap.p);
             LDPC_TRY(prof.mark(1));
@@ -924,7 +1071,8 @@ int run(Decoder* d, const DecodeCall& k, const SimSource* sim = nullptr) {
         ++sweeps;
     }
     launch_decisions(k, xbits, live, n, cur_tiles, sweeps, fmap);
-    if (k.soft) hipLaunchKernelGGL(k_soft_out<T>, dim3((n + 3) / 4, tiles), dim3(256), 0, st, marg, (T*)k.soft, B, n);
+    if (k.soft && LAYERED) hipLaunchKernelGGL(k_soft_out_swept<T>, dim3((n + 3) / 4, tiles), dim3(256), 0, st, marg, (const int32_t*)iters, (T*)k.soft, B, n);
+    if (k.soft && !LAYERED) hipLaunchKernelGGL(k_soft_out<T>, dim3((n + 3) / 4, tiles), dim3(256), 0, st, marg, (T*)k.soft, B, n);
     // polls still in flight copy into the pinned ring; the next decode of this handle may run on another stream and reuse the slots:
     // let the last copy land first (everything of this decode is enqueued by now, the GPU is not waiting for the host)
     if (!pending.empty()) LDPC_HIP_TRY(hipEventSynchronize(poll_ev[pending.back().slot]));
@@ -1368,6 +1516,7 @@ bool batch_fits(int64_t B) {
 template <typename T>
 int run_alg(Decoder* d, const DecodeCall& k, const SimSource* sim) {
     if (d->alg == ALG_NMSA) return run<T, ALG_NMSA>(d, k, sim);
+    if (d->alg == ALG_LMSA) return run<T, ALG_LMSA>(d, k, sim);
     if (d->alg == ALG_QMSA) return run<T, ALG_QMSA>(d, k, sim);
     return d->alg == ALG_MSA ? run<T, ALG_MSA>(d, k, sim) : run<T, ALG_SPA>(d, k, sim);
 }

@@ -33,23 +33,27 @@ def test(args, comm=None):
     # --codeword -1 (a random codeword per frame, src/main.py:38): on the device for the BP decoders -- from the code book where the code
     # has one, from the systematic GF(2) encoder (Code.encoder()) otherwise -- and for ML over the BEC of a code without a code book (the
     # elimination decoder, encoder words); the reference's sequential loop on host noise for the others
-    device_words = args.decoder in ("SPA", "MSA", "NMSA", "QMSA", "OSD") or (args.channel == "bec" and args.decoder == "ML" and code.gen_mtx is None)
+    device_words = args.decoder in ("SPA", "MSA", "NMSA", "QMSA", "LMSA", "OSD") or (args.channel == "bec" and args.decoder == "ML" and code.gen_mtx is None)
     exact = bool(args.exact) or (args.codeword == -1 and not device_words)
     if exact and comm.world > 1:
         raise SystemExit("--exact / --codeword -1 follow the reference's sequential rule and run on a single rank")
     if exact and args.np_seed is not None:
         np.random.seed(args.np_seed)
     kwargs = dict(vars(args))
+    if args.decoder in ("LMSA", "OSD"):
+        kwargs.pop("layers", None)  # (--layers is ADMMA's network shape, src/utils.py:43: not a layering of the checks; LMSA takes the greedy one)
     # fp32 message arithmetic in the throughput mode -- except min-sum over the BSC: every LLR is +-L there, the decoder is
     # tie-dominated and only the reference's fp64 arithmetic reproduces its curves
     # (fixed-point min-sum is no exception: its integers are the same in every arithmetic)
-    tie_dominated = args.channel == "bsc" and args.decoder in ("MSA", "NMSA", "OSD")  # (OSD: NMSA in front)
+    tie_dominated = args.channel == "bsc" and args.decoder in ("MSA", "NMSA", "LMSA", "OSD")  # (OSD: NMSA in front)
     kwargs["precision"] = args.precision or ("f64" if (exact or tie_dominated) else "f32")
     # (OSD orders the soft output of an f32 / f64 decoder: fp16 storage keeps none in the decoder's type)
     if kwargs["precision"] == "f16" and (args.decoder not in ("SPA", "MSA", "NMSA", "QMSA") or args.channel == "bec" or exact):
         raise SystemExit("--precision f16 (fp16 storage of the messages): the LLR decoders SPA / MSA over biawgn / bsc, device-noise mode")
+    if args.decoder == "LMSA" and args.backend == "fused":  # (refused before a decoder exists, like the two around it)
+        raise SystemExit("--backend fused: layered min-sum (LMSA) runs on the streaming kernels (--backend auto / stream)")
     # (NMSA, and OSD with NMSA in front: a scale takes values off the grid; QMSA quantises its priors itself; refused before a decoder exists)
-    if getattr(args, "prior_grid", None) is not None and args.decoder in ("NMSA", "QMSA", "OSD"):
+    if getattr(args, "prior_grid", None) is not None and args.decoder in ("NMSA", "QMSA", "LMSA", "OSD"):
         raise SystemExit("--prior-grid: fp32 min-sum over BI-AWGN (biawgn <code> MSA, without --precision f64)")
     results = OrderedDict()
 
@@ -127,9 +131,9 @@ def test(args, comm=None):
 
 def build_parser():
     """The reference's grammar with the reference's decoder names, plus this build's own (``models.extra_decoder_names``: NMSA,
-    ``models.fixed_point_decoder_names``: QMSA, ``models.post_processing_decoder_names``: OSD)."""
+    ``models.fixed_point_decoder_names``: QMSA, ``models.layered_decoder_names``: LMSA, ``models.post_processing_decoder_names``: OSD)."""
     return utils.setup_parser(codes.get_code_names(), models.keys(), utils.decoder_names + utils.extra_decoder_names + utils.fixed_point_decoder_names +
-                              utils.post_processing_decoder_names)
+                              utils.layered_decoder_names + utils.post_processing_decoder_names)
 
 
 def main(argv=None):

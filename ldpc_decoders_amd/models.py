@@ -9,6 +9,7 @@ from . import bec, biawgn, bsc
 decoder_names = ["ML", "SPA", "MSA", "LP", "ADMM", "ADMMA"]  # src/utils.py:16
 extra_decoder_names = ["NMSA"]  # this build's own decoders (no upstream counterpart): corrected min-sum, bpa.NMSA
 fixed_point_decoder_names = ["QMSA"]  # likewise: fixed-point min-sum (q-bit saturating messages), bpa.QMSA
+layered_decoder_names = ["LMSA"]  # likewise: layered (serial-C) corrected min-sum on the streaming kernels, bpa.LMSA
 post_processing_decoder_names = ["OSD"]  # likewise: BP + ordered-statistics decoding of the frames BP fails on, bpa.OSD
 
 

@@ -1,7 +1,7 @@
 """CLI flags, logging and the JSON result store -- mirror of the reference's ``src/utils.py:21-68,118-140``.
 
 The argument grammar (positional ``channel code decoder`` + ``--codeword --min-wec --params --max-iter ...``) and
-the result files (``<channel>-<code>-<decoder>-<codeword>-<min_wec>-<max_iter>.json``; NMSA: ``...-<max_iter>-<msa_scale>-<msa_offset>.json``; QMSA: ``...-<max_iter>-<msa_bits>-<msa_frac_bits>-<msa_scale>-<msa_offset>.json``; OSD: ``...-<max_iter>-<msa_scale>-<msa_offset>-<osd_order>-<osd_depth>.json``; with the id keys first, then
+the result files (``<channel>-<code>-<decoder>-<codeword>-<min_wec>-<max_iter>.json``; NMSA, LMSA: ``...-<max_iter>-<msa_scale>-<msa_offset>.json``; QMSA: ``...-<max_iter>-<msa_bits>-<msa_frac_bits>-<msa_scale>-<msa_offset>.json``; OSD: ``...-<max_iter>-<msa_scale>-<msa_offset>-<osd_order>-<osd_depth>.json``; with the id keys first, then
 ``tot wec wer bec ber`` as ``{str(param): value}``) are what ``simulations.py`` / ``run_sims.sh`` emit and what
 ``graph.py`` reads upstream (src/graph.py:25-58), so flag names, defaults and the file layout are kept; the help texts are
 this build's own.  ``--mu --eps --allow-pseudo`` configure the ADMM decoder; ``--layers --train --apprx`` belong to ADMMA, which
@@ -14,7 +14,7 @@ import os
 from collections import OrderedDict
 
 from . import codes
-from .models import decoder_names, extra_decoder_names, fixed_point_decoder_names, post_processing_decoder_names  # noqa: F401  (re-exported like upstream utils.decoder_names)
+from .models import decoder_names, extra_decoder_names, fixed_point_decoder_names, layered_decoder_names, post_processing_decoder_names  # noqa: F401  (re-exported like upstream utils.decoder_names)
 
 strl = lambda ll: (str(it_) for it_ in ll)  # noqa: E731
 
@@ -67,10 +67,10 @@ def setup_parser(code_names, channel_names, decoder_names):
                         "guard; the few frames beyond it are decoded again in fp64 -- every counted frame is what the fp64 reference returns "
                         "for those priors")
     g.add_argument("--msa-scale", type=float, default=0.8125,
-                   help="NMSA (corrected min-sum): every check message is multiplied by this, 0 < scale <= 1 (1 = plain min-sum); "
+                   help="NMSA, LMSA (corrected min-sum, flooding / layered): every check message is multiplied by this, 0 < scale <= 1 (1 = plain min-sum); "
                         "QMSA (fixed-point min-sum): likewise, a multiple of 1/64")
     g.add_argument("--msa-offset", type=float, default=0.0,
-                   help="NMSA (corrected min-sum): subtracted from every check-message magnitude, clamped at 0 (offset >= 0); "
+                   help="NMSA, LMSA (corrected min-sum, flooding / layered): subtracted from every check-message magnitude, clamped at 0 (offset >= 0); "
                         "QMSA (fixed-point min-sum): likewise, an integer number of levels")
     g.add_argument("--msa-bits", type=int, default=6,
                    help="QMSA (fixed-point min-sum): word length q of the channel values and messages, 2..12; they saturate at +-(2^(q-1) - 1) levels")
