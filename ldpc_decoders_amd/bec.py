@@ -5,7 +5,7 @@ the stopping-set exit of src/bec.py:120; symbols are {0, 1, 2 = erased}.
 """
 import numpy as np
 
-from . import admm
+from . import admm, registry
 from ._device import DecoderHandle, as_code
 
 
@@ -51,40 +51,7 @@ class MSA(SPA):
     pass
 
 
-class NMSA:
-    """Corrected min-sum has no meaning over the erasure channel: the ternary decoder has no magnitudes to scale or offset."""
-    id_keys = ["max_iter", "msa_scale", "msa_offset"]
-
-    def __init__(self, *a, **k):
-        raise NotImplementedError("decoder NMSA (corrected min-sum) does not exist over the bec: the erasure decoder has no magnitudes "
-                                  "to correct; use SPA / MSA there")
-
-
-class LMSA:
-    """Layered min-sum is corrected min-sum on another schedule: it has no meaning over the erasure channel either."""
-    id_keys = ["max_iter", "msa_scale", "msa_offset"]
-
-    def __init__(self, *a, **k):
-        raise NotImplementedError("decoder LMSA (layered corrected min-sum) does not exist over the bec: the erasure decoder has no "
-                                  "magnitudes to correct; use SPA / MSA there")
-
-
-class QMSA:
-    """Fixed-point min-sum has no meaning over the erasure channel either: the ternary decoder has no magnitudes to quantise."""
-    id_keys = ["max_iter", "msa_bits", "msa_frac_bits", "msa_scale", "msa_offset"]
-
-    def __init__(self, *a, **k):
-        raise NotImplementedError("decoder QMSA (fixed-point min-sum) does not exist over the bec: the erasure decoder has no magnitudes "
-                                  "to quantise; use SPA / MSA there")
-
-
-class OSD:
-    """Ordered-statistics post-processing orders soft values; over the erasure channel ``ML`` (elimination of the erased bits) is exact."""
-    id_keys = ["max_iter", "msa_scale", "msa_offset", "osd_order", "osd_depth"]
-
-    def __init__(self, *a, **k):
-        raise NotImplementedError("decoder OSD (BP + ordered-statistics post-processing) does not exist over the bec: use ML there, the "
-                                  "elimination decoder is exact")
+registry.add_bec_refusals(globals())  # NMSA, LMSA, QMSA, OSD: NotImplementedError, the sentence is the registry's
 
 
 class ADMM:  # src/bec.py:38-45,58-62: LLR wrapper with +-1e8 for the known symbols, 0 for an erasure

@@ -1,7 +1,7 @@
 """BI-AWGN channel and its LLR decoders -- mirror of the reference's ``src/biawgn.py:10-42``."""
 import numpy as np
 
-from . import admm, bpa
+from . import admm, registry
 
 noise_var = lambda snr_in_db: 10 ** (-snr_in_db / 10)  # noqa: E731  (src/biawgn.py:10)
 
@@ -33,48 +33,6 @@ class LLR:
         return self.dec.decode_batch(None if hasattr(y, "is_cuda") else y, self.priors(y))
 
 
-class SPA(LLR):
-    id_keys = bpa.SPA.id_keys
-
-    def __init__(self, snr_in_db, _code, **kwargs):
-        super().__init__(snr_in_db, bpa.SPA(_code, **kwargs))
-
-
-class MSA(LLR):
-    id_keys = bpa.MSA.id_keys
-
-    def __init__(self, snr_in_db, _code, **kwargs):
-        super().__init__(snr_in_db, bpa.MSA(_code, **kwargs))
-
-
-class NMSA(LLR):  # corrected (normalised / offset) min-sum: no upstream counterpart, wrapped like MSA
-    id_keys = bpa.NMSA.id_keys
-
-    def __init__(self, snr_in_db, _code, **kwargs):
-        super().__init__(snr_in_db, bpa.NMSA(_code, **kwargs))
-
-
-class LMSA(LLR):  # layered corrected min-sum on the streaming kernels: no upstream counterpart, wrapped like NMSA
-    id_keys = bpa.LMSA.id_keys
-
-    def __init__(self, snr_in_db, _code, **kwargs):
-        super().__init__(snr_in_db, bpa.LMSA(_code, **kwargs))
-
-
-class QMSA(LLR):  # fixed-point min-sum (q-bit saturating messages): no upstream counterpart, wrapped like MSA
-    id_keys = bpa.QMSA.id_keys
-
-    def __init__(self, snr_in_db, _code, **kwargs):
-        super().__init__(snr_in_db, bpa.QMSA(_code, **kwargs))
-
-
-class OSD(LLR):  # BP + ordered-statistics post-processing: no upstream counterpart, wrapped like NMSA
-    id_keys = bpa.OSD.id_keys
-
-    def __init__(self, snr_in_db, _code, **kwargs):
-        super().__init__(snr_in_db, bpa.OSD(_code, **kwargs))
-
-
 class ADMM(LLR):  # src/biawgn.py:52-56
     id_keys = admm.ADMM.id_keys
 
@@ -85,5 +43,7 @@ class ADMM(LLR):  # src/biawgn.py:52-56
     def decode_batch(self, y):
         return self.dec.decode_batch(self.priors(np.asarray(y)))
 
+
+registry.add_llr_wrappers(globals(), LLR)  # SPA, MSA and this build's own (NMSA, QMSA, LMSA, OSD): LLR around the bpa class of that name
 
 from .ml import BiawgnML as ML  # noqa: E402  (src/biawgn.py: class ML)

@@ -187,9 +187,11 @@ class OSD:
         if self.osd_order not in (0, 1) or self.osd_depth < 0:
             raise ValueError("osd_order must be 0 or 1 and osd_depth >= 0 (got %r, %r)" % (order, depth))
         self.osd_bp = kwargs.get("osd_bp") or "NMSA"
-        front = {"MSA": MSA, "SPA": SPA, "NMSA": NMSA, "QMSA": QMSA, "LMSA": LMSA}.get(self.osd_bp)
+        from .registry import osd_fronts  # (here: the registry imports this module)
+
+        front = osd_fronts().get(self.osd_bp)
         if front is None:
-            raise ValueError("osd_bp must be one of MSA, SPA, NMSA, QMSA, LMSA (got %r)" % (self.osd_bp,))
+            raise ValueError("osd_bp must be one of %s (got %r)" % (", ".join(osd_fronts()), self.osd_bp))
         self.precision = kwargs.get("precision") or "f64"
         if self.precision not in ("f32", "f64"):
             raise ValueError("ordered-statistics post-processing needs the soft output of an f32 or f64 decoder (got precision %r)" % self.precision)

@@ -1,7 +1,7 @@
 """Binary symmetric channel and its LLR decoders -- mirror of the reference's ``src/bsc.py:11-39``."""
 import numpy as np
 
-from . import admm, bpa
+from . import admm, registry
 
 
 class Channel:
@@ -35,48 +35,6 @@ class LLR:
         return self.dec.decode_batch(y, self.priors(np.asarray(y)))
 
 
-class SPA(LLR):
-    id_keys = bpa.SPA.id_keys
-
-    def __init__(self, p, _code, **kwargs):
-        super().__init__(p, bpa.SPA(_code, **kwargs))
-
-
-class MSA(LLR):
-    id_keys = bpa.MSA.id_keys
-
-    def __init__(self, p, _code, **kwargs):
-        super().__init__(p, bpa.MSA(_code, **kwargs))
-
-
-class NMSA(LLR):  # corrected (normalised / offset) min-sum: no upstream counterpart, wrapped like MSA
-    id_keys = bpa.NMSA.id_keys
-
-    def __init__(self, p, _code, **kwargs):
-        super().__init__(p, bpa.NMSA(_code, **kwargs))
-
-
-class LMSA(LLR):  # layered corrected min-sum on the streaming kernels: no upstream counterpart, wrapped like NMSA
-    id_keys = bpa.LMSA.id_keys
-
-    def __init__(self, p, _code, **kwargs):
-        super().__init__(p, bpa.LMSA(_code, **kwargs))
-
-
-class QMSA(LLR):  # fixed-point min-sum (q-bit saturating messages): no upstream counterpart, wrapped like MSA
-    id_keys = bpa.QMSA.id_keys
-
-    def __init__(self, p, _code, **kwargs):
-        super().__init__(p, bpa.QMSA(_code, **kwargs))
-
-
-class OSD(LLR):  # BP + ordered-statistics post-processing: no upstream counterpart, wrapped like NMSA
-    id_keys = bpa.OSD.id_keys
-
-    def __init__(self, p, _code, **kwargs):
-        super().__init__(p, bpa.OSD(_code, **kwargs))
-
-
 class ADMM(LLR):  # src/bsc.py:49-53
     id_keys = admm.ADMM.id_keys
 
@@ -87,5 +45,7 @@ class ADMM(LLR):  # src/bsc.py:49-53
     def decode_batch(self, y):
         return self.dec.decode_batch(self.priors(np.asarray(y)))
 
+
+registry.add_llr_wrappers(globals(), LLR)  # SPA, MSA and this build's own (NMSA, QMSA, LMSA, OSD): LLR around the bpa class of that name
 
 from .ml import BscML as ML  # noqa: E402  (src/bsc.py: class ML)

@@ -140,28 +140,6 @@ static void release_stream_workspaces(Decoder* d) {
 // frames of the next chunk of a walk over B frames in chunks of `step`
 inline int64_t chunk_at(int64_t b0, int64_t B, int64_t step) { return (B - b0) < step ? (B - b0) : step; }
 
-// LDPC_FLAG_PRIOR_GRID arms the exactness guard of the LDS-resident fp32 min-sum kernels.  The streaming kernels have no such guard:
-// a call that asks for it there is refused (as ldpc_simulate refuses it) instead of returning frames nobody vouched for.  fp64 decoders
-// need no guard (their arithmetic IS the reference's), the flag is then a no-op.
-int grid_guard_available(const Decoder* d, int bk, uint32_t flags, const char* who) {
-    if (LDPC_FLAG_PRIOR_GRID_OF(flags) >= 0 && d->alg == ALG_NMSA) {  // in any arithmetic, on every backend
-        set_error("%s: prior grid: corrected min-sum (LDPC_ALG_NMSA) has no exact-in-fp32 mode (a scale takes values off the grid)", who);
-        return LDPC_E_UNSUPPORTED;
-    }
-    if (LDPC_FLAG_PRIOR_GRID_OF(flags) >= 0 && d->alg == ALG_QMSA) {  // likewise
-        set_error("%s: prior grid: fixed-point min-sum (LDPC_ALG_QMSA) quantises its priors itself (ldpc_decoder_set_fixed_point)", who);
-        return LDPC_E_UNSUPPORTED;
-    }
-    if (LDPC_FLAG_PRIOR_GRID_OF(flags) >= 0 && d->alg == ALG_LMSA) {  // likewise
-        set_error("%s: prior grid: layered min-sum (LDPC_ALG_LMSA) has no exact-in-fp32 mode (a scale takes values off the grid)", who);
-        return LDPC_E_UNSUPPORTED;
-    }
-    if (LDPC_FLAG_PRIOR_GRID_OF(flags) < 0 || d->dtype == DT_F64) return LDPC_OK;
-    if (bk == BK_FUSED && d->alg == ALG_MSA) return LDPC_OK;
-    set_error("%s: prior grid: the exactness guard lives in the LDS-resident fp32 min-sum kernels; this decoder runs on the streaming kernels", who);
-    return LDPC_E_UNSUPPORTED;
-}
-
 int pick_backend(Decoder* d) {
     if (d->backend == BK_STREAM) return BK_STREAM;
     if (fused_supported(d)) return BK_FUSED;
@@ -194,6 +172,50 @@ int install_layers(Decoder* d, const int32_t* layer_of_check) {
     return LDPC_OK;
 }
 }  // namespace
+
+// LDPC_FLAG_PRIOR_GRID arms the exactness guard of the LDS-resident fp32 min-sum kernels.  The streaming kernels have no such guard:
+// a call that asks for it there is refused (as ldpc_simulate refuses it) instead of returning frames nobody vouched for.  fp64 decoders
+// need no guard (their arithmetic IS the reference's), the flag is then a no-op.
+// THE refusal: every entry point that takes the flag comes through here.  `who` (null: none) names it in the message.  bk == BK_AUTO: the
+// caller routes by itself (ldpc_simulate, the launch of the LDS-resident kernels) and asks only whether the algorithm refuses the flag.
+int grid_guard_available(const Decoder* d, int bk, uint32_t flags, const char* who) {
+    if (LDPC_FLAG_PRIOR_GRID_OF(flags) < 0) return LDPC_OK;
+    const std::string pre = who ? std::string(who) + ": " : std::string();
+    const AlgRow& a = alg_row(d->alg);
+    if (a.no_grid) {  // in any arithmetic, on every backend
+        set_error("%sprior grid: %s (%s) %s", pre.c_str(), a.words, a.name, a.no_grid);
+        return LDPC_E_UNSUPPORTED;
+    }
+    if (bk == BK_AUTO || d->dtype == DT_F64) return LDPC_OK;
+    if (bk == BK_FUSED && d->alg == ALG_MSA) return LDPC_OK;
+    set_error("%sprior grid: the exactness guard lives in the LDS-resident fp32 min-sum kernels; this decoder runs on the streaming kernels", pre.c_str());
+    return LDPC_E_UNSUPPORTED;
+}
+
+int rule_params(const Decoder* d, RuleParams* out) {
+    RuleParams r;
+    r.scale = d->corr_scale;
+    r.offset = d->corr_offset;
+    if (alg_row(d->alg).fixed_point) {
+        r.scale = d->fx_scale;
+        r.offset = d->fx_offset > 4096 ? 4096.0 : (double)d->fx_offset;
+        r.vmax = (double)((1 << (d->fx_bits - 1)) - 1);
+        r.step = d->fx_frac >= 0 ? (double)(1 << d->fx_frac) : 1.0 / (double)(1 << -d->fx_frac);
+        r.cap = std::max((double)(long long)(r.scale * r.vmax) - r.offset, 0.0);
+        // the LDS-resident kernels take the five as fp32 words, or as the high words of doubles whose low words are zero
+        const double fx[5] = {r.scale, r.offset, r.cap, r.step, r.vmax};
+        for (int i = 0; i < 5; ++i) {
+            uint64_t w64;
+            std::memcpy(&w64, &fx[i], 8);
+            if ((double)(float)fx[i] != fx[i] || (uint32_t)w64 != 0u) {
+                set_error("fixed-point min-sum: constant %d (%g) is not exact in fp32", i, fx[i]);
+                return LDPC_E_ARG;
+            }
+        }
+    }
+    *out = r;
+    return LDPC_OK;
+}
 
 int layering_build(const Code* c, const int32_t* layer_of_check, std::vector<int32_t>* of_check, std::vector<int32_t>* sorted,
                    std::vector<int32_t>* start) {
@@ -376,7 +398,7 @@ int ldpc_code_info(ldpc_code_t h, int32_t* m, int32_t* n, int64_t* E, int32_t* m
 int ldpc_plan_layout(int32_t m, int32_t n, int64_t E, const int32_t* chk, const int32_t* var, int alg, int dtype, int64_t moves,
                      const char* out_dir, double* info4) {
     return guarded("ldpc_plan_layout", [&]() -> int {
-        if (!info4 || alg < 0 || alg > ALG_QMSA || dtype < 0 || dtype > 1) {
+        if (!info4 || !alg_known(alg) || !alg_row(alg).lds || dtype < 0 || dtype > 1) {
             set_error("ldpc_plan_layout: bad arguments (alg=%d dtype=%d)", alg, dtype);
             return LDPC_E_ARG;
         }
@@ -388,14 +410,16 @@ int ldpc_plan_layout(int32_t m, int32_t n, int64_t E, const int32_t* chk, const 
 
 int ldpc_decoder_create(ldpc_code_t code, int alg, int dtype, int backend, ldpc_decoder_t* out) {
     return guarded("ldpc_decoder_create", [&]() -> int {
-        if (!code || !out || alg < 0 || alg > ALG_LMSA || dtype < 0 || dtype > 2 ||
-            (alg != ALG_LMSA && dtype == DT_F16 && (alg == ALG_BEC || backend == BK_FUSED)) || backend < 0 || backend > 2) {
+        // fp16 storage is the streaming kernels', for the algorithms that have it
+        const bool f16_refused = alg_known(alg) && dtype == DT_F16 && (!alg_row(alg).f16 || backend == BK_FUSED);
+        if (!code || !out || !alg_known(alg) || dtype < 0 || dtype > 2 || (f16_refused && !alg_row(alg).layered) || backend < 0 || backend > 2) {
             set_error("ldpc_decoder_create: bad arguments (alg=%d dtype=%d backend=%d)", alg, dtype, backend);
             return LDPC_E_ARG;
         }
-        if (alg == ALG_LMSA && (dtype == DT_F16 || backend == BK_FUSED || ((Code*)code)->min_dc < 2)) {
-            set_error("ldpc_decoder_create: layered min-sum (LDPC_ALG_LMSA) runs on the streaming kernels in fp32 or fp64, on codes whose checks "
-                      "all have degree >= 2 (dtype=%d backend=%d smallest check degree=%d)", dtype, backend, ((Code*)code)->min_dc);
+        const AlgRow& a = alg_row(alg);
+        if (a.layered && (f16_refused || (backend == BK_FUSED && !a.lds) || ((Code*)code)->min_dc < 2)) {
+            set_error("ldpc_decoder_create: %s (%s) runs on the streaming kernels in fp32 or fp64, on codes whose checks "
+                      "all have degree >= 2 (dtype=%d backend=%d smallest check degree=%d)", a.words, a.name, dtype, backend, ((Code*)code)->min_dc);
             return LDPC_E_UNSUPPORTED;
         }
         Decoder* d = new (std::nothrow) Decoder();
@@ -427,7 +451,7 @@ int ldpc_decoder_create(ldpc_code_t code, int alg, int dtype, int backend, ldpc_
             ldpc_decoder_destroy((ldpc_decoder_t)d);
             return LDPC_E_UNSUPPORTED;
         }
-        if (alg == ALG_LMSA) {
+        if (a.layered) {
             try {
                 rc = install_layers(d, nullptr);  // greedy
             } catch (...) {
@@ -464,8 +488,8 @@ int ldpc_decoder_destroy(ldpc_decoder_t h) {
 int ldpc_decoder_set_correction(ldpc_decoder_t h, double scale, double offset) {
     return guarded("ldpc_decoder_set_correction", [&]() -> int {
         Decoder* d = (Decoder*)h;
-        if (!d || (d->alg != ALG_NMSA && d->alg != ALG_LMSA)) {
-            set_error("ldpc_decoder_set_correction: a corrected min-sum decoder (LDPC_ALG_NMSA, LDPC_ALG_LMSA) is needed");
+        if (!d || !alg_row(d->alg).corrected) {
+            set_error("ldpc_decoder_set_correction: a corrected min-sum decoder (%s) is needed", alg_names(&AlgRow::corrected).c_str());
             return LDPC_E_ARG;
         }
         // (written so that a NaN fails every test)
@@ -482,8 +506,8 @@ int ldpc_decoder_set_correction(ldpc_decoder_t h, double scale, double offset) {
 int ldpc_decoder_get_correction(ldpc_decoder_t h, double* scale, double* offset) {
     return guarded("ldpc_decoder_get_correction", [&]() -> int {
         Decoder* d = (Decoder*)h;
-        if (!d || !scale || !offset || (d->alg != ALG_NMSA && d->alg != ALG_LMSA)) {
-            set_error("ldpc_decoder_get_correction: a corrected min-sum decoder (LDPC_ALG_NMSA, LDPC_ALG_LMSA) and two result pointers are needed");
+        if (!d || !scale || !offset || !alg_row(d->alg).corrected) {
+            set_error("ldpc_decoder_get_correction: a corrected min-sum decoder (%s) and two result pointers are needed", alg_names(&AlgRow::corrected).c_str());
             return LDPC_E_ARG;
         }
         *scale = d->corr_scale;
@@ -495,8 +519,8 @@ int ldpc_decoder_get_correction(ldpc_decoder_t h, double* scale, double* offset)
 int ldpc_decoder_set_fixed_point(ldpc_decoder_t h, int bits, int frac_bits, double scale, int offset) {
     return guarded("ldpc_decoder_set_fixed_point", [&]() -> int {
         Decoder* d = (Decoder*)h;
-        if (!d || d->alg != ALG_QMSA) {
-            set_error("ldpc_decoder_set_fixed_point: a fixed-point min-sum decoder (LDPC_ALG_QMSA) is needed");
+        if (!d || !alg_row(d->alg).fixed_point) {
+            set_error("ldpc_decoder_set_fixed_point: a fixed-point min-sum decoder (%s) is needed", alg_names(&AlgRow::fixed_point).c_str());
             return LDPC_E_ARG;
         }
         // (written so that a NaN scale fails; 64 * scale is exact, so the grid test is)
@@ -516,8 +540,8 @@ int ldpc_decoder_set_fixed_point(ldpc_decoder_t h, int bits, int frac_bits, doub
 int ldpc_decoder_get_fixed_point(ldpc_decoder_t h, int* bits, int* frac_bits, double* scale, int* offset) {
     return guarded("ldpc_decoder_get_fixed_point", [&]() -> int {
         Decoder* d = (Decoder*)h;
-        if (!d || !bits || !frac_bits || !scale || !offset || d->alg != ALG_QMSA) {
-            set_error("ldpc_decoder_get_fixed_point: a fixed-point min-sum decoder (LDPC_ALG_QMSA) and four result pointers are needed");
+        if (!d || !bits || !frac_bits || !scale || !offset || !alg_row(d->alg).fixed_point) {
+            set_error("ldpc_decoder_get_fixed_point: a fixed-point min-sum decoder (%s) and four result pointers are needed", alg_names(&AlgRow::fixed_point).c_str());
             return LDPC_E_ARG;
         }
         *bits = d->fx_bits;
@@ -531,8 +555,8 @@ int ldpc_decoder_get_fixed_point(ldpc_decoder_t h, int* bits, int* frac_bits, do
 int ldpc_decoder_set_layers(ldpc_decoder_t h, const int32_t* layer_of_check_host, int32_t m) {
     return guarded("ldpc_decoder_set_layers", [&]() -> int {
         Decoder* d = (Decoder*)h;
-        if (!d || d->alg != ALG_LMSA) {
-            set_error("ldpc_decoder_set_layers: a layered min-sum decoder (LDPC_ALG_LMSA) is needed");
+        if (!d || !alg_row(d->alg).layered) {
+            set_error("ldpc_decoder_set_layers: a layered min-sum decoder (%s) is needed", alg_names(&AlgRow::layered).c_str());
             return LDPC_E_ARG;
         }
         if (layer_of_check_host && m != d->code->m) {
@@ -546,8 +570,8 @@ int ldpc_decoder_set_layers(ldpc_decoder_t h, const int32_t* layer_of_check_host
 int ldpc_decoder_get_layers(ldpc_decoder_t h, int32_t* nlayers, int32_t* layer_of_check_host) {
     return guarded("ldpc_decoder_get_layers", [&]() -> int {
         Decoder* d = (Decoder*)h;
-        if (!d || !nlayers || d->alg != ALG_LMSA) {
-            set_error("ldpc_decoder_get_layers: a layered min-sum decoder (LDPC_ALG_LMSA) and a result pointer are needed");
+        if (!d || !nlayers || !alg_row(d->alg).layered) {
+            set_error("ldpc_decoder_get_layers: a layered min-sum decoder (%s) and a result pointer are needed", alg_names(&AlgRow::layered).c_str());
             return LDPC_E_ARG;
         }
         *nlayers = (int32_t)d->layer_start.size() - 1;
@@ -1057,22 +1081,13 @@ static int simulate_impl(ldpc_decoder_t h, int channel, double param, int codewo
         return LDPC_E_ARG;
     }
     const int grid_k = LDPC_FLAG_PRIOR_GRID_OF(flags);
-    if (grid_k >= 0 && d->alg == ALG_NMSA) {
-        set_error("ldpc_simulate: prior grid: corrected min-sum (LDPC_ALG_NMSA) has no exact-in-fp32 mode (a scale takes values off the grid)");
-        return LDPC_E_UNSUPPORTED;
-    }
-    if (grid_k >= 0 && d->alg == ALG_QMSA) {
-        set_error("ldpc_simulate: prior grid: fixed-point min-sum (LDPC_ALG_QMSA) quantises its priors itself (ldpc_decoder_set_fixed_point)");
-        return LDPC_E_UNSUPPORTED;
-    }
-    if (grid_k >= 0 && d->alg == ALG_LMSA) {
-        set_error("ldpc_simulate: prior grid: layered min-sum (LDPC_ALG_LMSA) has no exact-in-fp32 mode (a scale takes values off the grid)");
-        return LDPC_E_UNSUPPORTED;
-    }
+    LDPC_TRY(grid_guard_available(d, BK_AUTO, flags, "ldpc_simulate"));  // the algorithm's own refusal; the routing below has the rest
     // Fixed-point min-sum over a BSC whose LLR is (close to) less than half a level: every prior quantises to level 0 and no longer carries the
     // received bit, which the Monte-Carlo LDS kernels read off the prior's sign -- composed path below (the channel kernel hands y0 over)
+    RuleParams rule;
+    LDPC_TRY(rule_params(d, &rule));
     const bool level0_bsc = d->alg == ALG_QMSA && channel == CH_BSC && param > 0.0 && param < 1.0 &&
-                            std::fabs(std::log((1.0 - param) / param)) * d->fx_step() < 0.75;
+                            std::fabs(std::log((1.0 - param) / param)) * rule.step < 0.75;
     // (fp64 decoders with a prior grid take the composed path below: quantised priors from the channel kernel, no guard needed)
     if (d->backend != BK_STREAM && !level0_bsc && fused_simulate_supported(d, channel, param, hist_bins) &&
         !(grid_k >= 0 && d->dtype == DT_F64 && d->alg != ALG_BEC))

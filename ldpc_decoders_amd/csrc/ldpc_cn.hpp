@@ -135,7 +135,7 @@ struct last_int_arg {
     static __host__ __device__ __forceinline__ int value(int a) { return a; }
     static __host__ __device__ __forceinline__ Correction<T> correction(int) { return Correction<T>{T(1), T(0)}; }
     static __host__ __device__ __forceinline__ T cap(int) { return T(0); }
-    static __host__ __forceinline__ int make(int v, double, double, double = 0.0) { return v; }
+    static __host__ __forceinline__ int make(int v, const RuleParams&) { return v; }
 };
 template <typename T>
 struct last_int_arg<T, ALG_NMSA> {
@@ -143,7 +143,7 @@ struct last_int_arg<T, ALG_NMSA> {
     static __host__ __device__ __forceinline__ int value(const type& a) { return a.value; }
     static __host__ __device__ __forceinline__ Correction<T> correction(const type& a) { return Correction<T>{a.scale, a.offset}; }
     static __host__ __device__ __forceinline__ T cap(const type&) { return T(0); }
-    static __host__ __forceinline__ type make(int v, double scale, double offset, double = 0.0) { return type{v, (T)scale, (T)offset}; }
+    static __host__ __forceinline__ type make(int v, const RuleParams& r) { return type{v, (T)r.scale, (T)r.offset}; }
 };
 template <typename T>
 struct IntAndFixedPoint {
@@ -156,7 +156,7 @@ struct last_int_arg<T, ALG_QMSA> {
     static __host__ __device__ __forceinline__ int value(const type& a) { return a.value; }
     static __host__ __device__ __forceinline__ Correction<T> correction(const type& a) { return Correction<T>{a.scale, a.offset}; }
     static __host__ __device__ __forceinline__ T cap(const type& a) { return a.cap; }
-    static __host__ __forceinline__ type make(int v, double scale, double offset, double cap) { return type{v, (T)scale, (T)offset, (T)cap}; }
+    static __host__ __forceinline__ type make(int v, const RuleParams& r) { return type{v, (T)r.scale, (T)r.offset, (T)r.cap}; }
 };
 
 // ---- sum-product, fp64: the reference formula verbatim ---------------------------------------------

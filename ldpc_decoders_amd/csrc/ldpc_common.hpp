@@ -30,10 +30,45 @@ enum Alg : int {
     ALG_QMSA = 4,  // fixed-point min-sum: q-bit saturating messages on the integer grid (ldpc_cn.hpp cn_msa<.., MSA_FIXED>, quantise_prior)
     ALG_LMSA = 5   // layered (serial-C) corrected min-sum on the streaming kernels (ldpc_stream.hip k_layer; the rule is ALG_NMSA's)
 };
+// THE table of the algorithms, indexed by Alg: what the entry points, the dispatchers and the messages need to know about one.  A new variant
+// is one row here (plus its rule in ldpc_cn.hpp and its row in the Python registry, models.py).
+struct AlgRow {
+    const char* name;   // ABI name, as messages spell it
+    const char* words;  // the algorithm in words, as messages spell it
+    bool llr;           // decodes LLR priors (false: the erasure decoder, which decodes received symbols)
+    int family;         // whose variable pass, register tuning and table words it shares (alg_family)
+    bool corrected;     // carries Decoder::corr_scale / corr_offset (ldpc_decoder_set_correction)
+    bool fixed_point;   // carries Decoder::fx_* (ldpc_decoder_set_fixed_point)
+    bool layered;       // carries a layering (ldpc_decoder_set_layers); streaming kernels in fp32 / fp64 only
+    bool lds;           // LDS-resident shapes exist (fused backend, ldpc_plan_layout)
+    bool f16;           // fp16 storage of the streaming messages exists
+    const char* no_grid;  // why LDPC_FLAG_PRIOR_GRID is refused in any arithmetic on every backend; null: it is not
+};
+constexpr int ALG_COUNT = 6;
+constexpr AlgRow kAlgs[ALG_COUNT] = {
+    {"LDPC_ALG_MSA", "min-sum", true, ALG_MSA, false, false, false, true, true, nullptr},
+    {"LDPC_ALG_SPA", "sum-product", true, ALG_SPA, false, false, false, true, true, nullptr},
+    {"LDPC_ALG_BEC", "erasure decoder", false, ALG_BEC, false, false, false, true, false, nullptr},
+    {"LDPC_ALG_NMSA", "corrected min-sum", true, ALG_MSA, true, false, false, true, true,
+     "has no exact-in-fp32 mode (a scale takes values off the grid)"},
+    {"LDPC_ALG_QMSA", "fixed-point min-sum", true, ALG_MSA, false, true, false, true, true,
+     "quantises its priors itself (ldpc_decoder_set_fixed_point)"},
+    {"LDPC_ALG_LMSA", "layered min-sum", true, ALG_LMSA, true, false, true, false, false,
+     "has no exact-in-fp32 mode (a scale takes values off the grid)"},
+};
+constexpr bool alg_known(int alg) { return alg >= 0 && alg < ALG_COUNT; }
+constexpr const AlgRow& alg_row(int alg) { return kAlgs[alg]; }
 // min-sum family: everything that is keyed on "the rule is compare / negate only" (register tuning, sign-bit shortcuts, table words) treats
 // the corrected rule as min-sum
-constexpr bool alg_is_minsum(int alg) { return alg == ALG_MSA || alg == ALG_NMSA || alg == ALG_QMSA; }
-constexpr int alg_family(int alg) { return (alg == ALG_NMSA || alg == ALG_QMSA) ? (int)ALG_MSA : alg; }
+constexpr int alg_family(int alg) { return kAlgs[alg].family; }
+constexpr bool alg_is_minsum(int alg) { return alg_family(alg) == ALG_MSA; }
+// ABI names of the rows that have `flag` set, for messages: "LDPC_ALG_NMSA, LDPC_ALG_LMSA"
+inline std::string alg_names(bool AlgRow::*flag, const char* sep = ", ") {
+    std::string out;
+    for (const AlgRow& r : kAlgs)
+        if (r.*flag) out += (out.empty() ? "" : sep) + std::string(r.name);
+    return out;
+}
 enum DType : int { DT_F32 = 0, DT_F64 = 1, DT_F16 = 2 };  // DT_F16: fp16 STORAGE of the streaming messages, fp32 arithmetic and priors
 enum Backend : int { BK_AUTO = 0, BK_STREAM = 1, BK_FUSED = 2 };
 enum Channel : int { CH_BIAWGN = 0, CH_BSC = 1, CH_BEC = 2 };
@@ -130,13 +165,6 @@ struct Decoder {
     // c2v = sign * max(floor(fx_scale * min(m, V)) - fx_offset, 0)
     int fx_bits = 6, fx_frac = 2, fx_offset = 0;
     double fx_scale = 0.8125;
-    double fx_vmax() const { return (double)((1 << (fx_bits - 1)) - 1); }
-    double fx_offset_eff() const { return fx_offset > 4096 ? 4096.0 : (double)fx_offset; }  // beyond V <= 2047 every message is 0 already
-    double fx_cap() const {  // what a saturated minimum sends: max(floor(scale * V) - offset, 0)
-        const double c = (double)(long long)(fx_scale * fx_vmax()) - fx_offset_eff();
-        return c > 0.0 ? c : 0.0;
-    }
-    double fx_step() const { return fx_frac >= 0 ? (double)(1 << fx_frac) : 1.0 / (double)(1 << -fx_frac); }
     // ALG_LMSA (ldpc_decoder_set_layers; greedy at create): layer of every check as the caller numbered it; on the device the checks
     // sorted by (layer, index) -- the processing order -- and on the host where each layer begins in that list ([nlayers + 1])
     std::vector<int32_t> layer_of_check, layer_start;
@@ -183,6 +211,20 @@ struct Decoder {
     int chunk_retries = 0;  // how often decode_dev halved the streaming chunk after a failed reservation (ldpc_decoder_chunk_state)
     int64_t stream_chunk = 0;  // frames per pass through the streaming kernels (0: not decided yet; ldpc_api.hip stream_chunk_frames)
 };
+
+// The parameters of a decoder's check rule as a launch hands them to its kernels (the setters are read at every launch):
+//   corrected (ALG_NMSA, ALG_LMSA):  c2v = sign * max(scale * min - offset, 0); cap, step, vmax unused
+//   fixed point (ALG_QMSA):  step = 2^fx_frac (priors -> levels), vmax = V = 2^(fx_bits - 1) - 1, offset = min(fx_offset, 4096) (beyond V <= 2047
+//     every message is 0 already), cap = max(floor(scale * V) - offset, 0): what a saturated minimum sends
+// in this order the five are the FX_SCALE .. FX_VMAX words of the LDS-resident kernels.
+struct RuleParams {
+    double scale = 1.0, offset = 0.0, cap = 0.0, step = 1.0, vmax = 0.0;
+};
+// LDPC_E_ARG if a fixed-point constant were not exact in fp32 (cannot happen for values ldpc_decoder_set_fixed_point accepts)
+int rule_params(const Decoder* d, RuleParams* out);
+
+// LDPC_FLAG_PRIOR_GRID: may this call have it?  (ldpc_api.hip)
+int grid_guard_available(const Decoder* d, int bk, uint32_t flags, const char* who);
 
 // event-pair bookkeeping used when Decoder::profile is set
 struct ProfSpan {

@@ -66,10 +66,9 @@ int upload_vec(const std::vector<T>& h, T** d) {
 const std::vector<ShapeEntry>& all_shapes() {
     static const std::vector<ShapeEntry> v = [] {
         std::vector<ShapeEntry> out;
-        // (the corrected min-sum tables come last: the indices of the shapes that were there before them do not move)
-        for (auto fn : {fused_shapes_f32_dc6, fused_shapes_f32_dcx, fused_shapes_f64_dc6, fused_shapes_f64_dcx, fused_shapes_bec, fused_shapes_nmsa_f32_dc6,
-                        fused_shapes_nmsa_f32_dcx, fused_shapes_nmsa_f64_dc6, fused_shapes_nmsa_f64_dcx, fused_shapes_qmsa_f32_dc6,
-                        fused_shapes_qmsa_f32_dcx, fused_shapes_qmsa_f64_dc6, fused_shapes_qmsa_f64_dcx}) {
+#define LDPC_SHAPE_TABLE_FN(name) fused_shapes_##name,
+        for (auto fn : {LDPC_SHAPE_TABLES(LDPC_SHAPE_TABLE_FN)}) {
+#undef LDPC_SHAPE_TABLE_FN
             int cnt = 0;
             const ShapeEntry* p = fn(&cnt);
             out.insert(out.end(), p, p + cnt);
@@ -692,33 +691,24 @@ static int fused_launch(Decoder* d, FusedArgs& a, bool sim, int64_t B, int32_t m
     // exact-in-fp32 mode: the guarded variant of the kernel, its grid constants and the violation counter
     const int grid_k = LDPC_FLAG_PRIOR_GRID_OF(flags);
     const void* kern = sim ? shape.kernel_sim : shape.kernel;
+    LDPC_TRY(grid_guard_available(d, BK_AUTO, flags, nullptr));  // the algorithm's own refusal; what this shape has is looked at below
+    RuleParams r;
+    LDPC_TRY(rule_params(d, &r));
+    // (the rule parameters share their bytes with the grid constants, which these kernels never read)
     if (d->alg == ALG_NMSA) {
-        if (grid_k >= 0) {
-            set_error("prior grid: corrected min-sum (LDPC_ALG_NMSA) has no exact-in-fp32 mode (a scale takes values off the grid)");
-            return LDPC_E_UNSUPPORTED;
-        }
-        a.corr_scale_d = d->corr_scale;  // (shares its bytes with the grid constants, which these kernels never read)
-        a.corr_offset_d = d->corr_offset;
-        a.corr_scale = (float)d->corr_scale;
-        a.corr_offset = (float)d->corr_offset;
+        a.corr_scale_d = r.scale;
+        a.corr_offset_d = r.offset;
+        a.corr_scale = (float)r.scale;
+        a.corr_offset = (float)r.offset;
     }
     if (d->alg == ALG_QMSA) {
-        if (grid_k >= 0) {
-            set_error("prior grid: fixed-point min-sum (LDPC_ALG_QMSA) quantises its priors itself (ldpc_decoder_set_fixed_point)");
-            return LDPC_E_UNSUPPORTED;
-        }
-        // (share their bytes with the grid constants, which these kernels never read)
-        const double fx[5] = {d->fx_scale, d->fx_offset_eff(), d->fx_cap(), d->fx_step(), d->fx_vmax()};  // FX_SCALE .. FX_VMAX
+        const double fx[5] = {r.scale, r.offset, r.cap, r.step, r.vmax};  // FX_SCALE .. FX_VMAX
         for (int i = 0; i < 5; ++i) {
-            const float f = (float)fx[i];
+            const float f = (float)fx[i];  // (exact, and the double's low word zero: rule_params)
             uint64_t w64;
             uint32_t w32;
             std::memcpy(&w64, &fx[i], 8);
             std::memcpy(&w32, &f, 4);
-            if ((double)f != fx[i] || (uint32_t)w64 != 0u) {  // cannot happen for values ldpc_decoder_set_fixed_point accepts
-                set_error("fixed-point min-sum: constant %d (%g) is not exact in fp32", i, fx[i]);
-                return LDPC_E_ARG;
-            }
             a.fx_word[i] = shape.esz == 8 ? (uint32_t)(w64 >> 32) : w32;
         }
     }

@@ -61,23 +61,15 @@ constexpr int fused_check_rows(int esz, int DC, int DV, int CRW, int VRW, int NW
 }
 inline int fused_check_rows(const ShapeEntry& s) { return fused_check_rows(s.esz, s.DC, s.DV, s.CRW, s.VRW, s.NW, s.VRX); }
 
-// shape tables, one per translation unit (built in parallel); preference order = table order
-const ShapeEntry* fused_shapes_f32_dc6(int* count);
-const ShapeEntry* fused_shapes_f32_dcx(int* count);
-const ShapeEntry* fused_shapes_f64_dc6(int* count);
-const ShapeEntry* fused_shapes_f64_dcx(int* count);
-const ShapeEntry* fused_shapes_bec(int* count);  // bit-sliced erasure decoder (ldpc_bec_kernels.hpp)
-// corrected min-sum (ALG_NMSA): one sibling of every min-sum shape above, in the same order -- a decoder never changes shape because the
-// correction is on
-const ShapeEntry* fused_shapes_nmsa_f32_dc6(int* count);
-const ShapeEntry* fused_shapes_nmsa_f32_dcx(int* count);
-const ShapeEntry* fused_shapes_nmsa_f64_dc6(int* count);
-const ShapeEntry* fused_shapes_nmsa_f64_dcx(int* count);
-// fixed-point min-sum (ALG_QMSA): likewise, one sibling of every min-sum shape in the same order
-const ShapeEntry* fused_shapes_qmsa_f32_dc6(int* count);
-const ShapeEntry* fused_shapes_qmsa_f32_dcx(int* count);
-const ShapeEntry* fused_shapes_qmsa_f64_dc6(int* count);
-const ShapeEntry* fused_shapes_qmsa_f64_dcx(int* count);
+// shape tables, one per translation unit (built in parallel); preference order = table order.  The min-sum variants (ALG_NMSA, ALG_QMSA)
+// have a table per min-sum table, expanded from the same list of shapes (ldpc_fused_shapes.hpp): a decoder never changes shape because
+// the correction is on.  (Tables of a new variant go last: the indices of the shapes in front of them do not move.)
+#define LDPC_SHAPE_TABLES(X)                                                                                                    \
+    X(f32_dc6) X(f32_dcx) X(f64_dc6) X(f64_dcx) X(bec) /* bec: bit-sliced erasure decoder (ldpc_bec_kernels.hpp) */              \
+    X(nmsa_f32_dc6) X(nmsa_f32_dcx) X(nmsa_f64_dc6) X(nmsa_f64_dcx) X(qmsa_f32_dc6) X(qmsa_f32_dcx) X(qmsa_f64_dc6) X(qmsa_f64_dcx)
+#define LDPC_SHAPE_TABLE_DECL(name) const ShapeEntry* fused_shapes_##name(int* count);
+LDPC_SHAPE_TABLES(LDPC_SHAPE_TABLE_DECL)
+#undef LDPC_SHAPE_TABLE_DECL
 
 namespace {
 

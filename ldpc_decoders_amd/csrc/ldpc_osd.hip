@@ -340,7 +340,7 @@ int check_decoder(const char* who, const Osd* h, const Decoder* d) {
         set_error("%s: the decoder must be one of the code this handle was created for", who);
         return LDPC_E_ARG;
     }
-    if (d->alg == ALG_BEC || d->dtype == DT_F16) {
+    if (!alg_row(d->alg).llr || d->dtype == DT_F16) {
         set_error("%s: needs the soft output of an fp32 or fp64 LDPC_ALG_MSA / SPA / NMSA / QMSA / LMSA decoder (the erasure decoder has none, fp16 "
                   "storage keeps none in the decoder's type)", who);
         return LDPC_E_UNSUPPORTED;

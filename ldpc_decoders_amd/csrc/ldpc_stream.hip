@@ -172,8 +172,8 @@ __global__ __launch_bounds__(256) void k_quantise_tile(T* __restrict__ prior_t, 
     if (i < count) prior_t[i] = quantise_prior(prior_t[i], step, vmax);
 }
 template <typename T>
-void launch_quantise(const Decoder* d, T* prior_t, int64_t count, hipStream_t st) {
-    hipLaunchKernelGGL((k_quantise_tile<T>), dim3((unsigned)((count + 255) / 256)), dim3(256), 0, st, prior_t, count, (T)d->fx_step(), (T)d->fx_vmax());
+void launch_quantise(const RuleParams& r, T* prior_t, int64_t count, hipStream_t st) {
+    hipLaunchKernelGGL((k_quantise_tile<T>), dim3((unsigned)((count + 255) / 256)), dim3(256), 0, st, prior_t, count, (T)r.step, (T)r.vmax);
 }
 
 __global__ void k_init_live(u64* __restrict__ live, int64_t B, int tiles) {
@@ -811,8 +811,7 @@ constexpr int unroll_for(int row_bytes) {
 struct Geometry {
     int tiles, cn_chunks, cpw, vn_chunks, vpw, xcd_aware;
     int freeze = 0;  // lanes of departed frames do not compute or store (soft-output decodes)
-    double corr_scale = 1.0, corr_offset = 0.0;  // corrected min-sum (Decoder::corr_scale / corr_offset at the time of the call)
-    double cap = 0.0;                            // fixed-point min-sum: corr_scale / corr_offset hold Decoder::fx_scale / fx_offset, cap its saturation (msa_fixed)
+    RuleParams rule;  // of the check rule, at the time of the call
 };
 
 // The two passes.  GATHER (c2v_in / prior_out + srcmap): the sweep that carries a folded repack; those forms are built for the node
@@ -826,7 +825,7 @@ void dispatch_cn(const Code* c, T* c2v, const T* src, const u64* live, const Geo
         if constexpr (!GATHER || DCMAX <= 8)
             hipLaunchKernelGGL((k_cn<T, ALG, DCMAX, decltype(fdc)::value, UNR, GATHER>), dim3(task_blocks(g.tiles, g.cn_chunks, g.xcd_aware)), dim3(64, 4), 0, st,
                                c->d_row_ptr, c->d_edge_var, c2v, src, live, c->m, c->n, c->E, g.tiles, g.cn_chunks, g.cpw, first, g.xcd_aware,
-                               last_int_arg<T, ALG>::make(g.freeze, g.corr_scale, g.corr_offset, g.cap), c2v_in, srcmap);
+                               last_int_arg<T, ALG>::make(g.freeze, g.rule), c2v_in, srcmap);
     });
 }
 template <typename T, int ALG, bool GATHER = false>
@@ -853,7 +852,7 @@ void dispatch_layers(const Decoder* d, T* c2v, T* marg, const u64* live, const G
             const int chunks = (c1 - c0 + g.cpw - 1) / g.cpw;
             hipLaunchKernelGGL(kern, dim3(task_blocks(g.tiles, chunks, g.xcd_aware)), dim3(64, 4), 0, st, c->d_row_ptr, c->d_edge_var,
                                (const int32_t*)d->layer_order.p, c2v, marg, live, c->m, c->n, c->E, g.tiles, chunks, g.cpw, c0, c1, g.xcd_aware, g.freeze,
-                               (T)g.corr_scale, (T)g.corr_offset);
+                               (T)g.rule.scale, (T)g.rule.offset);
         }
     });
 }
@@ -937,9 +936,7 @@ int run(Decoder* d, const DecodeCall& k, const SimSource* sim = nullptr) {
     Geometry g;
     g.tiles = tiles;
     g.freeze = k.soft != nullptr ? 1 : 0;
-    g.corr_scale = ALG == ALG_QMSA ? d->fx_scale : d->corr_scale;
-    g.corr_offset = ALG == ALG_QMSA ? d->fx_offset_eff() : d->corr_offset;
-    g.cap = d->fx_cap();
+    LDPC_TRY(rule_params(d, &g.rule));
     // Nodes per wave.  The marginal lines a check pass gathers are re-used dv times; the fewer tiles are in flight at once, the
     // more of those re-reads hit on chip -- so a tile is cut into MANY short wave tasks (tile-major task order).  Measured on one
     // MI355X (sweep of 32 768 frames of the (3,6) n = 64 800 shape, profiles/r03_stream_chunking.txt): 64 checks per wave 20.9 ms,
@@ -971,7 +968,7 @@ int run(Decoder* d, const DecodeCall& k, const SimSource* sim = nullptr) {
     }
     if (!sim)
         hipLaunchKernelGGL((k_load_tile<T>), dim3((n + 63) / 64, tiles), dim3(256), 0, st, (const T*)k.priors, y0, B, n, LAYERED ? marg : prior, xbits);
-    if constexpr (ALG == ALG_QMSA) launch_quantise<T>(d, prior, (int64_t)tiles * n * 64, st);  // priors -> levels, in the workspace
+    if constexpr (ALG == ALG_QMSA) launch_quantise<T>(g.rule, prior, (int64_t)tiles * n * 64, st);  // priors -> levels, in the workspace
     hipLaunchKernelGGL(k_init_live, dim3((tiles + 255) / 256), dim3(256), 0, st, live, B, tiles);
 
     const int cap = max_iter > 0 ? max_iter : 100000;  // max_iter <= 0 == unlimited upstream (src/bpa.py:28); bounded here
@@ -1383,6 +1380,8 @@ int run16(Decoder* d, const DecodeCall& k, const SimSource* sim) {
     float* const soft_out = (float*)k.soft;
     const hipStream_t st = k.stream;
     if (!degrees_supported(c)) return LDPC_E_UNSUPPORTED;
+    RuleParams rule;
+    LDPC_TRY(rule_params(d, &rule));
     const int tiles0 = (int)((B + 63) / 64), pairs0 = (tiles0 + 1) / 2;
     int tiles = tiles0, pairs = pairs0;  // shrink when the live frames are repacked into dense pair-tiles
     const bool early = !(k.flags & FLAG_NO_EARLY_EXIT);
@@ -1440,7 +1439,7 @@ int run16(Decoder* d, const DecodeCall& k, const SimSource* sim) {
     } else {
         hipLaunchKernelGGL(k_load_tile16, dim3((n + 63) / 64, pairs), dim3(256), 0, st, (const float*)k.priors, y0, B, n, prior, xbits);
     }
-    if constexpr (ALG == ALG_QMSA) launch_quantise<float>(d, reinterpret_cast<float*>(prior), (int64_t)pairs * n * 128, st);  // priors -> levels
+    if constexpr (ALG == ALG_QMSA) launch_quantise<float>(rule, reinterpret_cast<float*>(prior), (int64_t)pairs * n * 128, st);  // priors -> levels
     hipLaunchKernelGGL(k_init_live, dim3((tiles + 255) / 256), dim3(256), 0, st, live, B, tiles);
     int repacks = 0;
     const int cpw = 4, vpw = 16;
@@ -1490,8 +1489,7 @@ int run16(Decoder* d, const DecodeCall& k, const SimSource* sim) {
             constexpr int DCM = decltype(dcm)::value, FDC = decltype(fdc)::value, UNR = DCM <= 6 ? 2 : 1;
             const auto kern = it == 0 ? k_cn16<ALG, DCM, FDC, UNR, true> : k_cn16<ALG, DCM, FDC, UNR, false>;
             hipLaunchKernelGGL(kern, cgrid, blk, 0, st, c->d_row_ptr, c->d_edge_var, edge_vpos, msg, v2c, prior, live, m, n, E, pairs, tiles, cn_chunks,
-                               last_int_arg<float, ALG>::make(cpw, ALG == ALG_QMSA ? d->fx_scale : d->corr_scale,
-                                                              ALG == ALG_QMSA ? d->fx_offset_eff() : d->corr_offset, d->fx_cap()));
+                               last_int_arg<float, ALG>::make(cpw, rule));
         });
         LDPC_TRY(prof.mark(1));
         var_class<false>(c, [&](auto dvm, auto fdv) {
@@ -1513,20 +1511,26 @@ bool batch_fits(int64_t B) {
     return false;
 }
 
-template <typename T>
-int run_alg(Decoder* d, const DecodeCall& k, const SimSource* sim) {
-    if (d->alg == ALG_NMSA) return run<T, ALG_NMSA>(d, k, sim);
-    if (d->alg == ALG_LMSA) return run<T, ALG_LMSA>(d, k, sim);
-    if (d->alg == ALG_QMSA) return run<T, ALG_QMSA>(d, k, sim);
-    return d->alg == ALG_MSA ? run<T, ALG_MSA>(d, k, sim) : run<T, ALG_SPA>(d, k, sim);
+// The decoder's algorithm -> f(ALG) as a std::integral_constant: one arm per LLR row of kAlgs
+template <class F>
+int alg_class(const Decoder* d, F&& f) {
+    switch (d->alg) {
+        case ALG_MSA: return f(int_c<ALG_MSA>{});
+        case ALG_NMSA: return f(int_c<ALG_NMSA>{});
+        case ALG_QMSA: return f(int_c<ALG_QMSA>{});
+        case ALG_LMSA: return f(int_c<ALG_LMSA>{});
+        default: return f(int_c<ALG_SPA>{});
+    }
 }
 
 // LLR decoders: the driver of the decoder's storage type; with `sim` the priors are drawn into the tiles instead of loaded
 int run_llr(Decoder* d, const DecodeCall& k, const SimSource* sim) {
-    if (d->dtype == DT_F16 && d->alg == ALG_NMSA) return run16<ALG_NMSA>(d, k, sim);
-    if (d->dtype == DT_F16 && d->alg == ALG_QMSA) return run16<ALG_QMSA>(d, k, sim);
-    if (d->dtype == DT_F16) return d->alg == ALG_MSA ? run16<ALG_MSA>(d, k, sim) : run16<ALG_SPA>(d, k, sim);  // priors are fp32
-    return d->dtype == DT_F64 ? run_alg<double>(d, k, sim) : run_alg<float>(d, k, sim);
+    return alg_class(d, [&](auto alg) -> int {
+        constexpr int ALG = decltype(alg)::value;
+        if constexpr (alg_row(ALG).f16)
+            if (d->dtype == DT_F16) return run16<ALG>(d, k, sim);  // priors are fp32
+        return d->dtype == DT_F64 ? run<double, ALG>(d, k, sim) : run<float, ALG>(d, k, sim);
+    });
 }
 
 }  // namespace

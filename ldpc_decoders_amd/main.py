@@ -16,7 +16,8 @@ from collections import OrderedDict
 import numpy as np
 
 from . import codes, dist, utils
-from .models import models
+from .models import all_decoder_names, models
+from .registry import BY_NAME
 from .montecarlo import DeviceSimulator, run_point_exact
 
 
@@ -24,6 +25,7 @@ def test(args, comm=None):
     comm = comm or dist.Comm()
     model = models[args.channel]
     dec_fac = getattr(model, args.decoder)
+    row = BY_NAME[args.decoder]  # what this driver may do with the name
     id_keys = ["channel", "code", "decoder", "codeword", "min_wec"] + dec_fac.id_keys
     id_val = [vars(args)[key] for key in id_keys]
     log = logging.getLogger(".".join(utils.strl(id_val)))
@@ -33,27 +35,27 @@ def test(args, comm=None):
     # --codeword -1 (a random codeword per frame, src/main.py:38): on the device for the BP decoders -- from the code book where the code
     # has one, from the systematic GF(2) encoder (Code.encoder()) otherwise -- and for ML over the BEC of a code without a code book (the
     # elimination decoder, encoder words); the reference's sequential loop on host noise for the others
-    device_words = args.decoder in ("SPA", "MSA", "NMSA", "QMSA", "LMSA", "OSD") or (args.channel == "bec" and args.decoder == "ML" and code.gen_mtx is None)
+    device_words = row.device_words or (args.channel == "bec" and args.decoder == "ML" and code.gen_mtx is None)
     exact = bool(args.exact) or (args.codeword == -1 and not device_words)
     if exact and comm.world > 1:
         raise SystemExit("--exact / --codeword -1 follow the reference's sequential rule and run on a single rank")
     if exact and args.np_seed is not None:
         np.random.seed(args.np_seed)
     kwargs = dict(vars(args))
-    if args.decoder in ("LMSA", "OSD"):
+    if row.pops_layers:
         kwargs.pop("layers", None)  # (--layers is ADMMA's network shape, src/utils.py:43: not a layering of the checks; LMSA takes the greedy one)
     # fp32 message arithmetic in the throughput mode -- except min-sum over the BSC: every LLR is +-L there, the decoder is
     # tie-dominated and only the reference's fp64 arithmetic reproduces its curves
     # (fixed-point min-sum is no exception: its integers are the same in every arithmetic)
-    tie_dominated = args.channel == "bsc" and args.decoder in ("MSA", "NMSA", "LMSA", "OSD")  # (OSD: NMSA in front)
+    tie_dominated = args.channel == "bsc" and row.tie_dominated  # (OSD: NMSA in front)
     kwargs["precision"] = args.precision or ("f64" if (exact or tie_dominated) else "f32")
     # (OSD orders the soft output of an f32 / f64 decoder: fp16 storage keeps none in the decoder's type)
-    if kwargs["precision"] == "f16" and (args.decoder not in ("SPA", "MSA", "NMSA", "QMSA") or args.channel == "bec" or exact):
+    if kwargs["precision"] == "f16" and (not row.f16 or args.channel == "bec" or exact):
         raise SystemExit("--precision f16 (fp16 storage of the messages): the LLR decoders SPA / MSA over biawgn / bsc, device-noise mode")
-    if args.decoder == "LMSA" and args.backend == "fused":  # (refused before a decoder exists, like the two around it)
+    if row.refuses_fused and args.backend == "fused":  # (refused before a decoder exists, like the two around it)
         raise SystemExit("--backend fused: layered min-sum (LMSA) runs on the streaming kernels (--backend auto / stream)")
     # (NMSA, and OSD with NMSA in front: a scale takes values off the grid; QMSA quantises its priors itself; refused before a decoder exists)
-    if getattr(args, "prior_grid", None) is not None and args.decoder in ("NMSA", "QMSA", "LMSA", "OSD"):
+    if getattr(args, "prior_grid", None) is not None and row.prior_grid is False:
         raise SystemExit("--prior-grid: fp32 min-sum over BI-AWGN (biawgn <code> MSA, without --precision f64)")
     results = OrderedDict()
 
@@ -114,7 +116,7 @@ def test(args, comm=None):
                 handle.on_iters = None
                 state["hist_into"] = (inner.iter, bins)  # intermediate result files then carry a real histogram, not zeros
             grid = getattr(args, "prior_grid", None)
-            if grid is not None and (args.decoder != "MSA" or args.channel != "biawgn" or kwargs["precision"] != "f32"):
+            if grid is not None and (row.prior_grid is not True or args.channel != "biawgn" or kwargs["precision"] != "f32"):
                 raise SystemExit("--prior-grid: fp32 min-sum over BI-AWGN (biawgn <code> MSA, without --precision f64)")
             sim = DeviceSimulator(handle, args.channel, args.max_iter, args.codeword, args.seed, comm, hist_bins=bins, prior_grid=grid)
             c = sim.run_point(param, stream_id=pi, min_wec=args.min_wec, batch_per_rank=args.batch, on_progress=progress,
@@ -130,10 +132,8 @@ def test(args, comm=None):
 
 
 def build_parser():
-    """The reference's grammar with the reference's decoder names, plus this build's own (``models.extra_decoder_names``: NMSA,
-    ``models.fixed_point_decoder_names``: QMSA, ``models.layered_decoder_names``: LMSA, ``models.post_processing_decoder_names``: OSD)."""
-    return utils.setup_parser(codes.get_code_names(), models.keys(), utils.decoder_names + utils.extra_decoder_names + utils.fixed_point_decoder_names +
-                              utils.layered_decoder_names + utils.post_processing_decoder_names)
+    """The reference's grammar with the reference's decoder names, plus this build's own (``registry.ROWS``: NMSA, QMSA, LMSA, OSD)."""
+    return utils.setup_parser(codes.get_code_names(), models.keys(), all_decoder_names)
 
 
 def main(argv=None):

@@ -4,13 +4,15 @@
 one (src/main.py:11-12).  The BP decoders, the exhaustive ML decoder of the short codes and the ADMM LP decoder are built for the GPU; the other
 upstream names (LP, ADMMA) resolve to a class that raises on construction.
 """
-from . import bec, biawgn, bsc
+from . import bec, biawgn, bsc, registry
 
-decoder_names = ["ML", "SPA", "MSA", "LP", "ADMM", "ADMMA"]  # src/utils.py:16
-extra_decoder_names = ["NMSA"]  # this build's own decoders (no upstream counterpart): corrected min-sum, bpa.NMSA
-fixed_point_decoder_names = ["QMSA"]  # likewise: fixed-point min-sum (q-bit saturating messages), bpa.QMSA
-layered_decoder_names = ["LMSA"]  # likewise: layered (serial-C) corrected min-sum on the streaming kernels, bpa.LMSA
-post_processing_decoder_names = ["OSD"]  # likewise: BP + ordered-statistics decoding of the frames BP fails on, bpa.OSD
+decoder_names = registry.names("reference")  # src/utils.py:16
+# this build's own decoders (no upstream counterpart; what each is: registry.ROWS)
+extra_decoder_names = registry.names("extra")
+fixed_point_decoder_names = registry.names("fixed_point")
+layered_decoder_names = registry.names("layered")
+post_processing_decoder_names = registry.names("post_processing")
+all_decoder_names = [r.name for r in registry.ROWS]  # the parser's choices
 
 
 def _unavailable(name):

@@ -1,0 +1,90 @@
+"""THE table of the decoder names this build knows: one row per name, in the order the command line lists them.
+
+Everything that is a fact about a NAME is a column here -- the class behind it, what the bec says to it, what ``main.test`` may do with
+it -- and everything that used to repeat those facts is derived: the wrapper classes of ``biawgn`` / ``bsc``, the refusing classes of
+``bec``, the name lists of ``models`` (and the parser's choices), the front decoders of ``bpa.OSD``.  A new variant is one row here, plus
+its row in the library's own table (``kAlgs``, csrc/ldpc_common.hpp).
+"""
+from collections import namedtuple
+
+from . import admm, bpa, ml
+
+Row = namedtuple("Row", [
+    "name",
+    "group",          # which list of ``models`` carries the name: reference (src/utils.py:16), extra, fixed_point, layered, post_processing
+    "backing",        # the bpa / admm class the LLR wrappers of biawgn / bsc hold ({channel: class}: the channel's own class; None: not built)
+    "bec_refusal",    # None: the bec module has its own class of this name; else (docstring, sentence) of the class that raises there
+    "osd_front",      # may run in front of bpa.OSD (osd_bp)
+    "device_words",   # --codeword -1 is drawn on the device (else: the reference's sequential loop on host noise)
+    "tie_dominated",  # over the bsc only the reference's fp64 arithmetic reproduces its curves: --precision defaults to f64 there
+    "f16",            # accepts --precision f16 (over biawgn / bsc, device noise)
+    "prior_grid",     # True: takes --prior-grid (in fp32 over biawgn); False: refused before a decoder exists; None: refused where the device loop would use it
+    "pops_layers",    # the ADMMA flag --layers must not reach it (to LMSA ``layers`` is a layering of the checks)
+    "refuses_fused",  # --backend fused is refused before a decoder exists
+])
+Row.__new__.__defaults__ = (None, False, False, False, False, None, False, False)
+
+ROWS = [
+    Row("ML", "reference", {"biawgn": ml.BiawgnML, "bsc": ml.BscML}),
+    Row("SPA", "reference", bpa.SPA, osd_front=True, device_words=True, f16=True),
+    Row("MSA", "reference", bpa.MSA, osd_front=True, device_words=True, tie_dominated=True, f16=True, prior_grid=True),
+    Row("LP", "reference", None),
+    Row("ADMM", "reference", admm.ADMM),
+    Row("ADMMA", "reference", None),
+    # this build's own decoders (no upstream counterpart), wrapped like MSA
+    Row("NMSA", "extra", bpa.NMSA,  # corrected (normalised / offset) min-sum
+        ("Corrected min-sum has no meaning over the erasure channel: the ternary decoder has no magnitudes to scale or offset.",
+         "decoder NMSA (corrected min-sum) does not exist over the bec: the erasure decoder has no magnitudes to correct; use SPA / MSA there"),
+        osd_front=True, device_words=True, tie_dominated=True, f16=True, prior_grid=False),
+    Row("QMSA", "fixed_point", bpa.QMSA,  # fixed-point min-sum (q-bit saturating messages); its integers are the same in every arithmetic
+        ("Fixed-point min-sum has no meaning over the erasure channel either: the ternary decoder has no magnitudes to quantise.",
+         "decoder QMSA (fixed-point min-sum) does not exist over the bec: the erasure decoder has no magnitudes to quantise; use SPA / MSA there"),
+        osd_front=True, device_words=True, f16=True, prior_grid=False),
+    Row("LMSA", "layered", bpa.LMSA,  # layered (serial-C) corrected min-sum on the streaming kernels
+        ("Layered min-sum is corrected min-sum on another schedule: it has no meaning over the erasure channel either.",
+         "decoder LMSA (layered corrected min-sum) does not exist over the bec: the erasure decoder has no magnitudes to correct; use SPA / MSA there"),
+        osd_front=True, device_words=True, tie_dominated=True, prior_grid=False, pops_layers=True, refuses_fused=True),
+    Row("OSD", "post_processing", bpa.OSD,  # BP + ordered-statistics decoding of the frames BP fails on (NMSA in front)
+        ("Ordered-statistics post-processing orders soft values; over the erasure channel ``ML`` (elimination of the erased bits) is exact.",
+         "decoder OSD (BP + ordered-statistics post-processing) does not exist over the bec: use ML there, the elimination decoder is exact"),
+        device_words=True, tie_dominated=True, prior_grid=False, pops_layers=True),
+]
+BY_NAME = {r.name: r for r in ROWS}
+
+
+def names(group):
+    return [r.name for r in ROWS if r.group == group]
+
+
+def osd_fronts():
+    """{name: bpa class} of the decoders that may run in front of ``bpa.OSD``."""
+    return {r.name: r.backing for r in ROWS if r.osd_front}
+
+
+def _llr_wrapper(name, base, backing, module):
+    def __init__(self, param, _code, **kwargs):
+        base.__init__(self, param, backing(_code, **kwargs))
+
+    return type(name, (base,), {"id_keys": backing.id_keys, "__init__": __init__, "__module__": module})
+
+
+def add_llr_wrappers(namespace, base):
+    """``class NAME(base)`` holding ``backing(_code, **kwargs)`` for every row with a backing class, into a channel module's namespace
+    (a name the module defines itself -- ADMM, which has its own decode_batch and stats -- is left alone)."""
+    for row in ROWS:
+        if isinstance(row.backing, type) and row.name not in namespace:
+            namespace[row.name] = _llr_wrapper(row.name, base, row.backing, namespace["__name__"])
+
+
+def _refusing(name, doc, sentence, id_keys, module):
+    def __init__(self, *a, **k):
+        raise NotImplementedError(sentence)
+
+    return type(name, (), {"__doc__": doc, "id_keys": id_keys, "__init__": __init__, "__module__": module})
+
+
+def add_bec_refusals(namespace):
+    """The classes of the bec module that raise: the decoders whose rule has nothing to work on over the erasure channel."""
+    for row in ROWS:
+        if row.bec_refusal is not None:
+            namespace[row.name] = _refusing(row.name, row.bec_refusal[0], row.bec_refusal[1], row.backing.id_keys, namespace["__name__"])
