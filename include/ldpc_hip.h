@@ -400,6 +400,58 @@ int ldpc_osd_simulate(ldpc_osd_t h, ldpc_decoder_t dec, int channel, double para
                       uint64_t frame0, int64_t B, int32_t max_iter, uint32_t flags, int32_t order, int64_t depth, int32_t hist_bins,
                       int64_t* counters_dev, void* stream);
 
+/* ---- Hard-decision decoding: bit-sliced Gallager-B (GALB) ------------------------------------------------------
+ * No upstream counterpart: every decoder of the reference works on soft values (src/bpa.py) or on erasures (src/bec.py).  Gallager's
+ * algorithm A / B passes ONE BIT per edge.  Per frame, for the received word y in {0,1}^n, d_v the degree of variable v and the
+ * threshold parameter t (0 <= t <= 255, ldpc_hard_set_threshold), the flip threshold of a variable of degree d is
+ *     b_d = floor((d - 1) / 2) + 1      for t = 0   (the majority of the d - 1 extrinsic messages; Gallager A for d = 3),
+ *     b_d = min(t, max(d - 1, 1))       for t >= 1  (any t >= dv_max - 1 is Gallager A).
+ *   1. Iteration 0.  If H y = 0 the frame leaves with x = y, iters = 0.  Otherwise v2c_(v->c) = y_v on every edge.
+ *   2. Sweep l = 1, 2, ...
+ *        check:     c2v_(c->v) = XOR over v' in N(c) \ {v} of v2c_(v'->c)   ( = P_c ^ v2c_(v->c), P_c the parity of all messages into c)
+ *        variable:  delta_j = c2v_j ^ y_v on each of the d edges, T = sum of delta_j;
+ *                   decision  x_v = y_v ^ [2 T > d + 1]          (majority of the d + 1 votes, the received bit wins a tie)
+ *                   message   v2c_j = y_v ^ [T - delta_j >= b_d]
+ *                   a variable of degree 0 keeps x_v = y_v
+ *        exit:      if H x = 0 the frame leaves with x and iters = l; after sweep max_iter every remaining frame leaves with the x of
+ *                   that sweep and iters = max_iter.
+ *   3. LDPC_FLAG_NO_EARLY_EXIT: exactly max_iter sweeps for every frame (the iteration-0 exit is off too), iters = max_iter.
+ *   4. Refusals.  max_iter <= 0: LDPC_E_ARG (a hard-decision decoder may oscillate for ever and has no "nothing changed" exit).
+ *      t outside 0..255: LDPC_E_ARG.  A code with a variable of degree above 63: LDPC_E_UNSUPPORTED (ldpc_hard_create).
+ *      LDPC_BACKEND_FUSED on a code whose slab does not fit the LDS (below): LDPC_E_UNSUPPORTED (ldpc_hard_create).
+ * Everything is an integer: decisions and iteration counts are one function of (H, y, t, max_iter, flags), the same on both backends, for
+ * any batch size and any position of a frame in its batch.
+ * Backends.  A message is one bit; a machine word holds it for 32 frames (a slab), bit f = frame f of the slab.
+ *   LDPC_BACKEND_STREAM  any code: the planes live in HBM in supertiles of 64 slabs (2048 frames, one wave lane per slab), v2c lines in
+ *                        variable-major order; a load / transposition kernel, one check + syndrome pass and one variable pass per sweep,
+ *                        exit bookkeeping per supertile (a supertile without a live frame is skipped), an unload kernel.
+ *   LDPC_BACKEND_FUSED   one workgroup owns one slab for all its sweeps: y, the decisions, v2c and the check parities live in the LDS,
+ *                        HBM sees the received word in and the decisions out, once.  LDS-fit rule:
+ *                            hard_lds_bytes = 4 * (2 n + E + m + 4) <= 163840
+ *                        (n words of y, n of x, E of v2c, m of parities, 4 of slab state).  Slabs are handed out by an atomic dispenser.
+ *   LDPC_BACKEND_AUTO    the LDS kernel where the rule holds, the streaming kernels otherwise.
+ * Handles are not thread-safe (one workspace). */
+typedef struct ldpc_hard_s* ldpc_hard_t;
+int ldpc_hard_create(ldpc_code_t code, int backend, ldpc_hard_t* out);
+int ldpc_hard_destroy(ldpc_hard_t h);
+/* The threshold parameter t of the rule above; after ldpc_hard_create: 0.  Handle state, read when a call is enqueued. */
+int ldpc_hard_set_threshold(ldpc_hard_t h, int t);
+int ldpc_hard_get_threshold(ldpc_hard_t h, int* t);
+/* Steps 1-3 for B frames.  y_dev [B, n] uint8 in {0, 1} (only bit 0 of a byte is read); xhat_dev [B, n] uint8 or NULL; xhat_bits_dev
+ * [B, W] uint32 in the layout of ldpc_decode_bits or NULL (at least one of the two); iters_dev [B] int32.  May synchronise `stream`. */
+int ldpc_hard_decode(ldpc_hard_t h, const uint8_t* y_dev, int64_t B, int32_t max_iter, uint32_t flags, uint8_t* xhat_dev,
+                     uint32_t* xhat_bits_dev, int32_t* iters_dev, void* stream);
+/* ldpc_channel + ldpc_hard_decode + ldpc_count_errors_bits for frames [frame0, frame0+B) of the all-`codeword` word -- the body of
+ * `while wec < min_wec` (src/main.py:37-45) as ldpc_osd_simulate is.  LDPC_CH_BSC (the received bits) and LDPC_CH_BIAWGN (the word sliced
+ * at prior < 0); codeword 0 or 1; 1 is refused (LDPC_E_ARG) when a check has odd degree.  The received bytes cross HBM once. */
+int ldpc_hard_simulate(ldpc_hard_t h, int channel, double param, int codeword, uint64_t seed, uint64_t stream_id, uint64_t frame0, int64_t B,
+                       int32_t max_iter, uint32_t flags, int32_t hist_bins, int64_t* counters_dev, void* stream);
+/* kernels of the last decode / simulate: LDPC_BACKEND_STREAM or LDPC_BACKEND_FUSED (before the first call: what AUTO resolved to) */
+int ldpc_hard_last_backend(ldpc_hard_t h, int* backend);
+/* out4 = {LDS bytes per slab (the rule's left side, also when it does not fit), frames per slab, slabs per CU as launched (0: the LDS
+ * kernel is not available for this code), workgroups of the LDS kernel's grid} */
+int ldpc_hard_info(ldpc_hard_t h, double* out4);
+
 /* ---- ADMM LP decoding ------------------------------------------------------------------------------------------
  * Replaces admm.ADMM (src/admm.py:9-77) together with its native projection (src/parity_polytope/projection.cpp:30-275, bound
  * upstream through ctypes in exact.py:12-53).  Check degrees up to 16. */

@@ -722,6 +722,109 @@ class OsdHandle:
             _lib.check(lib.ldpc_count_errors_words(xhat.data_ptr(), sent.data_ptr(), iters.data_ptr(), nb, n, hist_bins, counters.data_ptr(), st))
 
 
+class HardHandle:
+    """Bit-sliced Gallager-B hard-decision decoder (``ldpc_hard_*``): one bit per message, 32 frames per machine word.  ``backend``:
+    "stream" (planes in HBM, any code), "fused" (one slab per workgroup in the LDS; refused for a code that does not fit) or "auto"."""
+
+    def __init__(self, code, backend="auto", device=None, threshold=0):
+        lib = _lib.load()
+        self.code_handle = code_handle(code, device)
+        self.code, self.device, self.backend = code, self.code_handle.device, backend
+        h = ctypes.c_void_p()
+        _lib.check(lib.ldpc_hard_create(self.code_handle.h, _lib.BACKEND[backend], ctypes.byref(h)))
+        self.h = h
+        if threshold:
+            self.set_threshold(threshold)
+
+    def __del__(self):
+        try:
+            if getattr(self, "h", None):
+                _lib.load().ldpc_hard_destroy(self.h)
+                self.h = None
+        except Exception:
+            pass
+
+    def set_threshold(self, t):
+        _lib.check(_lib.load().ldpc_hard_set_threshold(self.h, int(t)))
+
+    def threshold(self):
+        t = ctypes.c_int(0)
+        _lib.check(_lib.load().ldpc_hard_get_threshold(self.h, ctypes.byref(t)))
+        return t.value
+
+    def last_backend(self):
+        """Kernels of the last decode / simulate: "stream" or "fused" (before the first call: what the handle will use)."""
+        b = ctypes.c_int(0)
+        _lib.check(_lib.load().ldpc_hard_last_backend(self.h, ctypes.byref(b)))
+        return _lib.BACKEND_NAME.get(b.value, "?")
+
+    def info(self):
+        out = (ctypes.c_double * 4)()
+        _lib.check(_lib.load().ldpc_hard_info(self.h, out))
+        return dict(zip(("lds_bytes_per_slab", "frames_per_slab", "slabs_per_cu", "workgroups"), (int(v) for v in out)))
+
+    def _check_y(self, y):
+        import torch
+
+        if not hasattr(y, "is_cuda") or not y.is_cuda or y.dtype != torch.uint8 or not y.is_contiguous() or y.dim() != 2 or y.shape[1] != self.code.n:
+            raise ValueError("y must be a contiguous CUDA uint8 tensor [B, %d]" % self.code.n)
+
+    def decode_device(self, y, max_iter, flags=0):
+        """y: contiguous CUDA uint8 [B, n] in {0, 1} -> (xhat uint8 [B, n], iters int32 [B])."""
+        import torch
+
+        self._check_y(y)
+        B, n = y.shape
+        xhat = torch.empty((B, n), dtype=torch.uint8, device=y.device)
+        iters = torch.empty((B,), dtype=torch.int32, device=y.device)
+        if B:
+            st = torch.cuda.current_stream(y.device).cuda_stream
+            _lib.check(_lib.load().ldpc_hard_decode(self.h, y.data_ptr(), B, int(max_iter), flags, xhat.data_ptr(), None, iters.data_ptr(), st))
+        return xhat, iters
+
+    def decode_device_bits(self, y, max_iter, flags=0):
+        """Packed decisions -> (xhat_bits int32 [B, ceil(n/32)] in the layout of ``DecoderHandle.decode_device_bits``, iters)."""
+        import torch
+
+        self._check_y(y)
+        B, W = y.shape[0], (self.code.n + 31) // 32
+        bits = torch.empty((B, W), dtype=torch.int32, device=y.device)
+        iters = torch.empty((B,), dtype=torch.int32, device=y.device)
+        if B:
+            st = torch.cuda.current_stream(y.device).cuda_stream
+            _lib.check(_lib.load().ldpc_hard_decode(self.h, y.data_ptr(), B, int(max_iter), flags, None, bits.data_ptr(), iters.data_ptr(), st))
+        return bits, iters
+
+    def simulate(self, channel, param, codeword, seed, stream_id, frame0, B, max_iter, counters, flags=0, hist_bins=0):
+        """Same call shape as DecoderHandle.simulate: channel -> hard decisions -> decode -> count on the device (``ldpc_hard_simulate``).
+        ``codeword == -1``: random codewords from the systematic encoder (``Code.encoder()``) through ``ldpc_channel_sent``."""
+        import torch
+
+        if channel not in ("biawgn", "bsc"):
+            raise ValueError("a hard-decision decoder works on the bsc and on the sliced biawgn; it has no erasures to work on")
+        if B <= 0:
+            return
+        lib = _lib.load()
+        st = torch.cuda.current_stream(counters.device).cuda_stream
+        if int(codeword) != -1:
+            _lib.check(lib.ldpc_hard_simulate(self.h, _lib.CHANNEL[channel], float(param), int(codeword), int(seed), int(stream_id), int(frame0),
+                                              int(B), int(max_iter), flags, hist_bins, counters.data_ptr(), st))
+            return
+        n, enc = self.code.n, self.code.encoder().handle(self.device)
+        step = max(2048, min(1 << 17, (1 << 28) // n))
+        for b0 in range(0, int(B), step):
+            nb = min(step, int(B) - b0)
+            sent = enc.encode_random(seed, stream_id, int(frame0) + b0, nb)
+            pri = torch.empty((nb, n), dtype=torch.float32, device=sent.device) if channel == "biawgn" else None
+            y = torch.empty((nb, n), dtype=torch.uint8, device=sent.device) if channel == "bsc" else None
+            _lib.check(lib.ldpc_channel_sent(_lib.CHANNEL[channel], _lib.DTYPE["f32"], float(param), sent.data_ptr(), int(seed), int(stream_id),
+                                             int(frame0) + b0, nb, n, None if pri is None else pri.data_ptr(), None if y is None else y.data_ptr(), st))
+            if y is None:
+                y = (pri < 0).to(torch.uint8)  # the word sliced at prior < 0
+            xhat, iters = self.decode_device(y, max_iter, flags)
+            _lib.check(lib.ldpc_count_errors_words(xhat.data_ptr(), sent.data_ptr(), iters.data_ptr(), nb, n, hist_bins, counters.data_ptr(), st))
+
+
 class AdmmHandle:
     """ADMM LP decoder workspace on one GPU (``ldpc_admm_*``)."""
 

@@ -103,6 +103,15 @@ SIGNATURES = {
     "ldpc_osd_decode": (_c.c_int, [_P, _P, _P, _P, _c.c_int64, _c.c_int32, _c.c_uint32, _c.c_int32, _c.c_int64, _P, _P, _P, _P]),
     "ldpc_osd_simulate": (_c.c_int, [_P, _P, _c.c_int, _c.c_double, _c.c_int, _c.c_uint64, _c.c_uint64, _c.c_uint64, _c.c_int64, _c.c_int32,
                                      _c.c_uint32, _c.c_int32, _c.c_int64, _c.c_int32, _P, _P]),
+    "ldpc_hard_create": (_c.c_int, [_P, _c.c_int, _c.POINTER(_P)]),
+    "ldpc_hard_destroy": (_c.c_int, [_P]),
+    "ldpc_hard_set_threshold": (_c.c_int, [_P, _c.c_int]),
+    "ldpc_hard_get_threshold": (_c.c_int, [_P, _c.POINTER(_c.c_int)]),
+    "ldpc_hard_decode": (_c.c_int, [_P, _P, _c.c_int64, _c.c_int32, _c.c_uint32, _P, _P, _P, _P]),
+    "ldpc_hard_simulate": (_c.c_int, [_P, _c.c_int, _c.c_double, _c.c_int, _c.c_uint64, _c.c_uint64, _c.c_uint64, _c.c_int64, _c.c_int32,
+                                      _c.c_uint32, _c.c_int32, _P, _P]),
+    "ldpc_hard_last_backend": (_c.c_int, [_P, _c.POINTER(_c.c_int)]),
+    "ldpc_hard_info": (_c.c_int, [_P, _c.POINTER(_c.c_double)]),
     "ldpc_admm_create": (_c.c_int, [_P, _c.POINTER(_P)]),
     "ldpc_admm_destroy": (_c.c_int, [_P]),
     "ldpc_admm_last_repacks": (_c.c_int, [_P, _c.POINTER(_c.c_int)]),

@@ -5,7 +5,7 @@ the stopping-set exit of src/bec.py:120; symbols are {0, 1, 2 = erased}.
 """
 import numpy as np
 
-from . import admm, registry
+from . import admm, hard, registry
 from ._device import DecoderHandle, as_code
 
 
@@ -52,6 +52,15 @@ class MSA(SPA):
 
 
 registry.add_bec_refusals(globals())  # NMSA, LMSA, QMSA, OSD: NotImplementedError, the sentence is the registry's
+
+
+class GALB:
+    """Gallager-B decodes hard decisions; the erasure channel delivers none for an erased symbol."""
+    id_keys = hard.GALB.id_keys
+
+    def __init__(self, *a, **k):
+        raise NotImplementedError("decoder GALB (hard-decision Gallager-B) does not exist over the bec: a hard-decision decoder has no erasures "
+                                  "to work on; use SPA / MSA (peeling) or ML there")
 
 
 class ADMM:  # src/bec.py:38-45,58-62: LLR wrapper with +-1e8 for the known symbols, 0 for an erasure

@@ -1,7 +1,7 @@
 """BI-AWGN channel and its LLR decoders -- mirror of the reference's ``src/biawgn.py:10-42``."""
 import numpy as np
 
-from . import admm, registry
+from . import admm, hard, registry
 
 noise_var = lambda snr_in_db: 10 ** (-snr_in_db / 10)  # noqa: E731  (src/biawgn.py:10)
 
@@ -42,6 +42,26 @@ class ADMM(LLR):  # src/biawgn.py:52-56
 
     def decode_batch(self, y):
         return self.dec.decode_batch(self.priors(np.asarray(y)))
+
+
+class GALB(LLR):  # no upstream counterpart: Gallager-B on the observation sliced where the LLR is negative (bit 1 <=> prior < 0 <=> y > 0)
+    id_keys = hard.GALB.id_keys
+
+    def __init__(self, snr_in_db, _code, **kwargs):
+        super().__init__(snr_in_db, hard.GALB(_code, **kwargs))
+
+    def _slice(self, y):
+        if hasattr(y, "is_cuda"):
+            import torch
+
+            return (self.priors(y) < 0).to(torch.uint8).contiguous()
+        return (self.priors(np.asarray(y)) < 0).astype(np.uint8)
+
+    def decode(self, y):
+        return self.dec.decode(self._slice(y))
+
+    def decode_batch(self, y):
+        return self.dec.decode_batch(self._slice(y))
 
 
 registry.add_llr_wrappers(globals(), LLR)  # SPA, MSA and this build's own (NMSA, QMSA, LMSA, OSD): LLR around the bpa class of that name

@@ -1,7 +1,7 @@
 """Binary symmetric channel and its LLR decoders -- mirror of the reference's ``src/bsc.py:11-39``."""
 import numpy as np
 
-from . import admm, registry
+from . import admm, hard, registry
 
 
 class Channel:
@@ -44,6 +44,20 @@ class ADMM(LLR):  # src/bsc.py:49-53
 
     def decode_batch(self, y):
         return self.dec.decode_batch(self.priors(np.asarray(y)))
+
+
+class GALB:  # no upstream counterpart: Gallager-B decodes the received bits themselves (``p`` plays no part in decoding)
+    id_keys = hard.GALB.id_keys
+    channel = "bsc"
+
+    def __init__(self, p, _code, **kwargs):
+        self.param, self.dec = p, hard.GALB(_code, **kwargs)
+
+    def decode(self, y):
+        return self.dec.decode(y)
+
+    def decode_batch(self, y):
+        return self.dec.decode_batch(y)
 
 
 registry.add_llr_wrappers(globals(), LLR)  # SPA, MSA and this build's own (NMSA, QMSA, LMSA, OSD): LLR around the bpa class of that name

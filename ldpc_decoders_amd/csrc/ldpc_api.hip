@@ -14,6 +14,7 @@
 #include "ldpc_common.hpp"
 #include "ldpc_bec_ml.hpp"
 #include "ldpc_encode.hpp"
+#include "ldpc_hard.hpp"
 #include "ldpc_osd.hpp"
 
 namespace ldpc {
@@ -1320,6 +1321,89 @@ int ldpc_osd_simulate(ldpc_osd_t h, ldpc_decoder_t dec, int channel, double para
         }
         return osd_simulate((Osd*)h, dec, channel, param, codeword, seed, stream_id, frame0, B, max_iter, flags, order, depth, hist_bins,
                             counters_dev, (hipStream_t)stream);
+    });
+}
+
+// ---- bit-sliced Gallager-B hard-decision decoder (ldpc_hard.hip) ----
+// no upstream counterpart (the reference decodes soft values, src/bpa.py, or erasures, src/bec.py)
+int ldpc_hard_create(ldpc_code_t code, int backend, ldpc_hard_t* out) {
+    return guarded("ldpc_hard_create", [&]() -> int {
+        if (!code || !out) {
+            set_error("ldpc_hard_create: bad arguments");
+            return LDPC_E_ARG;
+        }
+        Hard* h = nullptr;
+        LDPC_TRY(hard_create((Code*)code, backend, &h));
+        *out = (ldpc_hard_t)h;
+        return LDPC_OK;
+    });
+}
+
+int ldpc_hard_destroy(ldpc_hard_t h) {
+    return guarded("ldpc_hard_destroy", [&]() -> int {
+        hard_destroy((Hard*)h);
+        return LDPC_OK;
+    });
+}
+
+int ldpc_hard_set_threshold(ldpc_hard_t h, int t) {
+    return guarded("ldpc_hard_set_threshold", [&]() -> int {
+        if (!h) {
+            set_error("ldpc_hard_set_threshold: bad arguments");
+            return LDPC_E_ARG;
+        }
+        return hard_set_threshold((Hard*)h, t);
+    });
+}
+
+int ldpc_hard_get_threshold(ldpc_hard_t h, int* t) {
+    return guarded("ldpc_hard_get_threshold", [&]() -> int {
+        if (!h || !t) {
+            set_error("ldpc_hard_get_threshold: bad arguments");
+            return LDPC_E_ARG;
+        }
+        *t = hard_get_threshold((const Hard*)h);
+        return LDPC_OK;
+    });
+}
+
+int ldpc_hard_decode(ldpc_hard_t h, const uint8_t* y_dev, int64_t B, int32_t max_iter, uint32_t flags, uint8_t* xhat_dev, uint32_t* xhat_bits_dev,
+                     int32_t* iters_dev, void* stream) {
+    return guarded("ldpc_hard_decode", [&]() -> int {
+        if (!h || !y_dev || (!xhat_dev && !xhat_bits_dev) || !iters_dev || B < 0) {
+            set_error("ldpc_hard_decode: bad arguments (y, iters and at least one of xhat / xhat_bits are required)");
+            return LDPC_E_ARG;
+        }
+        return hard_decode((Hard*)h, y_dev, B, max_iter, flags, xhat_dev, xhat_bits_dev, iters_dev, (hipStream_t)stream);
+    });
+}
+
+// inside the loop of main.test (src/main.py:37-45)
+int ldpc_hard_simulate(ldpc_hard_t h, int channel, double param, int codeword, uint64_t seed, uint64_t stream_id, uint64_t frame0, int64_t B,
+                       int32_t max_iter, uint32_t flags, int32_t hist_bins, int64_t* counters_dev, void* stream) {
+    return guarded("ldpc_hard_simulate", [&]() -> int {
+        if (!h || !counters_dev || B < 0 || hist_bins < 0) {
+            set_error("ldpc_hard_simulate: bad arguments");
+            return LDPC_E_ARG;
+        }
+        return hard_simulate((Hard*)h, channel, param, codeword, seed, stream_id, frame0, B, max_iter, flags, hist_bins, counters_dev,
+                             (hipStream_t)stream);
+    });
+}
+
+int ldpc_hard_last_backend(ldpc_hard_t h, int* backend) {
+    return guarded("ldpc_hard_last_backend", [&]() -> int {
+        if (!h || !backend) return LDPC_E_ARG;
+        *backend = hard_last_backend((const Hard*)h);
+        return LDPC_OK;
+    });
+}
+
+int ldpc_hard_info(ldpc_hard_t h, double* out4) {
+    return guarded("ldpc_hard_info", [&]() -> int {
+        if (!h || !out4) return LDPC_E_ARG;
+        hard_info((const Hard*)h, out4);
+        return LDPC_OK;
     });
 }
 

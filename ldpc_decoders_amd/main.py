@@ -35,7 +35,7 @@ def test(args, comm=None):
     # --codeword -1 (a random codeword per frame, src/main.py:38): on the device for the BP decoders -- from the code book where the code
     # has one, from the systematic GF(2) encoder (Code.encoder()) otherwise -- and for ML over the BEC of a code without a code book (the
     # elimination decoder, encoder words); the reference's sequential loop on host noise for the others
-    device_words = row.device_words or (args.channel == "bec" and args.decoder == "ML" and code.gen_mtx is None)
+    device_words = row.device_words or row.hard or (args.channel == "bec" and args.decoder == "ML" and code.gen_mtx is None)
     exact = bool(args.exact) or (args.codeword == -1 and not device_words)
     if exact and comm.world > 1:
         raise SystemExit("--exact / --codeword -1 follow the reference's sequential rule and run on a single rank")
@@ -50,6 +50,13 @@ def test(args, comm=None):
     tie_dominated = args.channel == "bsc" and row.tie_dominated  # (OSD: NMSA in front)
     kwargs["precision"] = args.precision or ("f64" if (exact or tie_dominated) else "f32")
     # (OSD orders the soft output of an f32 / f64 decoder: fp16 storage keeps none in the decoder's type)
+    if row.hard:  # (one bit per message: nothing of a precision, a prior grid or an unbounded run applies; refused before a decoder exists)
+        if args.precision == "f16":
+            raise SystemExit("--precision f16: GALB passes one bit per message and has no arithmetic to store in fp16")
+        if getattr(args, "prior_grid", None) is not None:
+            raise SystemExit("--prior-grid: fp32 min-sum over BI-AWGN (biawgn <code> MSA, without --precision f64); GALB reads no priors")
+        if args.max_iter <= 0:
+            raise SystemExit("--max-iter must be >= 1 for GALB: a hard-decision decoder may oscillate for ever and has no exit of its own")
     if kwargs["precision"] == "f16" and (not row.f16 or args.channel == "bec" or exact):
         raise SystemExit("--precision f16 (fp16 storage of the messages): the LLR decoders SPA / MSA over biawgn / bsc, device-noise mode")
     if row.refuses_fused and args.backend == "fused":  # (refused before a decoder exists, like the two around it)
@@ -132,7 +139,7 @@ def test(args, comm=None):
 
 
 def build_parser():
-    """The reference's grammar with the reference's decoder names, plus this build's own (``registry.ROWS``: NMSA, QMSA, LMSA, OSD)."""
+    """The reference's grammar with the reference's decoder names, plus this build's own (``registry.ROWS``: NMSA, QMSA, LMSA, OSD, GALB)."""
     return utils.setup_parser(codes.get_code_names(), models.keys(), all_decoder_names)
 
 
