@@ -335,7 +335,8 @@ int ldpc_ml_simulate(ldpc_ml_t ml, int channel, int dtype, double param, int cod
  *      the solution set and depends only on the global frame index;
  *   4. nullity [B] int32: d = |R| - rank (the solution set has 2^d words; 0 for a frame peeling finished), -1 if the system is
  *      inconsistent (only possible when the sent word is no codeword; the decisions are then those of the same rule on the
- *      consistent part and are no codeword).
+ *      consistent part and are no codeword).  Under nullity -1 the word still returns every unerased symbol unchanged (the peeled ones
+ *      too); on R it holds the free bits and the pivot values of step 3, the rows left without a pivot being ignored.
  * The system of a frame lives in the LDS of one CU: create fails with LDPC_E_ARG unless the worst case (every bit erased) fits 160 KiB,
  * i.e.  4 * (3 W + 3 S + S * 64 ceil(m / 64)) <= 163840  with W = ceil(n / 32), S = ceil((n + 1) / 32)  (about m * n <= 1 310 720 bits),
  * and m <= 4096.  Handles are not thread-safe (one workspace). */

@@ -254,3 +254,71 @@ def test_cli_writes_the_reference_files(tmp_path):
     sd = np.sqrt(p0 * (1 - p0) / t0 + p1 * (1 - p1) / t1)
     print("CLI: OSD wer %g over %d frames, NMSA wer %g over %d frames" % (p0, t0, p1, t1))
     assert p0 <= p1 + 5 * sd, (p0, t0, p1, t1)
+
+
+# ---- over the BSC: ldpc_osd_decode with y0, ldpc_osd_simulate with LDPC_CH_BSC, k_osd_unswept ------------------------------------------
+
+def _bsc_frames(code, bp, B, frame0):
+    """B frames of device BSC noise at p = 0.05 on encoder words; frames 3, 300, 700 and B - 1 carry the noiseless word, so they leave at
+    the iteration-0 check of y0.  -> (priors, y0)"""
+    import torch
+
+    sent = code.encoder().handle().encode_random(SEED, STREAM, frame0, B)
+    pri, y0 = bp.channel_sent_device("bsc", 0.05, sent, SEED, STREAM, frame0)
+    llr = pri.abs().max()
+    assert bool((pri.abs() == llr).all())
+    clean = torch.tensor([3, 300, 700, B - 1], device=pri.device)
+    y0[clean] = sent[clean]
+    pri[clean] = torch.where(sent[clean] == 1, -llr, llr)
+    return pri, y0
+
+
+@pytest.mark.parametrize("precision", ["f64", "f32"])
+def test_bsc_decode_is_bp_then_the_statement(precision):
+    """ldpc_osd_decode with y0: BP's iters; a frame that left at the iteration-0 check keeps y0 (its soft output is its priors, not the
+    zeros BP leaves there); every other frame is osd_frame on BP's marginals."""
+    import torch
+
+    code = _code("512_3_6_rand_ldpc_1")
+    n, H = code.n, code.parity_mtx.astype(np.uint8)
+    bp, osd = _handles(code, precision)
+    pri, y0 = _bsc_frames(code, bp, 1024, 0)
+    xhat, iters, pick = osd.decode_device(pri, y0, 20, order=1, depth=64)
+    _, ibp, marg = bp.decode_soft_device(pri, y0, 20)
+    assert torch.equal(iters, ibp)
+    left = ibp == 0
+    assert int(left.sum()) >= 4 and bool((pick[left] == -1).all()) and torch.equal(xhat[left], y0[left])
+    post = torch.where(left[:, None], pri, marg)
+    po, pr, x, pk = post.cpu().numpy(), pri.cpu().numpy(), xhat.cpu().numpy(), pick.cpu().numpy()
+    h = OSD.hard(po)
+    listed = np.flatnonzero(((h.astype(np.int64) @ H.T.astype(np.int64)) % 2).any(axis=1))
+    passed = np.setdiff1d(np.arange(len(po)), listed)
+    print("bsc %s: %d listed, %d left at the iteration-0 check" % (precision, len(listed), int(left.sum())))
+    assert len(listed) >= 8
+    assert (x[passed] == h[passed]).all() and (pk[passed] == -1).all() and (pk[listed] >= 0).all()
+    for f in listed[np.linspace(0, len(listed) - 1, min(64, len(listed))).astype(int)]:
+        want_x, want_t, _ = OSD.osd_frame(H, po[f], pr[f], 1, 64)
+        assert pk[f] == want_t and (x[f] == want_x).all(), (precision, int(f), pk[f], want_t)
+    assert int(_syndrome_dev(code, xhat).max()) == 0
+
+
+@pytest.mark.parametrize("precision", ["f64", "f32"])
+def test_bsc_simulate_counts_what_decode_returns(precision):
+    import torch
+    from ldpc_decoders_amd import _lib
+
+    code = _code("512_3_6_rand_ldpc_1")
+    n, B, bins, frame0 = code.n, 4096, 21, 1000
+    bp, osd = _handles(code, precision)
+    osd.order, osd.depth = 1, 64
+    c_bp, c_osd, c_hand = (torch.zeros(4 + bins, dtype=torch.int64, device="cuda") for _ in range(3))
+    bp.simulate("bsc", 0.05, 0, SEED, STREAM, frame0, B, 20, c_bp, hist_bins=bins)
+    osd.simulate("bsc", 0.05, 0, SEED, STREAM, frame0, B, 20, c_osd, hist_bins=bins)
+    pri, y0 = bp.channel_device("bsc", 0.05, 0, SEED, STREAM, frame0, B)
+    xhat, iters, pick = osd.decode_device(pri, y0, 20)
+    _count(_lib.load(), xhat, None, iters, n, bins, c_hand)
+    a, b, c = c_bp.cpu().numpy(), c_osd.cpu().numpy(), c_hand.cpu().numpy()
+    print("bsc %s: BP %s, OSD %s" % (precision, a[:4], b[:4]))
+    assert (b == c).all()
+    assert a[_lib.CNT_TOT] == b[_lib.CNT_TOT] == B and a[_lib.CNT_ITER_SUM] == b[_lib.CNT_ITER_SUM] and (a[4:] == b[4:]).all()
+    assert int((pick >= 0).sum()) >= 8 and b[_lib.CNT_WEC] <= a[_lib.CNT_WEC]
