@@ -3,7 +3,8 @@
 # (/root/reference must exist; nothing here runs on the GPU box).  Each file has exactly one writer:
 #   make_goldens.py         codes_edges.npz, kat.json, decode_*.npz, main_counters.json
 #   make_goldens_ml.py      ml_vectors.npz, ml_cases.json, ml_kat.json, main_counters_ml.json
-#   make_goldens_admm.py    admm_vectors.npz, admm_cases.json, main_counters_admm.json   (needs oracle/_ref/libppolytope.so: make -C oracle)
+#   make_goldens_admm.py    admm_vectors.npz, admm_cases.json, main_counters_admm.json, admm_edge_vectors.npz, admm_edge_cases.json
+#                           (needs oracle/_ref/libppolytope.so: make -C oracle)
 #   make_goldens_gen.py     irregular_ensembles.json
 #   make_goldens_curves.py  published_curves.json, reference_checks.json
 #   make_goldens_codes.py   ldpc_decoders_amd/data/codes/*.txt
