@@ -453,6 +453,63 @@ int ldpc_hard_last_backend(ldpc_hard_t h, int* backend);
  * kernel is not available for this code), workgroups of the LDS kernel's grid} */
 int ldpc_hard_info(ldpc_hard_t h, double* out4);
 
+/* ---- Layered fixed-point min-sum, LDS-resident (LQMSA) -----------------------------------------------------------
+ * No upstream counterpart: LDPC_ALG_QMSA's integer rule on LDPC_ALG_LMSA's schedule, the whole frame resident in the LDS as integers
+ * (int16 marginals, int8 check messages).  Everything after the quantiser is an integer.
+ *   Parameters (handle state, ldpc_lqmsa_set_fixed_point; after create 6, 2, 0.8125, 0): bits q in 2..8, V = 2^(q-1) - 1 <= 127;
+ *      frac_bits k in -8..8; scale a multiple of 1/64 with 0 < scale <= 1, scale64 = 64 scale; offset an integer >= 0 in levels.
+ *      Layers (ldpc_lqmsa_set_layers): validity rule, greedy default and processing order -- ascending (layer, check index) -- are
+ *      exactly those of LDPC_ALG_LMSA.
+ *   1. Quantiser.  level_v = clamp(rint(prior_v * 2^k), -V, V) in the type the priors arrive in (fp32 or fp64): LDPC_ALG_QMSA's
+ *      quantiser, the same levels (+-inf -> +-V, -0 -> 0); what it leaves undefined (NaN) is undefined here.
+ *   2. Init and exits.  marg = level, every c2v = 0, x_hat = y0 if given.  Exits as BPA.decode (src/bpa.py:17-63): before each sweep,
+ *      stop at max_iter (<= 0: unbounded, capped at 100000), or when H x_hat = 0 -- checked from sweep 1 on, at sweep 0 only when y0 is
+ *      given.  LDPC_FLAG_NO_EARLY_EXIT runs exactly max_iter sweeps.  iters = sweeps executed.
+ *   3. One sweep.  For every check in processing order, with its edges j in H's row-major order:
+ *          v_j   = marg[var_j] - c2v_j
+ *          a_j   = min(|v_j|, V);   neg_j = (v_j < 0)
+ *          m_j   = min over i != j of a_i;   s_j = XOR over i != j of neg_i
+ *          c2v_j = (s_j ? -1 : +1) * max( ((scale64 * m_j) >> 6) - offset, 0 )
+ *          marg[var_j] = v_j + c2v_j                    (v_j itself is NOT clipped)
+ *      After the last layer x_hat = (marg < 0).  Invariant: marg_v = level_v + sum of c2v, so |marg| <= V (1 + dv) and int16 holds it
+ *      for every dv <= 255.  A variable of degree 0 keeps its level.
+ *   4. Outputs.  xhat as bytes and / or packed words (layout of ldpc_decode_bits), iters, optionally soft: int16 [B, n], the marginals
+ *      in levels of each frame's last executed sweep, 0 where it never swept.
+ *   5. Refusals.  ldpc_lqmsa_create, LDPC_E_UNSUPPORTED: a check of degree < 2 (as LDPC_ALG_LMSA), a variable of degree above 255, a
+ *      code whose frame does not fit the LDS rule below (use LDPC_ALG_LMSA for it).  ldpc_lqmsa_set_fixed_point, LDPC_E_ARG: a
+ *      parameter out of range or a scale off the 1/64 grid.  ldpc_lqmsa_set_layers, LDPC_E_ARG: a bad layering; the previous one stays
+ *      in force, as with ldpc_decoder_set_layers.
+ * Determinism: decisions, iteration counts and soft outputs are one function of (H, layers, parameters, priors, y0, max_iter, flags): the
+ * same for any batch size, any position of a frame in its batch and any number of waves per frame.
+ * Kernel.  One workgroup of W waves (W in {1, 2, 4, 8}) owns one frame for all its sweeps, lane = check, a barrier per layer; frames are
+ * handed out by an atomic dispenser.  HBM sees the priors in and the word, iters and the optional soft output out, once.  LDS rule:
+ *     lqmsa_lds_bytes(m, n, E, dc_max) = 8 ceil(2 n / 8) + m * row(dc_max) + 16 <= 163840,   row(d) = 8 for d <= 8, else 4 ceil(d / 4)
+ * (n int16 marginals, one row of int8 messages per check, 16 bytes of frame state; E does not enter), and n <= 65536 (16-bit index
+ * tables; implied by the rule for every code without 2^14 variables of degree 0).  With F = floor(163840 / bytes) frames in a CU's LDS, W is the
+ * smallest of 1, 2, 4, 8 that gives the CU the most waves, min(F, 32 / W) * W: 1 from F = 32 on, 2 from 16, 4 from 8, 8 below; the environment variable LDPC_LQMSA_NW (1, 2, 4, 8; read at create) overrides it.
+ * Handles are not thread-safe (one workspace). */
+typedef struct ldpc_lqmsa_s* ldpc_lqmsa_t;
+int ldpc_lqmsa_create(ldpc_code_t code, ldpc_lqmsa_t* out);
+int ldpc_lqmsa_destroy(ldpc_lqmsa_t h);
+/* Word length and correction; ranges above.  Handle state, read when a call is enqueued. */
+int ldpc_lqmsa_set_fixed_point(ldpc_lqmsa_t h, int bits, int frac_bits, double scale, int offset);
+int ldpc_lqmsa_get_fixed_point(ldpc_lqmsa_t h, int* bits, int* frac_bits, double* scale, int* offset);
+/* The layering, with the semantics of ldpc_decoder_set_layers / _get_layers: layer_of_check_host[m], NULL restores the greedy layering; a
+ * refused call leaves the previous layering in force and the handle usable; the call waits for the whole device. */
+int ldpc_lqmsa_set_layers(ldpc_lqmsa_t h, const int32_t* layer_of_check_host, int32_t m);
+int ldpc_lqmsa_get_layers(ldpc_lqmsa_t h, int32_t* nlayers, int32_t* layer_of_check_host_or_NULL);
+/* Steps 1-4 for B frames.  priors_dev [B, n] float or double per `dtype` (LDPC_DTYPE_F32 / _F64); y0_dev [B, n] uint8 or NULL; xhat_dev
+ * [B, n] uint8 or NULL; xhat_bits_dev [B, W] uint32 or NULL (at least one of the two); iters_dev [B] int32; soft_dev [B, n] int16 or NULL. */
+int ldpc_lqmsa_decode(ldpc_lqmsa_t h, int dtype, const void* priors_dev, const uint8_t* y0_dev, int64_t B, int32_t max_iter, uint32_t flags,
+                      uint8_t* xhat_dev, uint32_t* xhat_bits_dev, int32_t* iters_dev, int16_t* soft_dev, void* stream);
+/* ldpc_channel (fp32 priors) + ldpc_lqmsa_decode + ldpc_count_errors_bits for frames [frame0, frame0+B) of the all-`codeword` word, with
+ * the call shape and counters of ldpc_hard_simulate.  LDPC_CH_BIAWGN and LDPC_CH_BSC (the received word takes the iteration-0 check);
+ * codeword 0 or 1; 1 is refused (LDPC_E_ARG) when a check has odd degree. */
+int ldpc_lqmsa_simulate(ldpc_lqmsa_t h, int channel, double param, int codeword, uint64_t seed, uint64_t stream_id, uint64_t frame0, int64_t B,
+                        int32_t max_iter, uint32_t flags, int32_t hist_bins, int64_t* counters_dev, void* stream);
+/* out4 = {LDS bytes per frame, waves per frame, frames per CU as launched, workgroups of the kernel's grid} */
+int ldpc_lqmsa_info(ldpc_lqmsa_t h, double* out4);
+
 /* ---- ADMM LP decoding ------------------------------------------------------------------------------------------
  * Replaces admm.ADMM (src/admm.py:9-77) together with its native projection (src/parity_polytope/projection.cpp:30-275, bound
  * upstream through ctypes in exact.py:12-53).  Check degrees up to 16. */

@@ -825,6 +825,107 @@ class HardHandle:
             _lib.check(lib.ldpc_count_errors_words(xhat.data_ptr(), sent.data_ptr(), iters.data_ptr(), nb, n, hist_bins, counters.data_ptr(), st))
 
 
+class LqmsaHandle:
+    """Layered fixed-point min-sum with the frame resident in the LDS as integers (``ldpc_lqmsa_*``): one workgroup per frame, int16
+    marginals, int8 check messages; priors in fp32 or fp64, quantised on load."""
+
+    def __init__(self, code, device=None, bits=6, frac_bits=2, scale=0.8125, offset=0):
+        lib = _lib.load()
+        self.code_handle = code_handle(code, device)
+        self.code, self.device = code, self.code_handle.device
+        h = ctypes.c_void_p()
+        _lib.check(lib.ldpc_lqmsa_create(self.code_handle.h, ctypes.byref(h)))
+        self.h = h
+        self.set_fixed_point(bits, frac_bits, scale, offset)
+
+    def __del__(self):
+        try:
+            if getattr(self, "h", None):
+                _lib.load().ldpc_lqmsa_destroy(self.h)
+                self.h = None
+        except Exception:
+            pass
+
+    def set_fixed_point(self, bits, frac_bits, scale, offset=0):
+        _lib.check(_lib.load().ldpc_lqmsa_set_fixed_point(self.h, int(bits), int(frac_bits), float(scale), int(offset)))
+
+    def fixed_point(self):
+        b, k, o, s = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0), ctypes.c_double(0)
+        _lib.check(_lib.load().ldpc_lqmsa_get_fixed_point(self.h, ctypes.byref(b), ctypes.byref(k), ctypes.byref(s), ctypes.byref(o)))
+        return b.value, k.value, s.value, o.value
+
+    def set_layers(self, layers=None):
+        """``layers``: one non-negative int per check (two checks of one layer share no variable), or None for the greedy layering."""
+        if layers is None:
+            _lib.check(_lib.load().ldpc_lqmsa_set_layers(self.h, None, 0))
+            return
+        lay = np.ascontiguousarray(check_layers(self.code, layers), dtype=np.int32)
+        _lib.check(_lib.load().ldpc_lqmsa_set_layers(self.h, lay.ctypes.data, lay.size))
+
+    def layers(self):
+        """-> (number of layers, layer of every check as int32 [m])"""
+        nl, lay = ctypes.c_int32(0), np.empty(self.code.m, dtype=np.int32)
+        _lib.check(_lib.load().ldpc_lqmsa_get_layers(self.h, ctypes.byref(nl), lay.ctypes.data))
+        return nl.value, lay
+
+    def info(self):
+        out = (ctypes.c_double * 4)()
+        _lib.check(_lib.load().ldpc_lqmsa_info(self.h, out))
+        return dict(zip(("lds_bytes_per_frame", "waves_per_frame", "frames_per_cu", "workgroups"), (int(v) for v in out)))
+
+    def decode_device(self, priors, y0, max_iter, flags=0, bits=False, soft=False):
+        """priors: contiguous CUDA float32 / float64 [B, n]; y0: CUDA uint8 [B, n] or None -> (xhat uint8 [B, n], iters int32 [B]), with
+        ``bits`` the packed words int32 [B, ceil(n/32)] and with ``soft`` the marginals in levels int16 [B, n] appended."""
+        import torch
+
+        n = self.code.n
+        if not getattr(priors, "is_cuda", False) or priors.dtype not in (torch.float32, torch.float64) or not priors.is_contiguous() \
+                or priors.dim() != 2 or priors.shape[1] != n:
+            raise ValueError("priors must be a contiguous CUDA float32 or float64 tensor [B, %d]" % n)
+        B = priors.shape[0]
+        if y0 is not None and (not getattr(y0, "is_cuda", False) or y0.dtype != torch.uint8 or not y0.is_contiguous() or tuple(y0.shape) != (B, n)):
+            raise ValueError("y0 must be a contiguous CUDA uint8 tensor [%d, %d]" % (B, n))
+        dev = priors.device
+        xhat = torch.empty((B, n), dtype=torch.uint8, device=dev)
+        iters = torch.empty((B,), dtype=torch.int32, device=dev)
+        words = torch.empty((B, (n + 31) // 32), dtype=torch.int32, device=dev) if bits else None
+        marg = torch.empty((B, n), dtype=torch.int16, device=dev) if soft else None
+        if B:
+            st = torch.cuda.current_stream(dev).cuda_stream
+            _lib.check(_lib.load().ldpc_lqmsa_decode(self.h, _lib.DTYPE["f64" if priors.dtype == torch.float64 else "f32"], priors.data_ptr(),
+                                                     None if y0 is None else y0.data_ptr(), B, int(max_iter), flags, xhat.data_ptr(),
+                                                     None if words is None else words.data_ptr(), iters.data_ptr(),
+                                                     None if marg is None else marg.data_ptr(), st))
+        return (xhat, iters) + ((words,) if bits else ()) + ((marg,) if soft else ())
+
+    def simulate(self, channel, param, codeword, seed, stream_id, frame0, B, max_iter, counters, flags=0, hist_bins=0):
+        """Same call shape as DecoderHandle.simulate: channel -> LLR -> decode -> count on the device (``ldpc_lqmsa_simulate``).
+        ``codeword == -1``: random codewords from the systematic encoder (``Code.encoder()``) through ``ldpc_channel_sent``."""
+        import torch
+
+        if channel not in ("biawgn", "bsc"):
+            raise ValueError("layered fixed-point min-sum works on the LLR channels (biawgn, bsc)")
+        if B <= 0:
+            return
+        lib = _lib.load()
+        st = torch.cuda.current_stream(counters.device).cuda_stream
+        if int(codeword) != -1:
+            _lib.check(lib.ldpc_lqmsa_simulate(self.h, _lib.CHANNEL[channel], float(param), int(codeword), int(seed), int(stream_id), int(frame0),
+                                               int(B), int(max_iter), flags, hist_bins, counters.data_ptr(), st))
+            return
+        n, enc = self.code.n, self.code.encoder().handle(self.device)
+        step = max(2048, min(1 << 17, (1 << 26) // n))
+        for b0 in range(0, int(B), step):
+            nb = min(step, int(B) - b0)
+            sent = enc.encode_random(seed, stream_id, int(frame0) + b0, nb)
+            pri = torch.empty((nb, n), dtype=torch.float32, device=sent.device)
+            y = torch.empty((nb, n), dtype=torch.uint8, device=sent.device) if channel == "bsc" else None
+            _lib.check(lib.ldpc_channel_sent(_lib.CHANNEL[channel], _lib.DTYPE["f32"], float(param), sent.data_ptr(), int(seed), int(stream_id),
+                                             int(frame0) + b0, nb, n, pri.data_ptr(), None if y is None else y.data_ptr(), st))
+            xhat, iters = self.decode_device(pri, y, max_iter, flags)
+            _lib.check(lib.ldpc_count_errors_words(xhat.data_ptr(), sent.data_ptr(), iters.data_ptr(), nb, n, hist_bins, counters.data_ptr(), st))
+
+
 class AdmmHandle:
     """ADMM LP decoder workspace on one GPU (``ldpc_admm_*``)."""
 

@@ -112,6 +112,16 @@ SIGNATURES = {
                                       _c.c_uint32, _c.c_int32, _P, _P]),
     "ldpc_hard_last_backend": (_c.c_int, [_P, _c.POINTER(_c.c_int)]),
     "ldpc_hard_info": (_c.c_int, [_P, _c.POINTER(_c.c_double)]),
+    "ldpc_lqmsa_create": (_c.c_int, [_P, _c.POINTER(_P)]),
+    "ldpc_lqmsa_destroy": (_c.c_int, [_P]),
+    "ldpc_lqmsa_set_fixed_point": (_c.c_int, [_P, _c.c_int, _c.c_int, _c.c_double, _c.c_int]),
+    "ldpc_lqmsa_get_fixed_point": (_c.c_int, [_P, _c.POINTER(_c.c_int), _c.POINTER(_c.c_int), _c.POINTER(_c.c_double), _c.POINTER(_c.c_int)]),
+    "ldpc_lqmsa_set_layers": (_c.c_int, [_P, _P, _c.c_int32]),
+    "ldpc_lqmsa_get_layers": (_c.c_int, [_P, _c.POINTER(_c.c_int32), _P]),
+    "ldpc_lqmsa_decode": (_c.c_int, [_P, _c.c_int, _P, _P, _c.c_int64, _c.c_int32, _c.c_uint32, _P, _P, _P, _P, _P]),
+    "ldpc_lqmsa_simulate": (_c.c_int, [_P, _c.c_int, _c.c_double, _c.c_int, _c.c_uint64, _c.c_uint64, _c.c_uint64, _c.c_int64, _c.c_int32,
+                                       _c.c_uint32, _c.c_int32, _P, _P]),
+    "ldpc_lqmsa_info": (_c.c_int, [_P, _c.POINTER(_c.c_double)]),
     "ldpc_admm_create": (_c.c_int, [_P, _c.POINTER(_P)]),
     "ldpc_admm_destroy": (_c.c_int, [_P]),
     "ldpc_admm_last_repacks": (_c.c_int, [_P, _c.POINTER(_c.c_int)]),

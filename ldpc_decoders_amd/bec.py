@@ -5,7 +5,7 @@ the stopping-set exit of src/bec.py:120; symbols are {0, 1, 2 = erased}.
 """
 import numpy as np
 
-from . import admm, hard, registry
+from . import admm, hard, layered, registry
 from ._device import DecoderHandle, as_code
 
 
@@ -61,6 +61,15 @@ class GALB:
     def __init__(self, *a, **k):
         raise NotImplementedError("decoder GALB (hard-decision Gallager-B) does not exist over the bec: a hard-decision decoder has no erasures "
                                   "to work on; use SPA / MSA (peeling) or ML there")
+
+
+class LQMSA:
+    """Layered fixed-point min-sum quantises and scales magnitudes; the ternary erasure decoder has none."""
+    id_keys = layered.LQMSA.id_keys
+
+    def __init__(self, *a, **k):
+        raise NotImplementedError("decoder LQMSA (layered fixed-point min-sum) does not exist over the bec: the erasure decoder has no "
+                                  "magnitudes to quantise; use SPA / MSA there")
 
 
 class ADMM:  # src/bec.py:38-45,58-62: LLR wrapper with +-1e8 for the known symbols, 0 for an erasure

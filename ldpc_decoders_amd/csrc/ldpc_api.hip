@@ -15,6 +15,7 @@
 #include "ldpc_bec_ml.hpp"
 #include "ldpc_encode.hpp"
 #include "ldpc_hard.hpp"
+#include "ldpc_lqmsa.hpp"
 #include "ldpc_osd.hpp"
 
 namespace ldpc {
@@ -1403,6 +1404,102 @@ int ldpc_hard_info(ldpc_hard_t h, double* out4) {
     return guarded("ldpc_hard_info", [&]() -> int {
         if (!h || !out4) return LDPC_E_ARG;
         hard_info((const Hard*)h, out4);
+        return LDPC_OK;
+    });
+}
+
+// ---- layered fixed-point min-sum, LDS-resident (ldpc_lqmsa.hip) ----
+// no upstream counterpart (BPA.decode, src/bpa.py:17-63, runs the flooding schedule in floating point)
+int ldpc_lqmsa_create(ldpc_code_t code, ldpc_lqmsa_t* out) {
+    return guarded("ldpc_lqmsa_create", [&]() -> int {
+        if (!code || !out) {
+            set_error("ldpc_lqmsa_create: bad arguments");
+            return LDPC_E_ARG;
+        }
+        Lqmsa* h = nullptr;
+        LDPC_TRY(lqmsa_create((Code*)code, &h));
+        *out = (ldpc_lqmsa_t)h;
+        return LDPC_OK;
+    });
+}
+
+int ldpc_lqmsa_destroy(ldpc_lqmsa_t h) {
+    return guarded("ldpc_lqmsa_destroy", [&]() -> int {
+        lqmsa_destroy((Lqmsa*)h);
+        return LDPC_OK;
+    });
+}
+
+int ldpc_lqmsa_set_fixed_point(ldpc_lqmsa_t h, int bits, int frac_bits, double scale, int offset) {
+    return guarded("ldpc_lqmsa_set_fixed_point", [&]() -> int {
+        if (!h) {
+            set_error("ldpc_lqmsa_set_fixed_point: bad arguments");
+            return LDPC_E_ARG;
+        }
+        return lqmsa_set_fixed_point((Lqmsa*)h, bits, frac_bits, scale, offset);
+    });
+}
+
+int ldpc_lqmsa_get_fixed_point(ldpc_lqmsa_t h, int* bits, int* frac_bits, double* scale, int* offset) {
+    return guarded("ldpc_lqmsa_get_fixed_point", [&]() -> int {
+        if (!h || !bits || !frac_bits || !scale || !offset) {
+            set_error("ldpc_lqmsa_get_fixed_point: a handle and four result pointers are needed");
+            return LDPC_E_ARG;
+        }
+        lqmsa_get_fixed_point((const Lqmsa*)h, bits, frac_bits, scale, offset);
+        return LDPC_OK;
+    });
+}
+
+int ldpc_lqmsa_set_layers(ldpc_lqmsa_t h, const int32_t* layer_of_check_host, int32_t m) {
+    return guarded("ldpc_lqmsa_set_layers", [&]() -> int {
+        if (!h) {
+            set_error("ldpc_lqmsa_set_layers: bad arguments");
+            return LDPC_E_ARG;
+        }
+        return lqmsa_set_layers((Lqmsa*)h, layer_of_check_host, m);
+    });
+}
+
+int ldpc_lqmsa_get_layers(ldpc_lqmsa_t h, int32_t* nlayers, int32_t* layer_of_check_host) {
+    return guarded("ldpc_lqmsa_get_layers", [&]() -> int {
+        if (!h || !nlayers) {
+            set_error("ldpc_lqmsa_get_layers: a handle and a result pointer are needed");
+            return LDPC_E_ARG;
+        }
+        lqmsa_get_layers((const Lqmsa*)h, nlayers, layer_of_check_host);
+        return LDPC_OK;
+    });
+}
+
+int ldpc_lqmsa_decode(ldpc_lqmsa_t h, int dtype, const void* priors_dev, const uint8_t* y0_dev, int64_t B, int32_t max_iter, uint32_t flags,
+                      uint8_t* xhat_dev, uint32_t* xhat_bits_dev, int32_t* iters_dev, int16_t* soft_dev, void* stream) {
+    return guarded("ldpc_lqmsa_decode", [&]() -> int {
+        if (!h || !priors_dev || (!xhat_dev && !xhat_bits_dev) || !iters_dev || B < 0) {
+            set_error("ldpc_lqmsa_decode: bad arguments (priors, iters and at least one of xhat / xhat_bits are required)");
+            return LDPC_E_ARG;
+        }
+        return lqmsa_decode((Lqmsa*)h, dtype, priors_dev, y0_dev, B, max_iter, flags, xhat_dev, xhat_bits_dev, iters_dev, soft_dev, (hipStream_t)stream);
+    });
+}
+
+// inside the loop of main.test (src/main.py:37-45)
+int ldpc_lqmsa_simulate(ldpc_lqmsa_t h, int channel, double param, int codeword, uint64_t seed, uint64_t stream_id, uint64_t frame0, int64_t B,
+                        int32_t max_iter, uint32_t flags, int32_t hist_bins, int64_t* counters_dev, void* stream) {
+    return guarded("ldpc_lqmsa_simulate", [&]() -> int {
+        if (!h || !counters_dev || B < 0 || hist_bins < 0) {
+            set_error("ldpc_lqmsa_simulate: bad arguments");
+            return LDPC_E_ARG;
+        }
+        return lqmsa_simulate((Lqmsa*)h, channel, param, codeword, seed, stream_id, frame0, B, max_iter, flags, hist_bins, counters_dev,
+                              (hipStream_t)stream);
+    });
+}
+
+int ldpc_lqmsa_info(ldpc_lqmsa_t h, double* out4) {
+    return guarded("ldpc_lqmsa_info", [&]() -> int {
+        if (!h || !out4) return LDPC_E_ARG;
+        lqmsa_info((const Lqmsa*)h, out4);
         return LDPC_OK;
     });
 }
