@@ -510,6 +510,49 @@ int ldpc_lqmsa_simulate(ldpc_lqmsa_t h, int channel, double param, int codeword,
 /* out4 = {LDS bytes per frame, waves per frame, frames per CU as launched, workgroups of the kernel's grid} */
 int ldpc_lqmsa_info(ldpc_lqmsa_t h, double* out4);
 
+/* ---- Quasi-cyclic codes: shift-addressed layered fixed-point min-sum (QCMSA) ---------------------------------------
+ * No upstream counterpart.  H is an mb x nb array of Z x Z blocks, each zero or a cyclically shifted identity: block (i, j) with shift
+ * s, 0 <= s < Z, has its ones at (i Z + r, j Z + (r + s) mod Z), r = 0 .. Z - 1.  ldpc_qc_create finds the shifts from the code's own
+ * edge list for the lifting size Z it is given (no new file format; Z = 1 takes any code and makes every check a layer).
+ *   Contract.  The outputs are those of the LQMSA statement above (its steps 1-4: quantiser, init and exits, one sweep, outputs) on the
+ *      expanded H with every block row one layer:  layer[c] = position of block row c / Z in the processing order (ldpc_qc_set_order;
+ *      after create the natural order 0 .. mb - 1).  A block row's checks touch disjoint variables, and every value is an integer, so
+ *      the result depends neither on the order of a check's edges nor on the order of the checks within a layer: ldpc_lqmsa_decode
+ *      with that layering returns the same bytes, words, iteration counts and soft outputs.
+ *   Parameters (ldpc_qc_set_fixed_point): ranges and defaults of ldpc_lqmsa_set_fixed_point (after create 6, 2, 0.8125, 0).
+ *   Refusals.  ldpc_qc_create, LDPC_E_ARG: Z < 1, or Z does not divide m and n.  LDPC_E_UNSUPPORTED: a block that is neither zero nor one
+ *      shifted identity (the message names the block; use ldpc_lqmsa_create for such a code); a block row of degree < 2; a variable of
+ *      degree above 255; a frame that does not fit the LDS rule below.  ldpc_qc_set_order, LDPC_E_ARG: anything but a permutation of
+ *      0 .. mb - 1; the previous order stays in force and the handle usable.
+ * Determinism: as LQMSA -- one function of (H, Z, order, parameters, priors, y0, max_iter, flags), the same for any batch size, any
+ * position of a frame in its batch and any number of waves per frame.
+ * Kernel.  One workgroup of W waves (W in {1, 2, 4, 8}) owns one frame for all its sweeps; lane L of pass k of block row i owns check
+ * i Z + 64 k + L and reaches variable j Z + (r + s) mod Z from its row r and two wave-uniform scalars: no index table; the block row's
+ * degree is wave-uniform and selects a body unrolled at compile time (degrees 2..8; a loop above).  A barrier per block row; frames
+ * from an atomic dispenser.  LDS rule: LQMSA's layout and bound with dc_max = the largest block-row degree,
+ *     lqmsa_lds_bytes(m, n, E, dc_max) = 8 ceil(2 n / 8) + m * row(dc_max) + 16 <= 163840.
+ * With F = floor(163840 / bytes), W is LQMSA's rule for F capped at the smallest of 1, 2, 4, 8 that is >= ceil(Z / 64) (a block row has
+ * ceil(Z / 64) wave passes); the environment variable LDPC_QC_NW (1, 2, 4, 8; read at create) overrides it.  With Z < 64 part of the
+ * wave idles.  Handles are not thread-safe (one workspace). */
+typedef struct ldpc_qc_s* ldpc_qc_t;
+int ldpc_qc_create(ldpc_code_t code, int32_t Z, ldpc_qc_t* out);
+int ldpc_qc_destroy(ldpc_qc_t h);
+/* Word length and correction; ranges of ldpc_lqmsa_set_fixed_point.  Handle state, read when a call is enqueued. */
+int ldpc_qc_set_fixed_point(ldpc_qc_t h, int bits, int frac_bits, double scale, int offset);
+int ldpc_qc_get_fixed_point(ldpc_qc_t h, int* bits, int* frac_bits, double* scale, int* offset);
+/* The detected base: mb, nb, Z and, unless NULL, shifts_host[mb * nb] row-major, -1 for a zero block. */
+int ldpc_qc_get_base(ldpc_qc_t h, int32_t* mb, int32_t* nb, int32_t* Z, int32_t* shifts_host_or_NULL);
+/* The processing order of the block rows: order_host[mb], a permutation of 0 .. mb - 1 (block row processed at each position); NULL
+ * restores the natural order.  The call waits for the whole device. */
+int ldpc_qc_set_order(ldpc_qc_t h, const int32_t* order_host_or_NULL, int32_t mb);
+int ldpc_qc_get_order(ldpc_qc_t h, int32_t* mb, int32_t* order_host_or_NULL);
+/* Argument lists and semantics of ldpc_lqmsa_decode / ldpc_lqmsa_simulate / ldpc_lqmsa_info. */
+int ldpc_qc_decode(ldpc_qc_t h, int dtype, const void* priors_dev, const uint8_t* y0_dev, int64_t B, int32_t max_iter, uint32_t flags,
+                   uint8_t* xhat_dev, uint32_t* xhat_bits_dev, int32_t* iters_dev, int16_t* soft_dev, void* stream);
+int ldpc_qc_simulate(ldpc_qc_t h, int channel, double param, int codeword, uint64_t seed, uint64_t stream_id, uint64_t frame0, int64_t B,
+                     int32_t max_iter, uint32_t flags, int32_t hist_bins, int64_t* counters_dev, void* stream);
+int ldpc_qc_info(ldpc_qc_t h, double* out4);
+
 /* ---- ADMM LP decoding ------------------------------------------------------------------------------------------
  * Replaces admm.ADMM (src/admm.py:9-77) together with its native projection (src/parity_polytope/projection.cpp:30-275, bound
  * upstream through ctypes in exact.py:12-53).  Check degrees up to 16. */

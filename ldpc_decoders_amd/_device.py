@@ -828,6 +828,10 @@ class HardHandle:
 class LqmsaHandle:
     """Layered fixed-point min-sum with the frame resident in the LDS as integers (``ldpc_lqmsa_*``): one workgroup per frame, int16
     marginals, int8 check messages; priors in fp32 or fp64, quantised on load."""
+    family = "ldpc_lqmsa"  # the handle family of the C ABI the calls below go to (QcHandle: the same call shapes under ldpc_qc_*)
+
+    def _fn(self, name):
+        return getattr(_lib.load(), "%s_%s" % (self.family, name))
 
     def __init__(self, code, device=None, bits=6, frac_bits=2, scale=0.8125, offset=0):
         lib = _lib.load()
@@ -841,17 +845,17 @@ class LqmsaHandle:
     def __del__(self):
         try:
             if getattr(self, "h", None):
-                _lib.load().ldpc_lqmsa_destroy(self.h)
+                self._fn("destroy")(self.h)
                 self.h = None
         except Exception:
             pass
 
     def set_fixed_point(self, bits, frac_bits, scale, offset=0):
-        _lib.check(_lib.load().ldpc_lqmsa_set_fixed_point(self.h, int(bits), int(frac_bits), float(scale), int(offset)))
+        _lib.check(self._fn("set_fixed_point")(self.h, int(bits), int(frac_bits), float(scale), int(offset)))
 
     def fixed_point(self):
         b, k, o, s = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0), ctypes.c_double(0)
-        _lib.check(_lib.load().ldpc_lqmsa_get_fixed_point(self.h, ctypes.byref(b), ctypes.byref(k), ctypes.byref(s), ctypes.byref(o)))
+        _lib.check(self._fn("get_fixed_point")(self.h, ctypes.byref(b), ctypes.byref(k), ctypes.byref(s), ctypes.byref(o)))
         return b.value, k.value, s.value, o.value
 
     def set_layers(self, layers=None):
@@ -870,7 +874,7 @@ class LqmsaHandle:
 
     def info(self):
         out = (ctypes.c_double * 4)()
-        _lib.check(_lib.load().ldpc_lqmsa_info(self.h, out))
+        _lib.check(self._fn("info")(self.h, out))
         return dict(zip(("lds_bytes_per_frame", "waves_per_frame", "frames_per_cu", "workgroups"), (int(v) for v in out)))
 
     def decode_device(self, priors, y0, max_iter, flags=0, bits=False, soft=False):
@@ -892,10 +896,10 @@ class LqmsaHandle:
         marg = torch.empty((B, n), dtype=torch.int16, device=dev) if soft else None
         if B:
             st = torch.cuda.current_stream(dev).cuda_stream
-            _lib.check(_lib.load().ldpc_lqmsa_decode(self.h, _lib.DTYPE["f64" if priors.dtype == torch.float64 else "f32"], priors.data_ptr(),
-                                                     None if y0 is None else y0.data_ptr(), B, int(max_iter), flags, xhat.data_ptr(),
-                                                     None if words is None else words.data_ptr(), iters.data_ptr(),
-                                                     None if marg is None else marg.data_ptr(), st))
+            _lib.check(self._fn("decode")(self.h, _lib.DTYPE["f64" if priors.dtype == torch.float64 else "f32"], priors.data_ptr(),
+                                          None if y0 is None else y0.data_ptr(), B, int(max_iter), flags, xhat.data_ptr(),
+                                          None if words is None else words.data_ptr(), iters.data_ptr(),
+                                          None if marg is None else marg.data_ptr(), st))
         return (xhat, iters) + ((words,) if bits else ()) + ((marg,) if soft else ())
 
     def simulate(self, channel, param, codeword, seed, stream_id, frame0, B, max_iter, counters, flags=0, hist_bins=0):
@@ -910,8 +914,8 @@ class LqmsaHandle:
         lib = _lib.load()
         st = torch.cuda.current_stream(counters.device).cuda_stream
         if int(codeword) != -1:
-            _lib.check(lib.ldpc_lqmsa_simulate(self.h, _lib.CHANNEL[channel], float(param), int(codeword), int(seed), int(stream_id), int(frame0),
-                                               int(B), int(max_iter), flags, hist_bins, counters.data_ptr(), st))
+            _lib.check(self._fn("simulate")(self.h, _lib.CHANNEL[channel], float(param), int(codeword), int(seed), int(stream_id), int(frame0),
+                                            int(B), int(max_iter), flags, hist_bins, counters.data_ptr(), st))
             return
         n, enc = self.code.n, self.code.encoder().handle(self.device)
         step = max(2048, min(1 << 17, (1 << 26) // n))
@@ -924,6 +928,49 @@ class LqmsaHandle:
                                              int(frame0) + b0, nb, n, pri.data_ptr(), None if y is None else y.data_ptr(), st))
             xhat, iters = self.decode_device(pri, y, max_iter, flags)
             _lib.check(lib.ldpc_count_errors_words(xhat.data_ptr(), sent.data_ptr(), iters.data_ptr(), nb, n, hist_bins, counters.data_ptr(), st))
+
+
+class QcHandle(LqmsaHandle):
+    """Layered fixed-point min-sum on a quasi-cyclic code, shift-addressed (``ldpc_qc_*``): LqmsaHandle's call shapes and outputs with every
+    block row of the base matrix one layer; the library finds the shifts for the lifting size ``Z`` from the code's edge list."""
+    family = "ldpc_qc"
+
+    def __init__(self, code, Z, device=None, bits=6, frac_bits=2, scale=0.8125, offset=0):
+        lib = _lib.load()
+        self.code_handle = code_handle(code, device)
+        self.code, self.device = code, self.code_handle.device
+        h = ctypes.c_void_p()
+        _lib.check(lib.ldpc_qc_create(self.code_handle.h, int(Z), ctypes.byref(h)))
+        self.h = h
+        self.set_fixed_point(bits, frac_bits, scale, offset)
+
+    def set_layers(self, layers=None):
+        raise TypeError("the layers of a quasi-cyclic decoder are its block rows: set_order")
+
+    layers = set_layers
+
+    def base(self):
+        """-> (base matrix int32 [mb, nb] with -1 for a zero block, Z) as the library detected it (``ldpc_qc_get_base``)"""
+        mb, nb, Z = ctypes.c_int32(0), ctypes.c_int32(0), ctypes.c_int32(0)
+        _lib.check(self._fn("get_base")(self.h, ctypes.byref(mb), ctypes.byref(nb), ctypes.byref(Z), None))
+        shifts = np.empty((mb.value, nb.value), dtype=np.int32)
+        _lib.check(self._fn("get_base")(self.h, ctypes.byref(mb), ctypes.byref(nb), ctypes.byref(Z), shifts.ctypes.data))
+        return shifts, Z.value
+
+    def set_order(self, order=None):
+        """``order``: the block row processed at each position, a permutation of 0 .. mb - 1; None: the natural order."""
+        if order is None:
+            _lib.check(self._fn("set_order")(self.h, None, 0))
+            return
+        o = np.ascontiguousarray(order, dtype=np.int32)
+        _lib.check(self._fn("set_order")(self.h, o.ctypes.data, o.size))
+
+    def order(self):
+        mb = ctypes.c_int32(0)
+        _lib.check(self._fn("get_order")(self.h, ctypes.byref(mb), None))
+        o = np.empty(mb.value, dtype=np.int32)
+        _lib.check(self._fn("get_order")(self.h, ctypes.byref(mb), o.ctypes.data))
+        return o
 
 
 class AdmmHandle:

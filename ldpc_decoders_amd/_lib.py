@@ -122,6 +122,17 @@ SIGNATURES = {
     "ldpc_lqmsa_simulate": (_c.c_int, [_P, _c.c_int, _c.c_double, _c.c_int, _c.c_uint64, _c.c_uint64, _c.c_uint64, _c.c_int64, _c.c_int32,
                                        _c.c_uint32, _c.c_int32, _P, _P]),
     "ldpc_lqmsa_info": (_c.c_int, [_P, _c.POINTER(_c.c_double)]),
+    "ldpc_qc_create": (_c.c_int, [_P, _c.c_int32, _c.POINTER(_P)]),
+    "ldpc_qc_destroy": (_c.c_int, [_P]),
+    "ldpc_qc_set_fixed_point": (_c.c_int, [_P, _c.c_int, _c.c_int, _c.c_double, _c.c_int]),
+    "ldpc_qc_get_fixed_point": (_c.c_int, [_P, _c.POINTER(_c.c_int), _c.POINTER(_c.c_int), _c.POINTER(_c.c_double), _c.POINTER(_c.c_int)]),
+    "ldpc_qc_get_base": (_c.c_int, [_P, _c.POINTER(_c.c_int32), _c.POINTER(_c.c_int32), _c.POINTER(_c.c_int32), _P]),
+    "ldpc_qc_set_order": (_c.c_int, [_P, _P, _c.c_int32]),
+    "ldpc_qc_get_order": (_c.c_int, [_P, _c.POINTER(_c.c_int32), _P]),
+    "ldpc_qc_decode": (_c.c_int, [_P, _c.c_int, _P, _P, _c.c_int64, _c.c_int32, _c.c_uint32, _P, _P, _P, _P, _P]),
+    "ldpc_qc_simulate": (_c.c_int, [_P, _c.c_int, _c.c_double, _c.c_int, _c.c_uint64, _c.c_uint64, _c.c_uint64, _c.c_int64, _c.c_int32,
+                                    _c.c_uint32, _c.c_int32, _P, _P]),
+    "ldpc_qc_info": (_c.c_int, [_P, _c.POINTER(_c.c_double)]),
     "ldpc_admm_create": (_c.c_int, [_P, _c.POINTER(_P)]),
     "ldpc_admm_destroy": (_c.c_int, [_P]),
     "ldpc_admm_last_repacks": (_c.c_int, [_P, _c.POINTER(_c.c_int)]),

@@ -5,7 +5,7 @@ the stopping-set exit of src/bec.py:120; symbols are {0, 1, 2 = erased}.
 """
 import numpy as np
 
-from . import admm, hard, layered, registry
+from . import admm, hard, layered, qc, registry
 from ._device import DecoderHandle, as_code
 
 
@@ -70,6 +70,15 @@ class LQMSA:
     def __init__(self, *a, **k):
         raise NotImplementedError("decoder LQMSA (layered fixed-point min-sum) does not exist over the bec: the erasure decoder has no "
                                   "magnitudes to quantise; use SPA / MSA there")
+
+
+class QCMSA:
+    """The quasi-cyclic layered fixed-point min-sum quantises and scales magnitudes as LQMSA does; the ternary erasure decoder has none."""
+    id_keys = qc.QCMSA.id_keys
+
+    def __init__(self, *a, **k):
+        raise NotImplementedError("decoder QCMSA (quasi-cyclic layered fixed-point min-sum) does not exist over the bec: the erasure decoder "
+                                  "has no magnitudes to quantise; use SPA / MSA there")
 
 
 class ADMM:  # src/bec.py:38-45,58-62: LLR wrapper with +-1e8 for the known symbols, 0 for an erasure

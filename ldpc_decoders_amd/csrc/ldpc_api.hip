@@ -17,6 +17,7 @@
 #include "ldpc_hard.hpp"
 #include "ldpc_lqmsa.hpp"
 #include "ldpc_osd.hpp"
+#include "ldpc_qc.hpp"
 
 namespace ldpc {
 
@@ -1500,6 +1501,112 @@ int ldpc_lqmsa_info(ldpc_lqmsa_t h, double* out4) {
     return guarded("ldpc_lqmsa_info", [&]() -> int {
         if (!h || !out4) return LDPC_E_ARG;
         lqmsa_info((const Lqmsa*)h, out4);
+        return LDPC_OK;
+    });
+}
+
+// ---- quasi-cyclic layered fixed-point min-sum, shift-addressed (ldpc_qc.hip) ----
+// no upstream counterpart (the reference knows no structured codes)
+int ldpc_qc_create(ldpc_code_t code, int32_t Z, ldpc_qc_t* out) {
+    return guarded("ldpc_qc_create", [&]() -> int {
+        if (!code || !out) {
+            set_error("ldpc_qc_create: bad arguments");
+            return LDPC_E_ARG;
+        }
+        Qc* h = nullptr;
+        LDPC_TRY(qc_create((Code*)code, Z, &h));
+        *out = (ldpc_qc_t)h;
+        return LDPC_OK;
+    });
+}
+
+int ldpc_qc_destroy(ldpc_qc_t h) {
+    return guarded("ldpc_qc_destroy", [&]() -> int {
+        qc_destroy((Qc*)h);
+        return LDPC_OK;
+    });
+}
+
+int ldpc_qc_set_fixed_point(ldpc_qc_t h, int bits, int frac_bits, double scale, int offset) {
+    return guarded("ldpc_qc_set_fixed_point", [&]() -> int {
+        if (!h) {
+            set_error("ldpc_qc_set_fixed_point: bad arguments");
+            return LDPC_E_ARG;
+        }
+        return qc_set_fixed_point((Qc*)h, bits, frac_bits, scale, offset);
+    });
+}
+
+int ldpc_qc_get_fixed_point(ldpc_qc_t h, int* bits, int* frac_bits, double* scale, int* offset) {
+    return guarded("ldpc_qc_get_fixed_point", [&]() -> int {
+        if (!h || !bits || !frac_bits || !scale || !offset) {
+            set_error("ldpc_qc_get_fixed_point: a handle and four result pointers are needed");
+            return LDPC_E_ARG;
+        }
+        qc_get_fixed_point((const Qc*)h, bits, frac_bits, scale, offset);
+        return LDPC_OK;
+    });
+}
+
+int ldpc_qc_get_base(ldpc_qc_t h, int32_t* mb, int32_t* nb, int32_t* Z, int32_t* shifts_host) {
+    return guarded("ldpc_qc_get_base", [&]() -> int {
+        if (!h || !mb || !nb || !Z) {
+            set_error("ldpc_qc_get_base: a handle and three result pointers are needed");
+            return LDPC_E_ARG;
+        }
+        qc_get_base((const Qc*)h, mb, nb, Z, shifts_host);
+        return LDPC_OK;
+    });
+}
+
+int ldpc_qc_set_order(ldpc_qc_t h, const int32_t* order_host, int32_t mb) {
+    return guarded("ldpc_qc_set_order", [&]() -> int {
+        if (!h) {
+            set_error("ldpc_qc_set_order: bad arguments");
+            return LDPC_E_ARG;
+        }
+        return qc_set_order((Qc*)h, order_host, mb);
+    });
+}
+
+int ldpc_qc_get_order(ldpc_qc_t h, int32_t* mb, int32_t* order_host) {
+    return guarded("ldpc_qc_get_order", [&]() -> int {
+        if (!h || !mb) {
+            set_error("ldpc_qc_get_order: a handle and a result pointer are needed");
+            return LDPC_E_ARG;
+        }
+        qc_get_order((const Qc*)h, mb, order_host);
+        return LDPC_OK;
+    });
+}
+
+int ldpc_qc_decode(ldpc_qc_t h, int dtype, const void* priors_dev, const uint8_t* y0_dev, int64_t B, int32_t max_iter, uint32_t flags,
+                   uint8_t* xhat_dev, uint32_t* xhat_bits_dev, int32_t* iters_dev, int16_t* soft_dev, void* stream) {
+    return guarded("ldpc_qc_decode", [&]() -> int {
+        if (!h || !priors_dev || (!xhat_dev && !xhat_bits_dev) || !iters_dev || B < 0) {
+            set_error("ldpc_qc_decode: bad arguments (priors, iters and at least one of xhat / xhat_bits are required)");
+            return LDPC_E_ARG;
+        }
+        return qc_decode((Qc*)h, dtype, priors_dev, y0_dev, B, max_iter, flags, xhat_dev, xhat_bits_dev, iters_dev, soft_dev, (hipStream_t)stream);
+    });
+}
+
+// inside the loop of main.test (src/main.py:37-45)
+int ldpc_qc_simulate(ldpc_qc_t h, int channel, double param, int codeword, uint64_t seed, uint64_t stream_id, uint64_t frame0, int64_t B,
+                     int32_t max_iter, uint32_t flags, int32_t hist_bins, int64_t* counters_dev, void* stream) {
+    return guarded("ldpc_qc_simulate", [&]() -> int {
+        if (!h || !counters_dev || B < 0 || hist_bins < 0) {
+            set_error("ldpc_qc_simulate: bad arguments");
+            return LDPC_E_ARG;
+        }
+        return qc_simulate((Qc*)h, channel, param, codeword, seed, stream_id, frame0, B, max_iter, flags, hist_bins, counters_dev, (hipStream_t)stream);
+    });
+}
+
+int ldpc_qc_info(ldpc_qc_t h, double* out4) {
+    return guarded("ldpc_qc_info", [&]() -> int {
+        if (!h || !out4) return LDPC_E_ARG;
+        qc_info((const Qc*)h, out4);
         return LDPC_OK;
     });
 }

@@ -1,0 +1,554 @@
+// Layered fixed-point min-sum for quasi-cyclic codes, shift-addressed (include/ldpc_hip.h, ldpc_qc_*).
+//
+// H is an mb x nb array of Z x Z blocks, each zero or a cyclically shifted identity: check i Z + r meets, in block column j, variable
+// j Z + (r + s_ij) mod Z.  A block row is a layer (its Z checks touch disjoint variables), its degree is the same for all its checks, and a
+// lane's variable index is its row r plus two wave-uniform scalars: there is no index table and no degree table.  The arithmetic is
+// LQMSA's (ldpc_lqmsa.hip), so are the LDS layout (lqmsa_lds_bytes with dc_max = the largest block-row degree) and the frame hand-out:
+//     marg  int16 [n]            the marginals in levels
+//     c2v   int8  [m][row bytes] the check -> variable messages, the row of check c at c, byte j for the block row's j-th nonzero block
+//     ctl   4 words              frame index, two syndrome flags used by alternate sweeps, spare
+// One workgroup of NW waves owns one frame; lane L of pass k of a block row owns check i Z + 64 k + L, pass k goes to wave k mod NW; a block
+// row ends with a workgroup barrier.  Neighbouring lanes touch neighbouring int16 marginals (up to the one wrap), which share a dword, so
+// marginals are read and written as 16-bit LDS accesses only.
+// Table (Qc::tab, rebuilt by qc_set_order), in global memory in processing order and read with wave-uniform addresses through the constant
+// address space, so every entry arrives by a scalar load: per block row {degree, offset of its edges, i Z, 0}, per edge {j Z, shift}.
+#include <algorithm>
+#include <cmath>
+#include <cstdlib>
+#include <cstring>
+#include <new>
+#include <numeric>
+
+#include "ldpc_cn.hpp"
+#include "ldpc_qc.hpp"
+
+namespace ldpc {
+
+struct Qc {
+    Code* code = nullptr;
+    int32_t Z = 1, mb = 0, nb = 0, dc_max = 0;
+    int bits = 6, frac = 2, offset = 0;
+    double scale = 0.8125;
+    bool odd_check = false;
+    int num_cu = 0, nw = 1, frames_per_cu = 0, row_bytes = 8;
+    int64_t lds_bytes = 0;
+    std::vector<int32_t> row_ptr, col, shift;  // the base matrix by block rows: nonzero blocks of block row i are row_ptr[i] .. row_ptr[i + 1]
+    std::vector<int32_t> order;                // block row processed at each position
+    DevBuf tab;                                // int32: [mb][4] headers in processing order, then [nonzero blocks][2]
+    DevBuf ctl;                                // the frame dispenser
+    DevBuf sim_pri, sim_y, sim_bits, sim_iters;  // staging of ldpc_qc_simulate
+};
+
+namespace {
+
+typedef const int32_t __attribute__((address_space(4)))* qc_tab_t;  // uniform address + constant address space = scalar load
+
+struct QcArgs {
+    const void* priors;
+    const uint8_t* y0;
+    int64_t B;
+    int32_t n, m, Z, mb, row_bytes, cap, no_early;
+    int32_t scale64, offset, vmax;
+    double step;
+    const int32_t* tab;
+    uint32_t* dispenser;
+    uint8_t* xhat;
+    uint32_t* bits;
+    int32_t* iters;
+    int16_t* soft;
+};
+
+// |c2v| a minimum m <= V sends (LQMSA's rule, step 3 of its contract)
+__device__ __forceinline__ int qc_mag(int m, int scale64, int offset) {
+    const int t = ((scale64 * m) >> 6) - offset;
+    return t > 0 ? t : 0;
+}
+
+// variable of row r in the block {colZ, shift}: e[0] + (r + e[1]) mod Z
+__device__ __forceinline__ int qc_var(int r, int Z, int colZ, int shift) {
+    const int t = r + shift;
+    return colZ + (t < Z ? t : t - Z);
+}
+
+// One check of a block row of degree D <= 8: its 8-byte row in registers, the D blocks in e[2 j], e[2 j + 1].
+template <int D>
+__device__ __forceinline__ void qc_check8(int16_t* __restrict__ marg, uint2* __restrict__ rowp, int r, int Z, qc_tab_t e, int scale64, int offset, int V) {
+    int min1 = V, min2 = V, arg = -1;  // |v| enters as min(|v|, V), so V is the neutral element
+    uint32_t par = 0;
+    const uint2 row = *rowp;
+    const uint32_t rw[2] = {row.x, row.y};
+    int v[D], vi[D];
+#pragma unroll
+    for (int j = 0; j < D; ++j) {
+        vi[j] = qc_var(r, Z, e[2 * j], e[2 * j + 1]);
+        v[j] = (int)marg[vi[j]] - (int)(int8_t)(rw[j >> 2] >> (8 * (j & 3)));
+        const int a = min(abs(v[j]), V);
+        par ^= (uint32_t)(v[j] < 0);
+        if (a < min1) {
+            min2 = min1;
+            min1 = a;
+            arg = j;
+        } else if (a < min2) {
+            min2 = a;
+        }
+    }
+    const int f1 = qc_mag(min1, scale64, offset), f2 = qc_mag(min2, scale64, offset);
+    uint32_t out[2] = {0u, 0u};
+#pragma unroll
+    for (int j = 0; j < D; ++j) {
+        const int mag = j == arg ? f2 : f1;
+        const int c = (par ^ (uint32_t)(v[j] < 0)) ? -mag : mag;
+        marg[vi[j]] = (int16_t)(v[j] + c);
+        out[j >> 2] |= (uint32_t)(uint8_t)(int8_t)c << (8 * (j & 3));
+    }
+    *rowp = make_uint2(out[0], out[1]);
+}
+
+// The loop form, any degree: the row stays in the LDS and is read twice.
+__device__ __forceinline__ void qc_check_loop(int16_t* __restrict__ marg, uint8_t* __restrict__ row, int deg, int r, int Z, qc_tab_t e, int scale64, int offset,
+                                              int V) {
+    int min1 = V, min2 = V, arg = -1;
+    uint32_t par = 0;
+    for (int j = 0; j < deg; ++j) {
+        const int v = (int)marg[qc_var(r, Z, e[2 * j], e[2 * j + 1])] - (int)(int8_t)row[j];
+        const int a = min(abs(v), V);
+        par ^= (uint32_t)(v < 0);
+        if (a < min1) {
+            min2 = min1;
+            min1 = a;
+            arg = j;
+        } else if (a < min2) {
+            min2 = a;
+        }
+    }
+    const int f1 = qc_mag(min1, scale64, offset), f2 = qc_mag(min2, scale64, offset);
+    for (int j = 0; j < deg; ++j) {
+        const int vi = qc_var(r, Z, e[2 * j], e[2 * j + 1]);
+        const int v = (int)marg[vi] - (int)(int8_t)row[j];
+        const int mag = j == arg ? f2 : f1;
+        const int c = (par ^ (uint32_t)(v < 0)) ? -mag : mag;
+        marg[vi] = (int16_t)(v + c);
+        row[j] = (uint8_t)(int8_t)c;
+    }
+}
+
+template <typename T, int NW, bool ROW8>
+__global__ __launch_bounds__(64 * NW) void k_qc(const QcArgs a) {
+    extern __shared__ __attribute__((aligned(16))) uint32_t qc_sm[];
+    constexpr int NT = 64 * NW;
+    const int n = a.n, m = a.m, Z = a.Z, mb = a.mb;
+    int16_t* marg = (int16_t*)qc_sm;
+    uint8_t* c2v = (uint8_t*)qc_sm + ((size_t)2 * n + 7) / 8 * 8;
+    uint32_t* ctl = (uint32_t*)(c2v + (size_t)m * a.row_bytes);
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int Wd = (n + 31) / 32;
+    const int np = (Z + 63) >> 6;  // wave passes of a block row
+    const T step = (T)a.step, vmax = (T)a.vmax;
+    const qc_tab_t tab = (qc_tab_t)a.tab;
+    for (;;) {
+        __syncthreads();  // the frame before is written out
+        if (tid == 0) {
+            ctl[0] = atomicAdd(a.dispenser, 1u);
+            ctl[1] = 0u;
+            ctl[2] = 0u;
+        }
+        __syncthreads();
+        const int64_t f = ctl[0];
+        if (f >= a.B) break;
+        const T* __restrict__ pr = (const T*)a.priors + (size_t)f * n;
+        for (int v = tid; v < n; v += NT) marg[v] = (int16_t)(int)quantise_prior<T>(pr[v], step, vmax);
+        uint32_t* cw = (uint32_t*)c2v;
+        for (int i = tid; i < m * (a.row_bytes / 4); i += NT) cw[i] = 0u;
+        __syncthreads();
+        const uint8_t* __restrict__ yf = a.y0 ? a.y0 + (size_t)f * n : nullptr;
+        int it = 0;
+        for (; it < a.cap; ++it) {
+            if (!a.no_early && (it > 0 || yf)) {  // H x_hat = 0?  x_hat = (marg < 0); before the first sweep the received word
+                // every wave scans its own passes and stops at the first one that holds an unsatisfied check
+                bool bad = false;
+                for (int l = 0; l < mb && !bad; ++l) {
+                    const int deg = tab[4 * l];
+                    const qc_tab_t e = tab + tab[4 * l + 1];
+                    for (int k = w; k < np && !bad; k += NW) {
+                        const int r = k * 64 + lane;
+                        uint32_t par = 0;
+                        if (r < Z) {
+                            if (it == 0)
+                                for (int j = 0; j < deg; ++j) par ^= (uint32_t)(yf[qc_var(r, Z, e[2 * j], e[2 * j + 1])] & 1u);
+                            else
+                                for (int j = 0; j < deg; ++j) par ^= (uint32_t)(marg[qc_var(r, Z, e[2 * j], e[2 * j + 1])] < 0);
+                        }
+                        bad = __ballot(par != 0u) != 0ull;  // wave-uniform
+                    }
+                }
+                if (bad && lane == 0) ctl[1 + (it & 1)] = 1u;
+                __syncthreads();
+                const bool any = ctl[1 + (it & 1)] != 0u;
+                if (tid == 0) ctl[1 + ((it + 1) & 1)] = 0u;  // last read a sweep ago, next written a sweep (and a layer barrier) from now
+                if (!any) break;
+            }
+            for (int l = 0; l < mb; ++l) {
+                const int deg = tab[4 * l];  // wave-uniform: the dispatch below is a scalar branch
+                const qc_tab_t e = tab + tab[4 * l + 1];
+                const int row0 = tab[4 * l + 2];
+                for (int k = w; k < np; k += NW) {
+                    const int r = k * 64 + lane;
+                    if (r < Z) {
+                        if constexpr (ROW8) {
+                            uint2* rowp = (uint2*)(c2v + (size_t)(row0 + r) * 8);
+                            switch (deg) {
+                                case 2: qc_check8<2>(marg, rowp, r, Z, e, a.scale64, a.offset, a.vmax); break;
+                                case 3: qc_check8<3>(marg, rowp, r, Z, e, a.scale64, a.offset, a.vmax); break;
+                                case 4: qc_check8<4>(marg, rowp, r, Z, e, a.scale64, a.offset, a.vmax); break;
+                                case 5: qc_check8<5>(marg, rowp, r, Z, e, a.scale64, a.offset, a.vmax); break;
+                                case 6: qc_check8<6>(marg, rowp, r, Z, e, a.scale64, a.offset, a.vmax); break;
+                                case 7: qc_check8<7>(marg, rowp, r, Z, e, a.scale64, a.offset, a.vmax); break;
+                                default: qc_check8<8>(marg, rowp, r, Z, e, a.scale64, a.offset, a.vmax); break;
+                            }
+                        } else {
+                            qc_check_loop(marg, c2v + (size_t)(row0 + r) * a.row_bytes, deg, r, Z, e, a.scale64, a.offset, a.vmax);
+                        }
+                    }
+                }
+                __syncthreads();
+            }
+        }
+        // it == 0: the frame left at the check of the received word and keeps it (cap >= 1, so y0 was given)
+        if (tid == 0) a.iters[f] = it;
+        if (a.xhat)
+            for (int v = tid; v < n; v += NT) a.xhat[(size_t)f * n + v] = it == 0 ? yf[v] : (uint8_t)(marg[v] < 0);
+        if (a.soft)
+            for (int v = tid; v < n; v += NT) a.soft[(size_t)f * n + v] = it == 0 ? (int16_t)0 : marg[v];
+        if (a.bits)
+            for (int v0 = w * 64; v0 < n; v0 += NT) {
+                const int v = v0 + lane;
+                const bool bit = v < n && (it == 0 ? (yf[v] & 1u) != 0u : marg[v] < 0);
+                const unsigned long long b = __ballot(bit);
+                if (lane == 0) {
+                    uint32_t* out = a.bits + (size_t)f * Wd + (v0 >> 5);
+                    out[0] = (uint32_t)b;
+                    if ((v0 >> 5) + 1 < Wd) out[1] = (uint32_t)(b >> 32);
+                }
+            }
+    }
+}
+
+template <typename T, int NW>
+const void* kernel_of(bool row8) {
+    return row8 ? (const void*)k_qc<T, NW, true> : (const void*)k_qc<T, NW, false>;
+}
+template <typename T>
+const void* kernel_of(int nw, bool row8) {
+    switch (nw) {
+        case 1: return kernel_of<T, 1>(row8);
+        case 2: return kernel_of<T, 2>(row8);
+        case 4: return kernel_of<T, 4>(row8);
+        default: return kernel_of<T, 8>(row8);
+    }
+}
+
+// the table of a processing order (host side) and its upload
+int install(Qc* h, const std::vector<int32_t>& order) {
+    const Code* c = h->code;
+    const size_t mb = (size_t)h->mb;
+    std::vector<int32_t> tab(4 * mb + 2 * h->col.size());
+    size_t at = 4 * mb;
+    for (size_t l = 0; l < mb; ++l) {
+        const int32_t i = order[l], k0 = h->row_ptr[(size_t)i], k1 = h->row_ptr[(size_t)i + 1];
+        tab[4 * l] = k1 - k0;
+        tab[4 * l + 1] = (int32_t)at;
+        tab[4 * l + 2] = i * h->Z;
+        tab[4 * l + 3] = 0;
+        for (int32_t k = k0; k < k1; ++k) {
+            tab[at++] = h->col[(size_t)k] * h->Z;
+            tab[at++] = h->shift[(size_t)k];
+        }
+    }
+    // a decode of this handle still in flight reads the old table
+    LDPC_HIP_TRY(hipSetDevice(c->device));
+    LDPC_HIP_TRY(hipDeviceSynchronize());
+    LDPC_TRY(h->tab.reserve(std::max<size_t>(tab.size(), 1) * sizeof(int32_t)));
+    if (!tab.empty()) LDPC_HIP_TRY(hipMemcpy(h->tab.p, tab.data(), tab.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+    h->order = order;
+    return LDPC_OK;
+}
+
+// the base matrix of `code` for the lifting size Z into h (row_ptr / col / shift), O(E + mb + nb); LDPC_E_UNSUPPORTED names the first block
+// that is neither zero nor one shifted identity
+int detect(const Code* code, int32_t Z, Qc* h) {
+    const int32_t mb = code->m / Z, nb = code->n / Z;
+    std::vector<int32_t> sh((size_t)nb, -1), cnt((size_t)nb, 0), seen_in((size_t)nb, -1), touched;
+    h->row_ptr.assign(1, 0);
+    h->col.clear();
+    h->shift.clear();
+    for (int32_t i = 0; i < mb; ++i) {
+        touched.clear();
+        for (int32_t r = 0; r < Z; ++r) {
+            const int32_t c = i * Z + r;
+            for (int32_t k = code->row_ptr[c]; k < code->row_ptr[c + 1]; ++k) {
+                const int32_t v = code->edge_var[k], j = v / Z, s = (v % Z - r + Z) % Z;
+                bool ok = seen_in[(size_t)j] != c;  // a second one of this block in the row
+                seen_in[(size_t)j] = c;
+                if (ok && cnt[(size_t)j] == 0) {
+                    sh[(size_t)j] = s;
+                    touched.push_back(j);
+                } else if (ok) {
+                    ok = sh[(size_t)j] == s;
+                }
+                if (!ok) {
+                    set_error("ldpc_qc_create: block (%d, %d) of the %d x %d base at Z = %d is neither zero nor one cyclically shifted identity (row %d of "
+                              "the block); use ldpc_lqmsa_create (LQMSA, any layering) for a code without this structure", i, j, mb, nb, Z, r);
+                    return LDPC_E_UNSUPPORTED;
+                }
+                ++cnt[(size_t)j];
+            }
+        }
+        std::sort(touched.begin(), touched.end());
+        for (int32_t j : touched) {
+            if (cnt[(size_t)j] != Z) {
+                set_error("ldpc_qc_create: block (%d, %d) of the %d x %d base at Z = %d holds %d ones, a shifted identity holds %d; use "
+                          "ldpc_lqmsa_create (LQMSA, any layering) for a code without this structure", i, j, mb, nb, Z, cnt[(size_t)j], Z);
+                return LDPC_E_UNSUPPORTED;
+            }
+            h->col.push_back(j);
+            h->shift.push_back(sh[(size_t)j]);
+            cnt[(size_t)j] = 0;
+            sh[(size_t)j] = -1;
+        }
+        h->row_ptr.push_back((int32_t)h->col.size());
+    }
+    return LDPC_OK;
+}
+
+}  // namespace
+
+int qc_create(Code* code, int32_t Z, Qc** out) {
+    if (Z < 1 || code->m % Z != 0 || code->n % Z != 0) {
+        set_error("ldpc_qc_create: the lifting size Z = %d must be >= 1 and divide m = %d and n = %d", Z, code->m, code->n);
+        return LDPC_E_ARG;
+    }
+    Qc* h = new Qc();
+    h->code = code;
+    h->Z = Z;
+    h->mb = code->m / Z;
+    h->nb = code->n / Z;
+    int rc = detect(code, Z, h);
+    if (rc != LDPC_OK) {
+        delete h;
+        return rc;
+    }
+    int32_t dmin = code->m ? INT32_MAX : 0;
+    for (int32_t i = 0; i < h->mb; ++i) {
+        const int32_t d = h->row_ptr[(size_t)i + 1] - h->row_ptr[(size_t)i];
+        dmin = std::min(dmin, d);
+        h->dc_max = std::max(h->dc_max, d);
+        h->odd_check |= (d & 1) != 0;
+    }
+    const int64_t need = lqmsa_lds_bytes(code->m, code->n, code->E, h->dc_max);
+    if (dmin < 2) {
+        set_error("ldpc_qc_create: a block row of degree %d: layered min-sum needs every check to have degree >= 2", dmin);
+        rc = LDPC_E_UNSUPPORTED;
+    } else if (code->max_dv > LQMSA_MAX_DV) {
+        set_error("ldpc_qc_create: a variable of degree %d: the int16 marginals hold V (1 + dv) for dv <= %d", code->max_dv, LQMSA_MAX_DV);
+        rc = LDPC_E_UNSUPPORTED;
+    } else if (need > LQMSA_LDS_BYTES) {
+        set_error("ldpc_qc_create: one frame of this code (m = %d, n = %d, largest block-row degree %d) needs %lld bytes of LDS, above one CU's %lld; "
+                  "use LDPC_ALG_LMSA (layered min-sum on the streaming kernels) for it",
+                  code->m, code->n, h->dc_max, (long long)need, (long long)LQMSA_LDS_BYTES);
+        rc = LDPC_E_UNSUPPORTED;
+    }
+    if (rc != LDPC_OK) {
+        delete h;
+        return rc;
+    }
+    hipError_t e = hipSetDevice(code->device);
+    h->lds_bytes = need;
+    h->row_bytes = lqmsa_row_bytes(h->dc_max);
+    const int64_t fit = LQMSA_LDS_BYTES / need;
+    h->nw = qc_waves(fit, Z);
+    if (const char* env = std::getenv("LDPC_QC_NW")) {  // the tests and the wave table reach every wave count with it
+        const int v = std::atoi(env);
+        if (v == 1 || v == 2 || v == 4 || v == 8) h->nw = v;
+    }
+    h->frames_per_cu = (int)std::min<int64_t>(fit, 32 / h->nw);
+    hipDeviceProp_t prop;
+    if (e == hipSuccess) e = hipGetDeviceProperties(&prop, code->device);
+    if (e == hipSuccess && need > 64 * 1024) {  // above 64 KiB a workgroup's LDS has to be asked for
+        const bool row8 = h->row_bytes == 8;
+        e = hipFuncSetAttribute(kernel_of<float>(h->nw, row8), hipFuncAttributeMaxDynamicSharedMemorySize, (int)need);
+        if (e == hipSuccess) e = hipFuncSetAttribute(kernel_of<double>(h->nw, row8), hipFuncAttributeMaxDynamicSharedMemorySize, (int)need);
+    }
+    if (e != hipSuccess) {
+        set_error("ldpc_qc_create: device setup failed: %s", hipGetErrorString(e));
+        qc_destroy(h);
+        return LDPC_E_HIP;
+    }
+    h->num_cu = prop.multiProcessorCount;
+    rc = h->ctl.reserve(64);
+    if (rc == LDPC_OK) {
+        std::vector<int32_t> natural((size_t)h->mb);
+        std::iota(natural.begin(), natural.end(), 0);
+        rc = install(h, natural);
+    }
+    if (rc != LDPC_OK) {
+        qc_destroy(h);
+        return rc;
+    }
+    *out = h;
+    return LDPC_OK;
+}
+
+void qc_destroy(Qc* h) {
+    if (!h) return;
+    for (DevBuf* b : {&h->tab, &h->ctl, &h->sim_pri, &h->sim_y, &h->sim_bits, &h->sim_iters}) b->release();
+    delete h;
+}
+
+int qc_set_fixed_point(Qc* h, int bits, int frac_bits, double scale, int offset) {
+    // (written so that a NaN scale fails; 64 * scale is exact, so the grid test is)
+    if (bits < 2 || bits > 8 || frac_bits < -8 || frac_bits > 8 || !(scale > 0.0 && scale <= 1.0) || 64.0 * scale != (double)(long long)(64.0 * scale) ||
+        offset < 0) {
+        set_error("ldpc_qc_set_fixed_point: 2 <= bits <= 8, -8 <= frac_bits <= 8, scale a multiple of 1/64 in (0, 1] and offset >= 0 are needed "
+                  "(bits=%d frac_bits=%d scale=%g offset=%d)", bits, frac_bits, scale, offset);
+        return LDPC_E_ARG;
+    }
+    h->bits = bits;
+    h->frac = frac_bits;
+    h->scale = scale;
+    h->offset = offset;
+    return LDPC_OK;
+}
+
+void qc_get_fixed_point(const Qc* h, int* bits, int* frac_bits, double* scale, int* offset) {
+    *bits = h->bits;
+    *frac_bits = h->frac;
+    *scale = h->scale;
+    *offset = h->offset;
+}
+
+void qc_get_base(const Qc* h, int32_t* mb, int32_t* nb, int32_t* Z, int32_t* shifts) {
+    *mb = h->mb;
+    *nb = h->nb;
+    *Z = h->Z;
+    if (!shifts) return;
+    std::fill(shifts, shifts + (size_t)h->mb * (size_t)h->nb, -1);
+    for (int32_t i = 0; i < h->mb; ++i)
+        for (int32_t k = h->row_ptr[(size_t)i]; k < h->row_ptr[(size_t)i + 1]; ++k) shifts[(size_t)i * (size_t)h->nb + (size_t)h->col[(size_t)k]] = h->shift[(size_t)k];
+}
+
+int qc_set_order(Qc* h, const int32_t* order, int32_t mb) {
+    std::vector<int32_t> next((size_t)h->mb);
+    if (!order) {
+        std::iota(next.begin(), next.end(), 0);
+        return install(h, next);
+    }
+    if (mb != h->mb) {
+        set_error("ldpc_qc_set_order: %d entries for a base of %d block rows", mb, h->mb);
+        return LDPC_E_ARG;
+    }
+    std::vector<char> seen((size_t)h->mb, 0);
+    for (int32_t l = 0; l < mb; ++l) {
+        if (order[l] < 0 || order[l] >= mb || seen[(size_t)order[l]]) {
+            set_error("ldpc_qc_set_order: entry %d (%d): the order is a permutation of 0 .. %d", l, order[l], mb - 1);
+            return LDPC_E_ARG;
+        }
+        seen[(size_t)order[l]] = 1;
+        next[(size_t)l] = order[l];
+    }
+    return install(h, next);
+}
+
+void qc_get_order(const Qc* h, int32_t* mb, int32_t* order) {
+    *mb = h->mb;
+    if (order) std::copy(h->order.begin(), h->order.end(), order);
+}
+
+void qc_info(const Qc* h, double* out4) {
+    out4[0] = (double)h->lds_bytes;
+    out4[1] = h->nw;
+    out4[2] = h->frames_per_cu;
+    out4[3] = (double)h->num_cu * h->frames_per_cu;
+}
+
+int qc_decode(Qc* h, int dtype, const void* priors, const uint8_t* y0, int64_t B, int32_t max_iter, uint32_t flags, uint8_t* xhat, uint32_t* bits,
+              int32_t* iters, int16_t* soft, hipStream_t st) {
+    if (dtype != DT_F32 && dtype != DT_F64) {
+        set_error("ldpc_qc_decode: the priors are LDPC_DTYPE_F32 or LDPC_DTYPE_F64 (got %d)", dtype);
+        return LDPC_E_ARG;
+    }
+    if (flags & ~FLAG_NO_EARLY_EXIT) {
+        set_error("ldpc_qc_decode: the only flag is LDPC_FLAG_NO_EARLY_EXIT (got 0x%x)", flags);
+        return LDPC_E_UNSUPPORTED;
+    }
+    if (B > (int64_t)1 << 31) {
+        set_error("ldpc_qc_decode: at most 2^31 frames per call (got %lld)", (long long)B);
+        return LDPC_E_ARG;
+    }
+    const Code* c = h->code;
+    LDPC_HIP_TRY(hipSetDevice(c->device));
+    if (B == 0) return LDPC_OK;
+    QcArgs a;
+    a.priors = priors;
+    a.y0 = y0;
+    a.B = B;
+    a.n = c->n;
+    a.m = c->m;
+    a.Z = h->Z;
+    a.mb = h->mb;
+    a.row_bytes = h->row_bytes;
+    a.cap = max_iter > 0 ? max_iter : 100000;
+    a.no_early = (flags & FLAG_NO_EARLY_EXIT) ? 1 : 0;
+    a.scale64 = (int32_t)(64.0 * h->scale);
+    a.offset = std::min(h->offset, 1 << 20);  // beyond V every message is 0 already
+    a.vmax = (1 << (h->bits - 1)) - 1;
+    a.step = std::ldexp(1.0, h->frac);
+    a.tab = (const int32_t*)h->tab.p;
+    a.dispenser = (uint32_t*)h->ctl.p;
+    a.xhat = xhat;
+    a.bits = bits;
+    a.iters = iters;
+    a.soft = soft;
+    LDPC_HIP_TRY(hipMemsetAsync(a.dispenser, 0, 4, st));
+    const unsigned groups = (unsigned)std::min<int64_t>(B, (int64_t)h->num_cu * h->frames_per_cu);
+    const void* kern = dtype == DT_F64 ? kernel_of<double>(h->nw, h->row_bytes == 8) : kernel_of<float>(h->nw, h->row_bytes == 8);
+    void* args[] = {(void*)&a};
+    LDPC_HIP_TRY(hipLaunchKernel(kern, dim3(groups), dim3(64u * (unsigned)h->nw), args, (size_t)h->lds_bytes, st));
+    return LDPC_OK;
+}
+
+int qc_simulate(Qc* h, int channel, double param, int codeword, uint64_t seed, uint64_t stream_id, uint64_t frame0, int64_t B, int32_t max_iter,
+                uint32_t flags, int32_t hist_bins, int64_t* counters, hipStream_t st) {
+    if (channel != CH_BIAWGN && channel != CH_BSC) {
+        set_error("ldpc_qc_simulate: LDPC_CH_BIAWGN or LDPC_CH_BSC (min-sum has no magnitudes to work on over the erasure channel)");
+        return LDPC_E_ARG;
+    }
+    if (codeword != 0 && codeword != 1) {
+        set_error("ldpc_qc_simulate: codeword must be 0 or 1");
+        return LDPC_E_ARG;
+    }
+    if (codeword == 1 && h->odd_check) {
+        set_error("ldpc_qc_simulate: codeword 1: the all-ones word is no codeword of this code (a check has odd degree)");
+        return LDPC_E_ARG;
+    }
+    const size_t n = (size_t)h->code->n, W = (n + 31) / 32;
+    // the priors of one pass: about 256 MiB, at most 2^17 frames
+    int64_t cap = std::min<int64_t>(std::max<int64_t>((int64_t)(((size_t)256 << 20) / (n * sizeof(float))), 1), (int64_t)1 << 17);
+    cap = std::min(cap, std::max<int64_t>(B, 1));
+    LDPC_HIP_TRY(hipSetDevice(h->code->device));
+    LDPC_TRY(h->sim_pri.reserve((size_t)cap * n * sizeof(float)));
+    if (channel == CH_BSC) LDPC_TRY(h->sim_y.reserve((size_t)cap * n));
+    LDPC_TRY(h->sim_bits.reserve((size_t)cap * W * 4));
+    LDPC_TRY(h->sim_iters.reserve((size_t)cap * sizeof(int32_t)));
+    uint8_t* y = channel == CH_BSC ? (uint8_t*)h->sim_y.p : nullptr;  // over the BSC the received word takes the iteration-0 check, as upstream
+    for (int64_t b0 = 0; b0 < B; b0 += cap) {
+        const int64_t nb = std::min(cap, B - b0);
+        LDPC_TRY(channel_generate(channel, DT_F32, param, codeword, seed, stream_id, frame0 + (uint64_t)b0, nb, (int32_t)n, h->sim_pri.p, y, st));
+        LDPC_TRY(qc_decode(h, DT_F32, h->sim_pri.p, y, nb, max_iter, flags, nullptr, (uint32_t*)h->sim_bits.p, (int32_t*)h->sim_iters.p, nullptr, st));
+        LDPC_TRY(count_errors_bits((const uint32_t*)h->sim_bits.p, nullptr, nullptr, codeword, (const int32_t*)h->sim_iters.p, nb, (int32_t)n, hist_bins,
+                                   counters, st));
+    }
+    return LDPC_OK;
+}
+
+}  // namespace ldpc

@@ -15,7 +15,7 @@ from collections import OrderedDict
 
 import numpy as np
 
-from . import codes, dist, utils
+from . import codes, dist, qc, utils
 from .models import all_decoder_names, models
 from .registry import BY_NAME
 from .montecarlo import DeviceSimulator, run_point_exact
@@ -26,23 +26,35 @@ def test(args, comm=None):
     model = models[args.channel]
     dec_fac = getattr(model, args.decoder)
     row = BY_NAME[args.decoder]  # what this driver may do with the name
+    if row.integer_layered or row.quasi_cyclic:  # (an integer kernel in the LDS: refused before a decoder exists)
+        if args.precision == "f16":
+            raise SystemExit("--precision f16: %s keeps int16 marginals and int8 messages in the LDS and has no arithmetic to store in fp16" % row.name)
+        if getattr(args, "prior_grid", None) is not None:
+            raise SystemExit("--prior-grid: fp32 min-sum over BI-AWGN (biawgn <code> MSA, without --precision f64); %s quantises its priors itself" % row.name)
+        if args.backend == "stream":
+            raise SystemExit("--backend stream: %s is LDS-resident (--backend auto / fused); layered min-sum on the streaming kernels is LMSA" % row.name)
+    code = codes.get_code(args.code)
+    if row.quasi_cyclic:  # (the result file carries the lifting size the decoder runs with, not the 0 that asks for it)
+        try:
+            args.qc_lift = qc.resolve(code, args.qc_lift)[1]
+        except ValueError as e:
+            raise SystemExit("QCMSA: %s (LQMSA decodes any code)" % e)
     id_keys = ["channel", "code", "decoder", "codeword", "min_wec"] + dec_fac.id_keys
     id_val = [vars(args)[key] for key in id_keys]
     log = logging.getLogger(".".join(utils.strl(id_val)))
-    code = codes.get_code(args.code)
     code_n = code.get_n()
     saver = utils.Saver(args.data_dir, list(zip(id_keys, id_val))) if comm.is_root else None
     # --codeword -1 (a random codeword per frame, src/main.py:38): on the device for the BP decoders -- from the code book where the code
     # has one, from the systematic GF(2) encoder (Code.encoder()) otherwise -- and for ML over the BEC of a code without a code book (the
     # elimination decoder, encoder words); the reference's sequential loop on host noise for the others
-    device_words = row.device_words or row.hard or row.integer_layered or (args.channel == "bec" and args.decoder == "ML" and code.gen_mtx is None)
+    device_words = row.device_words or row.hard or row.integer_layered or row.quasi_cyclic or (args.channel == "bec" and args.decoder == "ML" and code.gen_mtx is None)
     exact = bool(args.exact) or (args.codeword == -1 and not device_words)
     if exact and comm.world > 1:
         raise SystemExit("--exact / --codeword -1 follow the reference's sequential rule and run on a single rank")
     if exact and args.np_seed is not None:
         np.random.seed(args.np_seed)
     kwargs = dict(vars(args))
-    if row.pops_layers or row.integer_layered:
+    if row.pops_layers or row.integer_layered or row.quasi_cyclic:
         kwargs.pop("layers", None)  # (--layers is ADMMA's network shape, src/utils.py:43: not a layering of the checks; LMSA takes the greedy one)
     # fp32 message arithmetic in the throughput mode -- except min-sum over the BSC: every LLR is +-L there, the decoder is
     # tie-dominated and only the reference's fp64 arithmetic reproduces its curves
@@ -57,13 +69,6 @@ def test(args, comm=None):
             raise SystemExit("--prior-grid: fp32 min-sum over BI-AWGN (biawgn <code> MSA, without --precision f64); GALB reads no priors")
         if args.max_iter <= 0:
             raise SystemExit("--max-iter must be >= 1 for GALB: a hard-decision decoder may oscillate for ever and has no exit of its own")
-    if row.integer_layered:  # (an integer kernel in the LDS: refused before a decoder exists)
-        if args.precision == "f16":
-            raise SystemExit("--precision f16: LQMSA keeps int16 marginals and int8 messages in the LDS and has no arithmetic to store in fp16")
-        if getattr(args, "prior_grid", None) is not None:
-            raise SystemExit("--prior-grid: fp32 min-sum over BI-AWGN (biawgn <code> MSA, without --precision f64); LQMSA quantises its priors itself")
-        if args.backend == "stream":
-            raise SystemExit("--backend stream: LQMSA is LDS-resident (--backend auto / fused); layered min-sum on the streaming kernels is LMSA")
     if kwargs["precision"] == "f16" and (not row.f16 or args.channel == "bec" or exact):
         raise SystemExit("--precision f16 (fp16 storage of the messages): the LLR decoders SPA / MSA over biawgn / bsc, device-noise mode")
     if row.refuses_fused and args.backend == "fused":  # (refused before a decoder exists, like the two around it)
@@ -146,7 +151,7 @@ def test(args, comm=None):
 
 
 def build_parser():
-    """The reference's grammar with the reference's decoder names, plus this build's own (``registry.ROWS``: NMSA, QMSA, LMSA, OSD, LQMSA, GALB)."""
+    """The reference's grammar with the reference's decoder names, plus this build's own (``registry.ROWS``: NMSA, QMSA, LMSA, OSD, QCMSA, LQMSA, GALB)."""
     return utils.setup_parser(codes.get_code_names(), models.keys(), all_decoder_names)
 
 

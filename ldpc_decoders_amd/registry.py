@@ -7,11 +7,11 @@ its row in the library's own table (``kAlgs``, csrc/ldpc_common.hpp).
 """
 from collections import namedtuple
 
-from . import admm, bpa, hard, layered, ml
+from . import admm, bpa, hard, layered, ml, qc
 
 Row = namedtuple("Row", [
     "name",
-    "group",          # which list of ``models`` carries the name: reference (src/utils.py:16), extra, fixed_point, layered, post_processing, layered_fixed_point, hard_decision
+    "group",          # which list of ``models`` carries the name: reference (src/utils.py:16), extra, fixed_point, layered, post_processing, quasi_cyclic, layered_fixed_point, hard_decision
     "backing",        # the bpa / admm class the LLR wrappers of biawgn / bsc hold ({channel: class}: the channel's own class; None: not built)
     "bec_refusal",    # None: the bec module has its own class of this name; else (docstring, sentence) of the class that raises there
     "osd_front",      # may run in front of bpa.OSD (osd_bp)
@@ -23,8 +23,9 @@ Row = namedtuple("Row", [
     "refuses_fused",  # --backend fused is refused before a decoder exists
     "hard",           # decodes hard decisions (one bit per message): words drawn on the device, no --precision f16, no --prior-grid, --max-iter >= 1
     "integer_layered",  # the LDS-resident integer kernel on the layered schedule: words drawn on the device, --layers dropped, no --precision f16, no --prior-grid, no --backend stream
+    "quasi_cyclic",   # the shift-addressed integer kernel for quasi-cyclic codes: as integer_layered, and --qc-lift resolved to the code's lifting size
 ])
-Row.__new__.__defaults__ = (None, False, False, False, False, None, False, False, False, False)
+Row.__new__.__defaults__ = (None, False, False, False, False, None, False, False, False, False, False)
 
 ROWS = [
     Row("ML", "reference", {"biawgn": ml.BiawgnML, "bsc": ml.BscML}),
@@ -50,6 +51,8 @@ ROWS = [
         ("Ordered-statistics post-processing orders soft values; over the erasure channel ``ML`` (elimination of the erased bits) is exact.",
          "decoder OSD (BP + ordered-statistics post-processing) does not exist over the bec: use ML there, the elimination decoder is exact"),
         device_words=True, tie_dominated=True, prior_grid=False, pops_layers=True),
+    # LQMSA's contract on a quasi-cyclic code with the block rows as layers, shift-addressed; bec writes its own (refusing) class of this name
+    Row("QCMSA", "quasi_cyclic", qc.QCMSA, quasi_cyclic=True),
     # QMSA's integer rule on LMSA's schedule, the frame resident in the LDS as integers; bec writes its own (refusing) class of this name
     Row("LQMSA", "layered_fixed_point", layered.LQMSA, integer_layered=True),
     # hard-decision decoding of the received bits (bit-sliced Gallager-B); biawgn / bsc / bec write their own class of this name, as for ADMM

@@ -1,7 +1,7 @@
 """CLI flags, logging and the JSON result store -- mirror of the reference's ``src/utils.py:21-68,118-140``.
 
 The argument grammar (positional ``channel code decoder`` + ``--codeword --min-wec --params --max-iter ...``) and
-the result files (``<channel>-<code>-<decoder>-<codeword>-<min_wec>-<max_iter>.json``; NMSA, LMSA: ``...-<max_iter>-<msa_scale>-<msa_offset>.json``; QMSA, LQMSA: ``...-<max_iter>-<msa_bits>-<msa_frac_bits>-<msa_scale>-<msa_offset>.json``; OSD: ``...-<max_iter>-<msa_scale>-<msa_offset>-<osd_order>-<osd_depth>.json``; GALB: ``...-<max_iter>-<gal_threshold>.json``; with the id keys first, then
+the result files (``<channel>-<code>-<decoder>-<codeword>-<min_wec>-<max_iter>.json``; NMSA, LMSA: ``...-<max_iter>-<msa_scale>-<msa_offset>.json``; QMSA, LQMSA: ``...-<max_iter>-<msa_bits>-<msa_frac_bits>-<msa_scale>-<msa_offset>.json``; QCMSA: the same followed by ``-<qc_lift>``; OSD: ``...-<max_iter>-<msa_scale>-<msa_offset>-<osd_order>-<osd_depth>.json``; GALB: ``...-<max_iter>-<gal_threshold>.json``; with the id keys first, then
 ``tot wec wer bec ber`` as ``{str(param): value}``) are what ``simulations.py`` / ``run_sims.sh`` emit and what
 ``graph.py`` reads upstream (src/graph.py:25-58), so flag names, defaults and the file layout are kept; the help texts are
 this build's own.  ``--mu --eps --allow-pseudo`` configure the ADMM decoder; ``--layers --train --apprx`` belong to ADMMA, which
@@ -14,7 +14,7 @@ import os
 from collections import OrderedDict
 
 from . import codes
-from .models import decoder_names, extra_decoder_names, fixed_point_decoder_names, layered_decoder_names, post_processing_decoder_names, layered_fixed_point_decoder_names, hard_decision_decoder_names  # noqa: F401  (re-exported like upstream utils.decoder_names)
+from .models import decoder_names, extra_decoder_names, fixed_point_decoder_names, layered_decoder_names, post_processing_decoder_names, quasi_cyclic_decoder_names, layered_fixed_point_decoder_names, hard_decision_decoder_names  # noqa: F401  (re-exported like upstream utils.decoder_names)
 
 strl = lambda ll: (str(it_) for it_ in ll)  # noqa: E731
 
@@ -83,6 +83,9 @@ def setup_parser(code_names, channel_names, decoder_names):
     g.add_argument("--gal-threshold", type=int, default=0, metavar="T",
                    help="GALB (Gallager-B on the received bits): a message flips when at least min(T, d - 1) of the other checks of a degree-d "
                         "variable disagree with the received bit, 1..255; 0 = their majority, floor((d - 1) / 2) + 1 (Gallager A for d = 3)")
+    g.add_argument("--qc-lift", type=int, default=0, metavar="Z",
+                   help="QCMSA (layered fixed-point min-sum on a quasi-cyclic code, parameters of LQMSA): the lifting size, H is an array of Z x Z blocks "
+                        "that are zero or cyclically shifted identities; 0 = the largest Z for which that holds")
     g.add_argument("--osd-depth", type=int, default=64, metavar="N", help="OSD order 1: how many single flips are tried (N >= 0)")
     return bind_parser_common(p)
 
