@@ -553,6 +553,50 @@ int ldpc_qc_simulate(ldpc_qc_t h, int channel, double param, int codeword, uint6
                      int32_t max_iter, uint32_t flags, int32_t hist_bins, int64_t* counters_dev, void* stream);
 int ldpc_qc_info(ldpc_qc_t h, double* out4);
 
+/* ---- Streaming layered fixed-point min-sum (SLQMSA): the LQMSA contract for codes beyond the LDS -------------------
+ * No upstream counterpart.
+ *   Contract.  Steps 1-4 of the LQMSA statement above (ldpc_lqmsa_*), word for word: the quantiser; the init and the exits (y0 and the
+ *      iteration-0 check, max_iter <= 0, LDPC_FLAG_NO_EARLY_EXIT); the sweep rule with scale64, the offset and the clip at V; the outputs
+ *      (bytes and / or packed words, iters, the optional int16 soft output of each frame's last executed sweep, 0 where it never swept).
+ *      Parameters, their ranges and defaults are those of ldpc_lqmsa_set_fixed_point; layers those of LDPC_ALG_LMSA (validity rule, greedy
+ *      default, processing order), with the refusal semantics of ldpc_lqmsa_set_layers.  On a code both take, ldpc_lqmsa_decode at the
+ *      same layering returns the same bytes, words, iteration counts and soft outputs.
+ *   Refusals.  ldpc_slq_create, LDPC_E_UNSUPPORTED: a check of degree < 2; a variable of degree above 255 (int16 marginals hold
+ *      V (1 + dv)).  Nothing else: no size rule, any check degree, n may exceed 65536 (32-bit indices).
+ * Determinism: as LQMSA -- one function of (H, layers, parameters, priors, y0, max_iter, flags), the same for any batch size, position of
+ * a frame in its batch, chunking of the batch, poll cadence and frame repack.
+ * Kernels.  The state lives in HBM in tiles of 64 frames, lane = frame: int16 marginals [tile][n][64], int8 check messages [tile][E][64],
+ * decision bit planes and live words as the floating-point streaming decoders keep them.  One launch per layer (a wave takes a tile and
+ * a run of the layer's checks) and a decision pass per sweep: 6 E + 2 n bytes per frame-sweep.  Frames leave one by one (syndrome before
+ * every sweep); when the batch has thinned out the live frames are gathered into dense tiles (never with a soft output), under the
+ * policy of the floating-point streaming decoders: LDPC_STREAM_REPACK=0 turns it off, LDPC_STREAM_REPACK_FILL sets the fill below which
+ * it fires; both are read at every decode.  A batch is decoded in chunks of whole tiles such that a chunk's state and a repack target of
+ * the same size stay within 24 GiB (LDPC_SLQ_WORKSPACE_MB, read at every decode, sets another bound; at least one tile per chunk).
+ * Handles are not thread-safe (one workspace). */
+typedef struct ldpc_slq_s* ldpc_slq_t;
+int ldpc_slq_create(ldpc_code_t code, ldpc_slq_t* out);
+int ldpc_slq_destroy(ldpc_slq_t h);
+/* Ranges, defaults and semantics of ldpc_lqmsa_set_fixed_point / _get_fixed_point / _set_layers / _get_layers. */
+int ldpc_slq_set_fixed_point(ldpc_slq_t h, int bits, int frac_bits, double scale, int offset);
+int ldpc_slq_get_fixed_point(ldpc_slq_t h, int* bits, int* frac_bits, double* scale, int* offset);
+int ldpc_slq_set_layers(ldpc_slq_t h, const int32_t* layer_of_check_host, int32_t m);
+int ldpc_slq_get_layers(ldpc_slq_t h, int32_t* nlayers, int32_t* layer_of_check_host_or_NULL);
+/* Argument lists and semantics of ldpc_lqmsa_decode / ldpc_lqmsa_simulate.  The calls poll the device while they enqueue and may
+ * synchronise `stream`.  ldpc_slq_simulate stages the fp32 priors of a chunk of frames ([chunk, n], 8 n bytes per frame written and
+ * read once, against 6 E + 2 n per sweep; there is no in-kernel noise on this path). */
+int ldpc_slq_decode(ldpc_slq_t h, int dtype, const void* priors_dev, const uint8_t* y0_dev, int64_t B, int32_t max_iter, uint32_t flags,
+                    uint8_t* xhat_dev, uint32_t* xhat_bits_dev, int32_t* iters_dev, int16_t* soft_dev, void* stream);
+int ldpc_slq_simulate(ldpc_slq_t h, int channel, double param, int codeword, uint64_t seed, uint64_t stream_id, uint64_t frame0, int64_t B,
+                      int32_t max_iter, uint32_t flags, int32_t hist_bins, int64_t* counters_dev, void* stream);
+/* out4 = {bytes of integer state per frame (2 n + E), tiles per chunk under the workspace bound, layers, launches per sweep (layers + 1)} */
+int ldpc_slq_info(ldpc_slq_t h, double* out4);
+/* Per-kernel timing, the slots LDPC_ALG_LMSA has in ldpc_decoder_profile: HIP events on the decode stream, accumulated as milliseconds /
+ * launch counts in ms3 / launches3 (either may be NULL): [0] the layer passes of a sweep, [1] its decision pass, [2] a whole decode.
+ * enable 1 / 0 switches it (a decode then ends with a stream synchronise), a negative value leaves it; reset != 0 clears the sums. */
+int ldpc_slq_profile(ldpc_slq_t h, int enable, double* ms3, int64_t* launches3, int reset);
+/* out3 = {sweeps enqueued by the last decode (the largest over its chunks), frame repacks, chunks} */
+int ldpc_slq_last_stats(ldpc_slq_t h, int32_t* out3);
+
 /* ---- ADMM LP decoding ------------------------------------------------------------------------------------------
  * Replaces admm.ADMM (src/admm.py:9-77) together with its native projection (src/parity_polytope/projection.cpp:30-275, bound
  * upstream through ctypes in exact.py:12-53).  Check degrees up to 16. */

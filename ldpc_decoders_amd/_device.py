@@ -834,11 +834,11 @@ class LqmsaHandle:
         return getattr(_lib.load(), "%s_%s" % (self.family, name))
 
     def __init__(self, code, device=None, bits=6, frac_bits=2, scale=0.8125, offset=0):
-        lib = _lib.load()
+        _lib.load()
         self.code_handle = code_handle(code, device)
         self.code, self.device = code, self.code_handle.device
         h = ctypes.c_void_p()
-        _lib.check(lib.ldpc_lqmsa_create(self.code_handle.h, ctypes.byref(h)))
+        _lib.check(self._fn("create")(self.code_handle.h, ctypes.byref(h)))
         self.h = h
         self.set_fixed_point(bits, frac_bits, scale, offset)
 
@@ -861,15 +861,15 @@ class LqmsaHandle:
     def set_layers(self, layers=None):
         """``layers``: one non-negative int per check (two checks of one layer share no variable), or None for the greedy layering."""
         if layers is None:
-            _lib.check(_lib.load().ldpc_lqmsa_set_layers(self.h, None, 0))
+            _lib.check(self._fn("set_layers")(self.h, None, 0))
             return
         lay = np.ascontiguousarray(check_layers(self.code, layers), dtype=np.int32)
-        _lib.check(_lib.load().ldpc_lqmsa_set_layers(self.h, lay.ctypes.data, lay.size))
+        _lib.check(self._fn("set_layers")(self.h, lay.ctypes.data, lay.size))
 
     def layers(self):
         """-> (number of layers, layer of every check as int32 [m])"""
         nl, lay = ctypes.c_int32(0), np.empty(self.code.m, dtype=np.int32)
-        _lib.check(_lib.load().ldpc_lqmsa_get_layers(self.h, ctypes.byref(nl), lay.ctypes.data))
+        _lib.check(self._fn("get_layers")(self.h, ctypes.byref(nl), lay.ctypes.data))
         return nl.value, lay
 
     def info(self):
@@ -971,6 +971,33 @@ class QcHandle(LqmsaHandle):
         o = np.empty(mb.value, dtype=np.int32)
         _lib.check(self._fn("get_order")(self.h, ctypes.byref(mb), o.ctypes.data))
         return o
+
+
+class SlqHandle(LqmsaHandle):
+    """Layered fixed-point min-sum on the streaming kernels (``ldpc_slq_*``): LqmsaHandle's call shapes and outputs with the integer state
+    in HBM tiles (int16 marginals, int8 messages, lane = frame), for any code -- no LDS rule."""
+    family = "ldpc_slq"
+
+    def info(self):
+        out = (ctypes.c_double * 4)()
+        _lib.check(self._fn("info")(self.h, out))
+        return dict(zip(("state_bytes_per_frame", "tiles_per_chunk", "layers", "launches_per_sweep"), (int(v) for v in out)))
+
+    def profile(self, on=True):
+        """Per-kernel timing with HIP events on the decode stream; a decode then ends with a stream synchronise."""
+        _lib.check(self._fn("profile")(self.h, 1 if on else 0, None, None, 0))
+
+    def read_profile(self, reset=True):
+        """-> {kernel class: (milliseconds, launches)} accumulated since the last reset."""
+        ms, ln = (ctypes.c_double * 3)(), (ctypes.c_int64 * 3)()
+        _lib.check(self._fn("profile")(self.h, -1, ms, ln, 1 if reset else 0))
+        return {k: (ms[i], ln[i]) for i, k in enumerate(("layer_passes", "decision_pass", "decode_total"))}
+
+    def last_stats(self):
+        """-> (sweeps enqueued by the last decode, frame repacks, chunks)"""
+        out = (ctypes.c_int32 * 3)()
+        _lib.check(self._fn("last_stats")(self.h, out))
+        return tuple(out)
 
 
 class AdmmHandle:

@@ -133,6 +133,18 @@ SIGNATURES = {
     "ldpc_qc_simulate": (_c.c_int, [_P, _c.c_int, _c.c_double, _c.c_int, _c.c_uint64, _c.c_uint64, _c.c_uint64, _c.c_int64, _c.c_int32,
                                     _c.c_uint32, _c.c_int32, _P, _P]),
     "ldpc_qc_info": (_c.c_int, [_P, _c.POINTER(_c.c_double)]),
+    "ldpc_slq_create": (_c.c_int, [_P, _c.POINTER(_P)]),
+    "ldpc_slq_destroy": (_c.c_int, [_P]),
+    "ldpc_slq_set_fixed_point": (_c.c_int, [_P, _c.c_int, _c.c_int, _c.c_double, _c.c_int]),
+    "ldpc_slq_get_fixed_point": (_c.c_int, [_P, _c.POINTER(_c.c_int), _c.POINTER(_c.c_int), _c.POINTER(_c.c_double), _c.POINTER(_c.c_int)]),
+    "ldpc_slq_set_layers": (_c.c_int, [_P, _P, _c.c_int32]),
+    "ldpc_slq_get_layers": (_c.c_int, [_P, _c.POINTER(_c.c_int32), _P]),
+    "ldpc_slq_decode": (_c.c_int, [_P, _c.c_int, _P, _P, _c.c_int64, _c.c_int32, _c.c_uint32, _P, _P, _P, _P, _P]),
+    "ldpc_slq_simulate": (_c.c_int, [_P, _c.c_int, _c.c_double, _c.c_int, _c.c_uint64, _c.c_uint64, _c.c_uint64, _c.c_int64, _c.c_int32,
+                                     _c.c_uint32, _c.c_int32, _P, _P]),
+    "ldpc_slq_info": (_c.c_int, [_P, _c.POINTER(_c.c_double)]),
+    "ldpc_slq_profile": (_c.c_int, [_P, _c.c_int, _c.POINTER(_c.c_double), _c.POINTER(_c.c_int64), _c.c_int]),
+    "ldpc_slq_last_stats": (_c.c_int, [_P, _c.POINTER(_c.c_int32)]),
     "ldpc_admm_create": (_c.c_int, [_P, _c.POINTER(_P)]),
     "ldpc_admm_destroy": (_c.c_int, [_P]),
     "ldpc_admm_last_repacks": (_c.c_int, [_P, _c.POINTER(_c.c_int)]),

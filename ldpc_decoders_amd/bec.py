@@ -72,6 +72,15 @@ class LQMSA:
                                   "magnitudes to quantise; use SPA / MSA there")
 
 
+class SLQMSA:
+    """The streaming layered fixed-point min-sum quantises and scales magnitudes as LQMSA does; the ternary erasure decoder has none."""
+    id_keys = layered.SLQMSA.id_keys
+
+    def __init__(self, *a, **k):
+        raise NotImplementedError("decoder SLQMSA (streaming layered fixed-point min-sum) does not exist over the bec: the erasure decoder "
+                                  "has no magnitudes to quantise; use SPA / MSA there")
+
+
 class QCMSA:
     """The quasi-cyclic layered fixed-point min-sum quantises and scales magnitudes as LQMSA does; the ternary erasure decoder has none."""
     id_keys = qc.QCMSA.id_keys

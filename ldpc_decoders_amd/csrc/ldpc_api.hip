@@ -18,6 +18,7 @@
 #include "ldpc_lqmsa.hpp"
 #include "ldpc_osd.hpp"
 #include "ldpc_qc.hpp"
+#include "ldpc_slq.hpp"
 
 namespace ldpc {
 
@@ -1607,6 +1608,117 @@ int ldpc_qc_info(ldpc_qc_t h, double* out4) {
     return guarded("ldpc_qc_info", [&]() -> int {
         if (!h || !out4) return LDPC_E_ARG;
         qc_info((const Qc*)h, out4);
+        return LDPC_OK;
+    });
+}
+
+// ---- streaming layered fixed-point min-sum (ldpc_slq.hip) ----
+// no upstream counterpart: ldpc_lqmsa_*'s contract with the integer state in HBM tiles, for codes beyond the LDS
+int ldpc_slq_create(ldpc_code_t code, ldpc_slq_t* out) {
+    return guarded("ldpc_slq_create", [&]() -> int {
+        if (!code || !out) {
+            set_error("ldpc_slq_create: bad arguments");
+            return LDPC_E_ARG;
+        }
+        Slq* h = nullptr;
+        LDPC_TRY(slq_create((Code*)code, &h));
+        *out = (ldpc_slq_t)h;
+        return LDPC_OK;
+    });
+}
+
+int ldpc_slq_destroy(ldpc_slq_t h) {
+    return guarded("ldpc_slq_destroy", [&]() -> int {
+        slq_destroy((Slq*)h);
+        return LDPC_OK;
+    });
+}
+
+int ldpc_slq_set_fixed_point(ldpc_slq_t h, int bits, int frac_bits, double scale, int offset) {
+    return guarded("ldpc_slq_set_fixed_point", [&]() -> int {
+        if (!h) {
+            set_error("ldpc_slq_set_fixed_point: bad arguments");
+            return LDPC_E_ARG;
+        }
+        return slq_set_fixed_point((Slq*)h, bits, frac_bits, scale, offset);
+    });
+}
+
+int ldpc_slq_get_fixed_point(ldpc_slq_t h, int* bits, int* frac_bits, double* scale, int* offset) {
+    return guarded("ldpc_slq_get_fixed_point", [&]() -> int {
+        if (!h || !bits || !frac_bits || !scale || !offset) {
+            set_error("ldpc_slq_get_fixed_point: a handle and four result pointers are needed");
+            return LDPC_E_ARG;
+        }
+        slq_get_fixed_point((const Slq*)h, bits, frac_bits, scale, offset);
+        return LDPC_OK;
+    });
+}
+
+int ldpc_slq_set_layers(ldpc_slq_t h, const int32_t* layer_of_check_host, int32_t m) {
+    return guarded("ldpc_slq_set_layers", [&]() -> int {
+        if (!h) {
+            set_error("ldpc_slq_set_layers: bad arguments");
+            return LDPC_E_ARG;
+        }
+        return slq_set_layers((Slq*)h, layer_of_check_host, m);
+    });
+}
+
+int ldpc_slq_get_layers(ldpc_slq_t h, int32_t* nlayers, int32_t* layer_of_check_host) {
+    return guarded("ldpc_slq_get_layers", [&]() -> int {
+        if (!h || !nlayers) {
+            set_error("ldpc_slq_get_layers: a handle and a result pointer are needed");
+            return LDPC_E_ARG;
+        }
+        slq_get_layers((const Slq*)h, nlayers, layer_of_check_host);
+        return LDPC_OK;
+    });
+}
+
+int ldpc_slq_decode(ldpc_slq_t h, int dtype, const void* priors_dev, const uint8_t* y0_dev, int64_t B, int32_t max_iter, uint32_t flags,
+                    uint8_t* xhat_dev, uint32_t* xhat_bits_dev, int32_t* iters_dev, int16_t* soft_dev, void* stream) {
+    return guarded("ldpc_slq_decode", [&]() -> int {
+        if (!h || !priors_dev || (!xhat_dev && !xhat_bits_dev) || !iters_dev || B < 0) {
+            set_error("ldpc_slq_decode: bad arguments (priors, iters and at least one of xhat / xhat_bits are required)");
+            return LDPC_E_ARG;
+        }
+        return slq_decode((Slq*)h, dtype, priors_dev, y0_dev, B, max_iter, flags, xhat_dev, xhat_bits_dev, iters_dev, soft_dev, (hipStream_t)stream);
+    });
+}
+
+// inside the loop of main.test (src/main.py:37-45)
+int ldpc_slq_simulate(ldpc_slq_t h, int channel, double param, int codeword, uint64_t seed, uint64_t stream_id, uint64_t frame0, int64_t B,
+                      int32_t max_iter, uint32_t flags, int32_t hist_bins, int64_t* counters_dev, void* stream) {
+    return guarded("ldpc_slq_simulate", [&]() -> int {
+        if (!h || !counters_dev || B < 0 || hist_bins < 0) {
+            set_error("ldpc_slq_simulate: bad arguments");
+            return LDPC_E_ARG;
+        }
+        return slq_simulate((Slq*)h, channel, param, codeword, seed, stream_id, frame0, B, max_iter, flags, hist_bins, counters_dev, (hipStream_t)stream);
+    });
+}
+
+int ldpc_slq_info(ldpc_slq_t h, double* out4) {
+    return guarded("ldpc_slq_info", [&]() -> int {
+        if (!h || !out4) return LDPC_E_ARG;
+        slq_info((const Slq*)h, out4);
+        return LDPC_OK;
+    });
+}
+
+int ldpc_slq_profile(ldpc_slq_t h, int enable, double* ms3, int64_t* launches3, int reset) {
+    return guarded("ldpc_slq_profile", [&]() -> int {
+        if (!h) return LDPC_E_ARG;
+        slq_profile((Slq*)h, enable, ms3, launches3, reset);
+        return LDPC_OK;
+    });
+}
+
+int ldpc_slq_last_stats(ldpc_slq_t h, int32_t* out3) {
+    return guarded("ldpc_slq_last_stats", [&]() -> int {
+        if (!h || !out3) return LDPC_E_ARG;
+        slq_last_stats((const Slq*)h, out3);
         return LDPC_OK;
     });
 }

@@ -1,9 +1,10 @@
-"""Layered fixed-point min-sum, LDS-resident (no upstream counterpart -- ``BPA.decode``, src/bpa.py:17-63, runs the flooding schedule in
+"""Layered fixed-point min-sum, LDS-resident (``LQMSA``) and on the streaming kernels (``SLQMSA``) (no upstream counterpart -- ``BPA.decode``, src/bpa.py:17-63, runs the flooding schedule in
 floating point).  ``QMSA``'s integer rule on ``LMSA``'s schedule with the whole frame in the LDS as integers: int16 marginals, int8 check
-messages.  The contract is the ``ldpc_lqmsa_*`` block of include/ldpc_hip.h."""
+messages.  The contract is the ``ldpc_lqmsa_*`` block of include/ldpc_hip.h;
+``SLQMSA`` keeps the same integers in HBM tiles for the codes whose frame does not fit the LDS (``ldpc_slq_*``)."""
 import numpy as np
 
-from ._device import LqmsaHandle, as_code, check_layers
+from ._device import LqmsaHandle, SlqHandle, as_code, check_layers
 
 LDS_BYTES = 160 * 1024
 MAX_DV = 255
@@ -113,3 +114,38 @@ class LQMSA:
             out = self._host(y, priors)
         self.last_iters = out[1]
         return out
+
+
+def check_code_streamed(code):
+    """ValueError unless ``ldpc_slq_create`` takes the code (checked before the library is loaded): the two degree rules of ``check_code``
+    and no size rule."""
+    dc = np.bincount(np.asarray(code.edge_chk), minlength=code.m)
+    dv = np.bincount(np.asarray(code.edge_var), minlength=code.n)
+    if dc.min() < 2:
+        raise ValueError("layered min-sum needs every check to have at least two variables")
+    if dv.max() > MAX_DV:
+        raise ValueError("SLQMSA: a variable of degree %d: the int16 marginals hold degrees up to %d" % (dv.max(), MAX_DV))
+
+
+class SLQMSA(LQMSA):
+    """Layered fixed-point min-sum on the streaming kernels: ``LQMSA``'s rule, parameters, layers and outputs, bit for bit, with the int16
+    marginals and int8 messages in HBM tiles instead of the LDS -- any code, whatever its size.  ``decode`` / ``decode_batch`` / ``layers``
+    / ``last_iters`` as ``LQMSA``."""
+
+    def __init__(self, parity_mtx, max_iter=10, msa_bits=6, msa_frac_bits=2, msa_scale=0.8125, msa_offset=0, layers=None, **_):
+        given = (msa_bits, msa_frac_bits, msa_scale, msa_offset)
+        values = [d if v is None else v for v, d in zip(given, (6, 2, 0.8125, 0))]
+        # (checked before the decoder is created: a bad value never reaches the device)
+        self.msa_bits, self.msa_frac_bits, self.msa_scale, self.msa_offset = check_params(*values)
+        if _.get("precision") == "f16" or _.get("backend") == "fused":
+            raise ValueError("SLQMSA keeps integer tiles in HBM: no fp16 storage, no LDS-resident backend (LQMSA is the LDS-resident kernel)")
+        self.max_iter = int(max_iter)
+        self.code = as_code(parity_mtx)
+        if layers is not None:
+            layers = check_layers(self.code, layers)
+        check_code_streamed(self.code)
+        self.precision = "f64" if _.get("precision") == "f64" else "f32"  # the type the priors are quantised in
+        self.handle = SlqHandle(self.code, _.get("device"), self.msa_bits, self.msa_frac_bits, self.msa_scale, self.msa_offset)
+        if layers is not None:
+            self.handle.set_layers(layers)
+        self.last_iters = None

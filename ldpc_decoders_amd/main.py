@@ -33,6 +33,13 @@ def test(args, comm=None):
             raise SystemExit("--prior-grid: fp32 min-sum over BI-AWGN (biawgn <code> MSA, without --precision f64); %s quantises its priors itself" % row.name)
         if args.backend == "stream":
             raise SystemExit("--backend stream: %s is LDS-resident (--backend auto / fused); layered min-sum on the streaming kernels is LMSA" % row.name)
+    if row.integer_streamed:  # (integer tiles in HBM: refused before a decoder exists)
+        if args.precision == "f16":
+            raise SystemExit("--precision f16: %s keeps int16 marginals and int8 messages and has no arithmetic to store in fp16" % row.name)
+        if getattr(args, "prior_grid", None) is not None:
+            raise SystemExit("--prior-grid: fp32 min-sum over BI-AWGN (biawgn <code> MSA, without --precision f64); %s quantises its priors itself" % row.name)
+        if args.backend == "fused":
+            raise SystemExit("--backend fused: %s runs on the streaming kernels (--backend auto / stream); the LDS-resident integer kernel is LQMSA" % row.name)
     code = codes.get_code(args.code)
     if row.quasi_cyclic:  # (the result file carries the lifting size the decoder runs with, not the 0 that asks for it)
         try:
@@ -47,14 +54,14 @@ def test(args, comm=None):
     # --codeword -1 (a random codeword per frame, src/main.py:38): on the device for the BP decoders -- from the code book where the code
     # has one, from the systematic GF(2) encoder (Code.encoder()) otherwise -- and for ML over the BEC of a code without a code book (the
     # elimination decoder, encoder words); the reference's sequential loop on host noise for the others
-    device_words = row.device_words or row.hard or row.integer_layered or row.quasi_cyclic or (args.channel == "bec" and args.decoder == "ML" and code.gen_mtx is None)
+    device_words = row.device_words or row.hard or row.integer_layered or row.integer_streamed or row.quasi_cyclic or (args.channel == "bec" and args.decoder == "ML" and code.gen_mtx is None)
     exact = bool(args.exact) or (args.codeword == -1 and not device_words)
     if exact and comm.world > 1:
         raise SystemExit("--exact / --codeword -1 follow the reference's sequential rule and run on a single rank")
     if exact and args.np_seed is not None:
         np.random.seed(args.np_seed)
     kwargs = dict(vars(args))
-    if row.pops_layers or row.integer_layered or row.quasi_cyclic:
+    if row.pops_layers or row.integer_layered or row.integer_streamed or row.quasi_cyclic:
         kwargs.pop("layers", None)  # (--layers is ADMMA's network shape, src/utils.py:43: not a layering of the checks; LMSA takes the greedy one)
     # fp32 message arithmetic in the throughput mode -- except min-sum over the BSC: every LLR is +-L there, the decoder is
     # tie-dominated and only the reference's fp64 arithmetic reproduces its curves
@@ -151,7 +158,7 @@ def test(args, comm=None):
 
 
 def build_parser():
-    """The reference's grammar with the reference's decoder names, plus this build's own (``registry.ROWS``: NMSA, QMSA, LMSA, OSD, QCMSA, LQMSA, GALB)."""
+    """The reference's grammar with the reference's decoder names, plus this build's own (``registry.ROWS``: NMSA, QMSA, LMSA, SLQMSA, OSD, QCMSA, LQMSA, GALB)."""
     return utils.setup_parser(codes.get_code_names(), models.keys(), all_decoder_names)
 
 

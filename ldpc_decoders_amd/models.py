@@ -14,6 +14,7 @@ layered_decoder_names = registry.names("layered")
 post_processing_decoder_names = registry.names("post_processing")
 quasi_cyclic_decoder_names = registry.names("quasi_cyclic")
 layered_fixed_point_decoder_names = registry.names("layered_fixed_point")
+streaming_fixed_point_decoder_names = registry.names("streaming_fixed_point")
 hard_decision_decoder_names = registry.names("hard_decision")
 all_decoder_names = [r.name for r in registry.ROWS]  # the parser's choices
 

@@ -11,7 +11,7 @@ from . import admm, bpa, hard, layered, ml, qc
 
 Row = namedtuple("Row", [
     "name",
-    "group",          # which list of ``models`` carries the name: reference (src/utils.py:16), extra, fixed_point, layered, post_processing, quasi_cyclic, layered_fixed_point, hard_decision
+    "group",          # which list of ``models`` carries the name: reference (src/utils.py:16), extra, fixed_point, layered, post_processing, quasi_cyclic, layered_fixed_point, streaming_fixed_point, hard_decision
     "backing",        # the bpa / admm class the LLR wrappers of biawgn / bsc hold ({channel: class}: the channel's own class; None: not built)
     "bec_refusal",    # None: the bec module has its own class of this name; else (docstring, sentence) of the class that raises there
     "osd_front",      # may run in front of bpa.OSD (osd_bp)
@@ -23,9 +23,10 @@ Row = namedtuple("Row", [
     "refuses_fused",  # --backend fused is refused before a decoder exists
     "hard",           # decodes hard decisions (one bit per message): words drawn on the device, no --precision f16, no --prior-grid, --max-iter >= 1
     "integer_layered",  # the LDS-resident integer kernel on the layered schedule: words drawn on the device, --layers dropped, no --precision f16, no --prior-grid, no --backend stream
+    "integer_streamed",  # the integer kernels on the layered schedule with the state in HBM tiles: words drawn on the device, --layers dropped, no --precision f16, no --prior-grid, no --backend fused
     "quasi_cyclic",   # the shift-addressed integer kernel for quasi-cyclic codes: as integer_layered, and --qc-lift resolved to the code's lifting size
 ])
-Row.__new__.__defaults__ = (None, False, False, False, False, None, False, False, False, False, False)
+Row.__new__.__defaults__ = (None, False, False, False, False, None, False, False, False, False, False, False)
 
 ROWS = [
     Row("ML", "reference", {"biawgn": ml.BiawgnML, "bsc": ml.BscML}),
@@ -47,6 +48,8 @@ ROWS = [
         ("Layered min-sum is corrected min-sum on another schedule: it has no meaning over the erasure channel either.",
          "decoder LMSA (layered corrected min-sum) does not exist over the bec: the erasure decoder has no magnitudes to correct; use SPA / MSA there"),
         osd_front=True, device_words=True, tie_dominated=True, prior_grid=False, pops_layers=True, refuses_fused=True),
+    # LQMSA's contract with the integer state in HBM tiles, for the codes beyond the LDS; bec writes its own (refusing) class of this name
+    Row("SLQMSA", "streaming_fixed_point", layered.SLQMSA, integer_streamed=True),
     Row("OSD", "post_processing", bpa.OSD,  # BP + ordered-statistics decoding of the frames BP fails on (NMSA in front)
         ("Ordered-statistics post-processing orders soft values; over the erasure channel ``ML`` (elimination of the erased bits) is exact.",
          "decoder OSD (BP + ordered-statistics post-processing) does not exist over the bec: use ML there, the elimination decoder is exact"),

@@ -1,7 +1,7 @@
 """CLI flags, logging and the JSON result store -- mirror of the reference's ``src/utils.py:21-68,118-140``.
 
 The argument grammar (positional ``channel code decoder`` + ``--codeword --min-wec --params --max-iter ...``) and
-the result files (``<channel>-<code>-<decoder>-<codeword>-<min_wec>-<max_iter>.json``; NMSA, LMSA: ``...-<max_iter>-<msa_scale>-<msa_offset>.json``; QMSA, LQMSA: ``...-<max_iter>-<msa_bits>-<msa_frac_bits>-<msa_scale>-<msa_offset>.json``; QCMSA: the same followed by ``-<qc_lift>``; OSD: ``...-<max_iter>-<msa_scale>-<msa_offset>-<osd_order>-<osd_depth>.json``; GALB: ``...-<max_iter>-<gal_threshold>.json``; with the id keys first, then
+the result files (``<channel>-<code>-<decoder>-<codeword>-<min_wec>-<max_iter>.json``; NMSA, LMSA: ``...-<max_iter>-<msa_scale>-<msa_offset>.json``; QMSA, LQMSA, SLQMSA: ``...-<max_iter>-<msa_bits>-<msa_frac_bits>-<msa_scale>-<msa_offset>.json``; QCMSA: the same followed by ``-<qc_lift>``; OSD: ``...-<max_iter>-<msa_scale>-<msa_offset>-<osd_order>-<osd_depth>.json``; GALB: ``...-<max_iter>-<gal_threshold>.json``; with the id keys first, then
 ``tot wec wer bec ber`` as ``{str(param): value}``) are what ``simulations.py`` / ``run_sims.sh`` emit and what
 ``graph.py`` reads upstream (src/graph.py:25-58), so flag names, defaults and the file layout are kept; the help texts are
 this build's own.  ``--mu --eps --allow-pseudo`` configure the ADMM decoder; ``--layers --train --apprx`` belong to ADMMA, which
@@ -14,7 +14,7 @@ import os
 from collections import OrderedDict
 
 from . import codes
-from .models import decoder_names, extra_decoder_names, fixed_point_decoder_names, layered_decoder_names, post_processing_decoder_names, quasi_cyclic_decoder_names, layered_fixed_point_decoder_names, hard_decision_decoder_names  # noqa: F401  (re-exported like upstream utils.decoder_names)
+from .models import decoder_names, extra_decoder_names, fixed_point_decoder_names, layered_decoder_names, post_processing_decoder_names, quasi_cyclic_decoder_names, layered_fixed_point_decoder_names, streaming_fixed_point_decoder_names, hard_decision_decoder_names  # noqa: F401  (re-exported like upstream utils.decoder_names)
 
 strl = lambda ll: (str(it_) for it_ in ll)  # noqa: E731
 
@@ -68,15 +68,15 @@ def setup_parser(code_names, channel_names, decoder_names):
                         "for those priors")
     g.add_argument("--msa-scale", type=float, default=0.8125,
                    help="NMSA, LMSA (corrected min-sum, flooding / layered): every check message is multiplied by this, 0 < scale <= 1 (1 = plain min-sum); "
-                        "QMSA, LQMSA (fixed-point min-sum, flooding / layered): likewise, a multiple of 1/64")
+                        "QMSA, LQMSA, SLQMSA (fixed-point min-sum, flooding / layered in the LDS / layered on the streaming kernels): likewise, a multiple of 1/64")
     g.add_argument("--msa-offset", type=float, default=0.0,
                    help="NMSA, LMSA (corrected min-sum, flooding / layered): subtracted from every check-message magnitude, clamped at 0 (offset >= 0); "
-                        "QMSA, LQMSA (fixed-point min-sum, flooding / layered): likewise, an integer number of levels")
+                        "QMSA, LQMSA, SLQMSA (fixed-point min-sum): likewise, an integer number of levels")
     g.add_argument("--msa-bits", type=int, default=6,
                    help="QMSA (fixed-point min-sum): word length q of the channel values and messages, 2..12; they saturate at +-(2^(q-1) - 1) levels; "
-                        "LQMSA (layered fixed-point min-sum): likewise, 2..8")
+                        "LQMSA, SLQMSA (layered fixed-point min-sum, in the LDS / on the streaming kernels for codes of any size): likewise, 2..8")
     g.add_argument("--msa-frac-bits", type=int, default=2,
-                   help="QMSA, LQMSA (fixed-point min-sum, flooding / layered): fractional bits k of the quantiser, -8..8: one level is 2^-k of LLR")
+                   help="QMSA, LQMSA, SLQMSA (fixed-point min-sum, flooding / layered): fractional bits k of the quantiser, -8..8: one level is 2^-k of LLR")
     g.add_argument("--osd-order", type=int, default=0, choices=[0, 1],
                    help="OSD (BP + ordered-statistics post-processing of the frames BP fails on): 0 = the codeword that agrees with BP's hard "
                         "decisions on the most reliable information set, 1 = also try single flips of its least reliable bits")
