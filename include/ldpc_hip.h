@@ -285,6 +285,10 @@ typedef struct ldpc_encoder_s* ldpc_encoder_t;
 int ldpc_encoder_create(int device, int32_t n, int32_t k, int32_t r, const int32_t* info_pos, const int32_t* par_pos, const uint8_t* P_bits_host,
                         ldpc_encoder_t* out);
 int ldpc_encoder_destroy(ldpc_encoder_t enc);
+/* Read-only: the launch shape the handle settled on, so that a test can assert which kernels it reaches.  out[0] = nt, the 32-column
+ * tiles per wave (1, 2, 4 or 8: the instantiation of the GEMM kernel); out[1] = column groups of nt tiles (the grid's y); out[2] =
+ * k-groups of 128 information bits, ceil(k / 128); out[3] = 8192-bit chunks of the information-bit kernel, ceil(out[2] / 64). */
+int ldpc_encoder_info(ldpc_encoder_t enc, int32_t out[4]);
 /* Codewords of B given information words: info_dev [B, k] uint8 in {0,1} -> sent_dev [B, n] uint8 (the layout ldpc_count_errors_words
  * reads).  u . P runs on v_mfma_i32_32x32x32_i8 (int32 accumulation, & 1): exact.  Uses a workspace of the handle (one call at a time). */
 int ldpc_encode(ldpc_encoder_t enc, const uint8_t* info_dev, int64_t B, uint8_t* sent_dev, void* stream);

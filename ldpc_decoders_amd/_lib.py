@@ -85,6 +85,7 @@ SIGNATURES = {
                                         _c.c_uint64, _c.c_int32, _c.c_uint32, _c.c_int32, _P, _P]),
     "ldpc_encoder_create": (_c.c_int, [_c.c_int, _c.c_int32, _c.c_int32, _c.c_int32, _P, _P, _P, _c.POINTER(_P)]),
     "ldpc_encoder_destroy": (_c.c_int, [_P]),
+    "ldpc_encoder_info": (_c.c_int, [_P, _P]),
     "ldpc_encode": (_c.c_int, [_P, _P, _c.c_int64, _P, _P]),
     "ldpc_encode_random": (_c.c_int, [_P, _c.c_uint64, _c.c_uint64, _c.c_uint64, _c.c_int64, _P, _P]),
     "ldpc_channel_sent": (_c.c_int, [_c.c_int, _c.c_int, _c.c_double, _P, _c.c_uint64, _c.c_uint64, _c.c_uint64, _c.c_int64, _c.c_int32,

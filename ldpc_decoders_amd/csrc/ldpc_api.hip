@@ -1020,6 +1020,10 @@ int ldpc_encoder_destroy(ldpc_encoder_t enc) {
     });
 }
 
+int ldpc_encoder_info(ldpc_encoder_t enc, int32_t out[4]) {
+    return guarded("ldpc_encoder_info", [&]() -> int { return encoder_info((const Encoder*)enc, out); });
+}
+
 int ldpc_encode(ldpc_encoder_t enc, const uint8_t* info_dev, int64_t B, uint8_t* sent_dev, void* stream) {
     return guarded("ldpc_encode", [&]() -> int { return encode((Encoder*)enc, info_dev, B, sent_dev, (hipStream_t)stream); });
 }

@@ -319,6 +319,15 @@ int encoder_create(int device, int32_t n, int32_t k, int32_t r, const int32_t* i
     return LDPC_OK;
 }
 
+int encoder_info(const Encoder* e, int32_t out[4]) {
+    if (!e || !out) {
+        set_error("ldpc_encoder_info: bad arguments");
+        return LDPC_E_ARG;
+    }
+    out[0] = e->nt, out[1] = e->cgroups, out[2] = e->kgroups, out[3] = (e->kgroups + 63) / 64;
+    return LDPC_OK;
+}
+
 int encode(Encoder* e, const uint8_t* u, int64_t B, uint8_t* sent, hipStream_t st) {
     if (!e || !sent || B < 0 || (B > 0 && e->k > 0 && !u)) {
         set_error("ldpc_encode: bad arguments");

@@ -129,6 +129,13 @@ class EncoderHandle:
         except Exception:
             pass
 
+    def info(self):
+        """The launch shape of the handle (``ldpc_encoder_info``): {"nt": 32-column tiles per wave of ``k_encode``, "cgroups": column groups
+        of nt tiles, "kgroups": ceil(k / 128), "chunks": 8192-bit chunks of ``k_info``}."""
+        out = (ctypes.c_int32 * 4)()
+        _lib.check(_lib.load().ldpc_encoder_info(self.h, out))
+        return dict(zip(("nt", "cgroups", "kgroups", "chunks"), (int(x) for x in out)))
+
     def encode(self, u, out=None):
         import torch
 

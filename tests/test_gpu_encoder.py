@@ -8,7 +8,6 @@ import pytest
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-INFO_BLOCK0 = 0x80000000
 
 
 def _irregular_10000():
@@ -18,21 +17,10 @@ def _irregular_10000():
 
 
 def _philox_info_bits(seed, stream, frame0, B, k):
-    """Information bits of frames [frame0, frame0 + B) from the oracle's Philox4x32-10: bit t of word w of block 0x80000000 + j is bit
-    128 j + 32 w + t."""
-    import bp_oracle as O
+    """The oracle's statement of the random information bits: shared with test_gpu_encoder_edges.py, so it lives in encoder_codes.py."""
+    from encoder_codes import philox_info_bits
 
-    nblk = (k + 127) // 128
-    f = np.arange(frame0, frame0 + B, dtype=np.uint64)
-    ctr = np.zeros((B, nblk, 4), dtype=np.uint32)
-    ctr[..., 0] = (INFO_BLOCK0 + np.arange(nblk)).astype(np.uint32)[None, :]
-    ctr[..., 1] = np.uint32(stream)
-    ctr[..., 2] = (f & np.uint64(0xFFFFFFFF)).astype(np.uint32)[:, None]
-    ctr[..., 3] = (f >> np.uint64(32)).astype(np.uint32)[:, None]
-    key = np.zeros((B, nblk, 2), dtype=np.uint32)
-    key[..., 0], key[..., 1] = seed & 0xFFFFFFFF, seed >> 32
-    words = np.ascontiguousarray(O.philox4x32(ctr, key), dtype=np.uint32).reshape(B, nblk * 4)
-    return np.unpackbits(words.view(np.uint8), axis=1, bitorder="little")[:, :k]
+    return philox_info_bits(seed, stream, frame0, B, k)
 
 
 @pytest.mark.parametrize("name,B", [("7_4_hamming", 100), ("12_3_4_ldpc", 1), ("1200_3_6_ldpc", 1), ("1200_3_6_ldpc", 1000),
