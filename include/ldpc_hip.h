@@ -536,8 +536,19 @@ int ldpc_lqmsa_info(ldpc_lqmsa_t h, double* out4);
  * from an atomic dispenser.  LDS rule: LQMSA's layout and bound with dc_max = the largest block-row degree,
  *     lqmsa_lds_bytes(m, n, E, dc_max) = 8 ceil(2 n / 8) + m * row(dc_max) + 16 <= 163840.
  * With F = floor(163840 / bytes), W is LQMSA's rule for F capped at the smallest of 1, 2, 4, 8 that is >= ceil(Z / 64) (a block row has
- * ceil(Z / 64) wave passes); the environment variable LDPC_QC_NW (1, 2, 4, 8; read at create) overrides it.  With Z < 64 part of the
- * wave idles.  Handles are not thread-safe (one workspace). */
+ * ceil(Z / 64) wave passes); the environment variable LDPC_QC_NW (1, 2, 4, 8; read at create) overrides it.
+ * Several frames per wave.  With Z < 64 one frame leaves part of the wave dark.  For Z <= 32 (a block row is one pass) a second kernel
+ * puts P frames, 2 <= P <= floor(64 / Z), into one workgroup of one wave: lane L serves frame slot L / Z with row L mod Z, lanes >= P Z
+ * idle, slot g keeps its own frame image (the layout above) at byte g * stride of the LDS,
+ *     stride(bytes, Z) = the smallest multiple of 16 that is >= bytes and congruent to 16 ceil(2 Z / 16) modulo 128
+ * (slots that share a 32-lane group then read one block column on disjoint LDS banks).  The slots are independent: own frame index, own
+ * sweep count, the syndrome is the wave's ballot under the slot's lane mask, and a slot whose frame has left (syndrome zero, cap, or the
+ * received word at sweep 0) writes its outputs and draws the next frame at once while the others keep sweeping.  The outputs are those of
+ * the contract above for every P.  The rule, pick(Z, bytes): 1 for Z > 32, else min(floor(64 / Z), floor(163840 / stride)), at least
+ * 1; at P >= 2 the grid holds min(floor(163840 / (P stride)), 32) workgroups per CU and LDPC_QC_NW has no part.  Z = 33 .. 63 and the
+ * tail pass of Z > 64 still leave lanes dark.  After create P = 1: ldpc_qcpack_set opts in.  The environment variable LDPC_QC_PACK_GRID
+ * (read at create) caps the grid of the second kernel; with 1 the frames are handed out in index order (tests).
+ * Handles are not thread-safe (one workspace). */
 typedef struct ldpc_qc_s* ldpc_qc_t;
 int ldpc_qc_create(ldpc_code_t code, int32_t Z, ldpc_qc_t* out);
 int ldpc_qc_destroy(ldpc_qc_t h);
@@ -556,6 +567,11 @@ int ldpc_qc_decode(ldpc_qc_t h, int dtype, const void* priors_dev, const uint8_t
 int ldpc_qc_simulate(ldpc_qc_t h, int channel, double param, int codeword, uint64_t seed, uint64_t stream_id, uint64_t frame0, int64_t B,
                      int32_t max_iter, uint32_t flags, int32_t hist_bins, int64_t* counters_dev, void* stream);
 int ldpc_qc_info(ldpc_qc_t h, double* out4);
+/* Frames per wave of ldpc_qc_decode / ldpc_qc_simulate on this handle.  0: the rule's pick; 1: one frame per workgroup (the state after
+ * create); P >= 2: LDPC_E_ARG (the message names Z and the bytes, the previous value stays) unless P Z <= 64 and P stride <= 163840.
+ * With P >= 2 ldpc_qc_info reports {bytes per frame, 1, P * workgroups per CU, workgroups}. */
+int ldpc_qcpack_set(ldpc_qc_t h, int32_t frames_per_wave);
+int ldpc_qcpack_get(ldpc_qc_t h, int32_t* frames_per_wave, int32_t* rule_pick);
 
 /* ---- Streaming layered fixed-point min-sum (SLQMSA): the LQMSA contract for codes beyond the LDS -------------------
  * No upstream counterpart.

@@ -935,7 +935,7 @@ class QcHandle(LqmsaHandle):
     block row of the base matrix one layer; the library finds the shifts for the lifting size ``Z`` from the code's edge list."""
     family = "ldpc_qc"
 
-    def __init__(self, code, Z, device=None, bits=6, frac_bits=2, scale=0.8125, offset=0):
+    def __init__(self, code, Z, device=None, bits=6, frac_bits=2, scale=0.8125, offset=0, pack=1):
         lib = _lib.load()
         self.code_handle = code_handle(code, device)
         self.code, self.device = code, self.code_handle.device
@@ -943,6 +943,19 @@ class QcHandle(LqmsaHandle):
         _lib.check(lib.ldpc_qc_create(self.code_handle.h, int(Z), ctypes.byref(h)))
         self.h = h
         self.set_fixed_point(bits, frac_bits, scale, offset)
+        if pack != 1:
+            self.set_pack(pack)
+
+    def set_pack(self, P):
+        """Frames per wave (``ldpc_qcpack_set``): 0 the rule's pick (``qc.qc_pack``), 1 one frame per workgroup, P >= 2 needs Z <= 32,
+        P Z <= 64 and P strides of LDS.  No result depends on it."""
+        _lib.check(_lib.load().ldpc_qcpack_set(self.h, int(P)))
+
+    def pack(self):
+        """-> (frames per wave in force, the rule's pick)"""
+        P, pick = ctypes.c_int32(0), ctypes.c_int32(0)
+        _lib.check(_lib.load().ldpc_qcpack_get(self.h, ctypes.byref(P), ctypes.byref(pick)))
+        return P.value, pick.value
 
     def set_layers(self, layers=None):
         raise TypeError("the layers of a quasi-cyclic decoder are its block rows: set_order")

@@ -134,6 +134,8 @@ SIGNATURES = {
     "ldpc_qc_simulate": (_c.c_int, [_P, _c.c_int, _c.c_double, _c.c_int, _c.c_uint64, _c.c_uint64, _c.c_uint64, _c.c_int64, _c.c_int32,
                                     _c.c_uint32, _c.c_int32, _P, _P]),
     "ldpc_qc_info": (_c.c_int, [_P, _c.POINTER(_c.c_double)]),
+    "ldpc_qcpack_set": (_c.c_int, [_P, _c.c_int32]),
+    "ldpc_qcpack_get": (_c.c_int, [_P, _c.POINTER(_c.c_int32), _c.POINTER(_c.c_int32)]),
     "ldpc_slq_create": (_c.c_int, [_P, _c.POINTER(_P)]),
     "ldpc_slq_destroy": (_c.c_int, [_P]),
     "ldpc_slq_set_fixed_point": (_c.c_int, [_P, _c.c_int, _c.c_int, _c.c_double, _c.c_int]),

@@ -1616,6 +1616,28 @@ int ldpc_qc_info(ldpc_qc_t h, double* out4) {
     });
 }
 
+// several frames per wave for Z <= 32 (ldpc_qc.hip k_qc_pack); the prefix differs, the handle is ldpc_qc_*'s
+int ldpc_qcpack_set(ldpc_qc_t h, int32_t frames_per_wave) {
+    return guarded("ldpc_qcpack_set", [&]() -> int {
+        if (!h) {
+            set_error("ldpc_qcpack_set: bad arguments");
+            return LDPC_E_ARG;
+        }
+        return qcpack_set((Qc*)h, frames_per_wave);
+    });
+}
+
+int ldpc_qcpack_get(ldpc_qc_t h, int32_t* frames_per_wave, int32_t* rule_pick) {
+    return guarded("ldpc_qcpack_get", [&]() -> int {
+        if (!h || !frames_per_wave || !rule_pick) {
+            set_error("ldpc_qcpack_get: a handle and two result pointers are needed");
+            return LDPC_E_ARG;
+        }
+        qcpack_get((const Qc*)h, frames_per_wave, rule_pick);
+        return LDPC_OK;
+    });
+}
+
 // ---- streaming layered fixed-point min-sum (ldpc_slq.hip) ----
 // no upstream counterpart: ldpc_lqmsa_*'s contract with the integer state in HBM tiles, for codes beyond the LDS
 int ldpc_slq_create(ldpc_code_t code, ldpc_slq_t* out) {

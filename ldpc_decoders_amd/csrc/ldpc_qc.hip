@@ -9,7 +9,7 @@
 //     ctl   4 words              frame index, two syndrome flags used by alternate sweeps, spare
 // One workgroup of NW waves owns one frame; lane L of pass k of a block row owns check i Z + 64 k + L, pass k goes to wave k mod NW; a block
 // row ends with a workgroup barrier.  Neighbouring lanes touch neighbouring int16 marginals (up to the one wrap), which share a dword, so
-// marginals are read and written as 16-bit LDS accesses only.
+// marginals are read and written as 16-bit LDS accesses only.  For Z <= 32 a second kernel, k_qc_pack below, puts several frames into a wave.
 // Table (Qc::tab, rebuilt by qc_set_order), in global memory in processing order and read with wave-uniform addresses through the constant
 // address space, so every entry arrives by a scalar load: per block row {degree, offset of its edges, i Z, 0}, per edge {j Z, shift}.
 #include <algorithm>
@@ -32,6 +32,7 @@ struct Qc {
     bool odd_check = false;
     int num_cu = 0, nw = 1, frames_per_cu = 0, row_bytes = 8;
     int64_t lds_bytes = 0;
+    int pack = 1, pack_grid = 0;  // frames per wave (>= 2: k_qc_pack); LDPC_QC_PACK_GRID, 0 = no cap on the packed kernel's grid
     std::vector<int32_t> row_ptr, col, shift;  // the base matrix by block rows: nonzero blocks of block row i are row_ptr[i] .. row_ptr[i + 1]
     std::vector<int32_t> order;                // block row processed at each position
     DevBuf tab;                                // int32: [mb][4] headers in processing order, then [nonzero blocks][2]
@@ -248,6 +249,166 @@ const void* kernel_of(int nw, bool row8) {
     }
 }
 
+// ---- several frames per wave: Z <= 32, a block row is one pass and floor(64 / Z) frames fill the lanes a single frame leaves dark ----
+// One workgroup of one wave owns P frame slots.  Lane L serves slot g = L / Z with row r = L - g Z; lanes >= P Z idle.  Slot g keeps its own
+// frame image, the layout above, at byte g * stride of the LDS (qc_pack_stride); the table is shared and still read by scalar loads, the
+// degree dispatch is still a scalar branch.  The slots are independent: each has its own frame index and sweep count (held by its lanes), its
+// syndrome is the wave's ballot under the slot's lane mask, and a slot whose frame has left is served at once -- outputs written, the next
+// frame drawn, again for as long as a fresh frame leaves on its received word -- while the others keep their state.  Serving is done by
+// the whole wave (64 lanes over a frame's n values), one slot after the other, and the slots served together draw their frames with one
+// atomic on the dispenser (one word takes a bounded number of returning atomics per microsecond, and short frames reach that bound).
+struct QcPackArgs {
+    QcArgs a;
+    int32_t P, stride;
+};
+
+constexpr uint32_t QC_NO_FRAME = 0xffffffffu;  // frame indices stay below 2^31
+
+// frame f of sweep count it leaves the image at marg: xhat, iters, soft and the packed words as k_qc writes them (it == 0: the received word)
+__device__ __forceinline__ void qc_pack_write(const QcArgs& a, const int16_t* marg, uint32_t f, int it, int lane) {
+    const int n = a.n, Wd = (n + 31) / 32;
+    const uint8_t* __restrict__ yf = a.y0 ? a.y0 + (size_t)f * n : nullptr;
+    if (lane == 0) a.iters[f] = it;
+    if (a.xhat)
+        for (int v = lane; v < n; v += 64) a.xhat[(size_t)f * n + v] = it == 0 ? yf[v] : (uint8_t)(marg[v] < 0);
+    if (a.soft)
+        for (int v = lane; v < n; v += 64) a.soft[(size_t)f * n + v] = it == 0 ? (int16_t)0 : marg[v];
+    if (a.bits)
+        for (int v0 = 0; v0 < n; v0 += 64) {
+            const int v = v0 + lane;
+            const bool bit = v < n && (it == 0 ? (yf[v] & 1u) != 0u : marg[v] < 0);
+            const unsigned long long b = __ballot(bit);
+            if (lane == 0) {
+                uint32_t* out = a.bits + (size_t)f * Wd + (v0 >> 5);
+                out[0] = (uint32_t)b;
+                if ((v0 >> 5) + 1 < Wd) out[1] = (uint32_t)(b >> 32);
+            }
+        }
+}
+
+template <typename T, bool ROW8>
+__global__ __launch_bounds__(64) void k_qc_pack(const QcPackArgs pa) {
+    extern __shared__ __attribute__((aligned(16))) uint32_t qc_sm[];
+    const QcArgs& a = pa.a;
+    const int n = a.n, m = a.m, Z = a.Z, mb = a.mb;
+    const int lane = threadIdx.x;
+    const size_t c2v_at = ((size_t)2 * n + 7) / 8 * 8;
+    const T step = (T)a.step, vmax = (T)a.vmax;
+    const qc_tab_t tab = (qc_tab_t)a.tab;
+    const bool live = lane < pa.P * Z;
+    const int g = live ? lane / Z : 0;  // computed once
+    const int r = lane - g * Z;
+    const unsigned long long slot0 = (1ull << Z) - 1ull;                 // the lanes of slot 0
+    const unsigned long long mine = live ? slot0 << (g * Z) : 0ull;      // the lanes of this lane's slot
+    int16_t* const marg = (int16_t*)((uint8_t*)qc_sm + (size_t)g * pa.stride);
+    uint8_t* const c2v = (uint8_t*)marg + c2v_at;
+    uint32_t f = QC_NO_FRAME;  // the slot's frame and its sweeps so far, the same in all lanes of a slot
+    int it = 0;
+    bool need = live;  // the slot's frame has left (or it never had one)
+    for (;;) {
+        // serve the slots whose frame has left; a round: write their frames out, draw as many new ones, check the received words, load
+        for (unsigned long long todo = __ballot(need); todo != 0ull;) {
+            int k = 0;
+            for (unsigned long long t = todo; t != 0ull; ++k) {
+                const int lead = __ffsll((long long)t) - 1;
+                const int g0 = __builtin_amdgcn_readlane(g, lead);
+                const uint32_t f0 = (uint32_t)__builtin_amdgcn_readlane((int)f, lead);
+                if (f0 != QC_NO_FRAME)
+                    qc_pack_write(a, (const int16_t*)((uint8_t*)qc_sm + (size_t)g0 * pa.stride), f0, __builtin_amdgcn_readlane(it, lead), lane);
+                t &= ~(slot0 << (g0 * Z));
+            }
+            uint32_t drawn = 0u;
+            if (lane == 0) drawn = atomicAdd(a.dispenser, (uint32_t)k);  // frames drawn .. drawn + k - 1, in slot order
+            drawn = (uint32_t)__builtin_amdgcn_readfirstlane((int)drawn);
+            __syncthreads();  // the outputs above have read the images
+            unsigned long long again = 0ull;
+            for (unsigned long long t = todo; t != 0ull; ++drawn) {
+                const int lead = __ffsll((long long)t) - 1;
+                const int g0 = __builtin_amdgcn_readlane(g, lead);
+                const unsigned long long lanes0 = slot0 << (g0 * Z);
+                t &= ~lanes0;
+                uint32_t f0 = drawn;
+                if ((int64_t)f0 >= a.B) {
+                    f0 = QC_NO_FRAME;  // the slot is dead
+                } else {
+                    bool bad = true;
+                    if (!a.no_early && a.y0) {  // H y0 = 0?  Then the frame leaves before its priors are read, and the slot draws again
+                        const uint8_t* __restrict__ yf = a.y0 + (size_t)f0 * n;
+                        bad = false;
+                        for (int l = 0; l < mb && !bad; ++l) {
+                            const int deg = tab[4 * l];
+                            const qc_tab_t e = tab + tab[4 * l + 1];
+                            uint32_t par = 0;
+                            if (lane < Z)
+                                for (int j = 0; j < deg; ++j) par ^= (uint32_t)(yf[qc_var(lane, Z, e[2 * j], e[2 * j + 1])] & 1u);
+                            bad = __ballot(par != 0u) != 0ull;  // wave-uniform
+                        }
+                    }
+                    if (bad) {
+                        const T* __restrict__ pr = (const T*)a.priors + (size_t)f0 * n;
+                        int16_t* const marg0 = (int16_t*)((uint8_t*)qc_sm + (size_t)g0 * pa.stride);
+                        uint32_t* const cw0 = (uint32_t*)((uint8_t*)marg0 + c2v_at);
+                        for (int v = lane; v < n; v += 64) marg0[v] = (int16_t)(int)quantise_prior<T>(pr[v], step, vmax);
+                        for (int i = lane; i < m * (a.row_bytes / 4); i += 64) cw0[i] = 0u;
+                    } else {
+                        again |= lanes0;  // written out with 0 sweeps in the next round
+                    }
+                }
+                if ((mine >> lead) & 1ull) {  // the lanes of slot g0
+                    f = f0;
+                    it = 0;
+                }
+            }
+            todo = again;
+        }
+        const bool active = f != QC_NO_FRAME;
+        if (__ballot(active) == 0ull) break;
+        __syncthreads();  // the new images are in place
+        for (int l = 0; l < mb; ++l) {
+            const int deg = tab[4 * l];  // wave-uniform: the dispatch below is a scalar branch
+            const qc_tab_t e = tab + tab[4 * l + 1];
+            const int row0 = tab[4 * l + 2];
+            if (active) {
+                if constexpr (ROW8) {
+                    uint2* rowp = (uint2*)(c2v + (size_t)(row0 + r) * 8);
+                    switch (deg) {
+                        case 2: qc_check8<2>(marg, rowp, r, Z, e, a.scale64, a.offset, a.vmax); break;
+                        case 3: qc_check8<3>(marg, rowp, r, Z, e, a.scale64, a.offset, a.vmax); break;
+                        case 4: qc_check8<4>(marg, rowp, r, Z, e, a.scale64, a.offset, a.vmax); break;
+                        case 5: qc_check8<5>(marg, rowp, r, Z, e, a.scale64, a.offset, a.vmax); break;
+                        case 6: qc_check8<6>(marg, rowp, r, Z, e, a.scale64, a.offset, a.vmax); break;
+                        case 7: qc_check8<7>(marg, rowp, r, Z, e, a.scale64, a.offset, a.vmax); break;
+                        default: qc_check8<8>(marg, rowp, r, Z, e, a.scale64, a.offset, a.vmax); break;
+                    }
+                } else {
+                    qc_check_loop(marg, c2v + (size_t)(row0 + r) * a.row_bytes, deg, r, Z, e, a.scale64, a.offset, a.vmax);
+                }
+            }
+            __syncthreads();  // one wave: orders the block rows' LDS accesses, no hardware barrier
+        }
+        if (active) ++it;
+        // who leaves: at the cap without a look, else when H x_hat = 0, x_hat = (marg < 0); a slot's verdict is the ballot under its mask
+        const bool look = active && it < a.cap && !a.no_early;
+        bool bad = false;
+        unsigned long long open = __ballot(look);  // lanes of slots not yet known to hold an unsatisfied check
+        for (int l = 0; l < mb && open != 0ull; ++l) {
+            const int deg = tab[4 * l];
+            const qc_tab_t e = tab + tab[4 * l + 1];
+            uint32_t par = 0;
+            if (look && !bad)
+                for (int j = 0; j < deg; ++j) par ^= (uint32_t)(marg[qc_var(r, Z, e[2 * j], e[2 * j + 1])] < 0);
+            bad = bad || (__ballot(par != 0u) & mine) != 0ull;
+            open = __ballot(look && !bad);
+        }
+        need = active && (it >= a.cap || (look && !bad));
+    }
+}
+
+template <typename T>
+const void* pack_kernel_of(bool row8) {
+    return row8 ? (const void*)k_qc_pack<T, true> : (const void*)k_qc_pack<T, false>;
+}
+
 // the table of a processing order (host side) and its upload
 int install(Qc* h, const std::vector<int32_t>& order) {
     const Code* c = h->code;
@@ -372,6 +533,7 @@ int qc_create(Code* code, int32_t Z, Qc** out) {
         if (v == 1 || v == 2 || v == 4 || v == 8) h->nw = v;
     }
     h->frames_per_cu = (int)std::min<int64_t>(fit, 32 / h->nw);
+    if (const char* env = std::getenv("LDPC_QC_PACK_GRID")) h->pack_grid = std::max(std::atoi(env), 0);  // the tests put chosen frames into one wave's slots
     hipDeviceProp_t prop;
     if (e == hipSuccess) e = hipGetDeviceProperties(&prop, code->device);
     if (e == hipSuccess && need > 64 * 1024) {  // above 64 KiB a workgroup's LDS has to be asked for
@@ -464,8 +626,42 @@ void qc_get_order(const Qc* h, int32_t* mb, int32_t* order) {
     if (order) std::copy(h->order.begin(), h->order.end(), order);
 }
 
+// workgroups of k_qc_pack one CU holds at P frames per wave
+static int pack_groups_per_cu(const Qc* h, int P) { return (int)std::min<int64_t>(LQMSA_LDS_BYTES / (P * qc_pack_stride(h->lds_bytes, h->Z)), 32); }
+
+int qcpack_set(Qc* h, int32_t P) {
+    const int64_t stride = qc_pack_stride(h->lds_bytes, h->Z);
+    if (P == 0) P = qc_pack(h->Z, h->lds_bytes);
+    if (P < 1 || (P >= 2 && ((int64_t)P * h->Z > 64 || P * stride > LQMSA_LDS_BYTES))) {
+        set_error("ldpc_qcpack_set: %d frames per wave at Z = %d with %lld bytes from frame to frame (%lld per frame): the frames of a wave take "
+                  "P Z <= 64 lanes and P times those bytes <= %lld of LDS; 0 takes the rule's %d, 1 is one frame per workgroup",
+                  P, h->Z, (long long)stride, (long long)h->lds_bytes, (long long)LQMSA_LDS_BYTES, qc_pack(h->Z, h->lds_bytes));
+        return LDPC_E_ARG;
+    }
+    if (P >= 2 && P * stride > 64 * 1024) {  // above 64 KiB a workgroup's LDS has to be asked for
+        const bool row8 = h->row_bytes == 8;
+        LDPC_HIP_TRY(hipSetDevice(h->code->device));
+        LDPC_HIP_TRY(hipFuncSetAttribute(pack_kernel_of<float>(row8), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LQMSA_LDS_BYTES));
+        LDPC_HIP_TRY(hipFuncSetAttribute(pack_kernel_of<double>(row8), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LQMSA_LDS_BYTES));
+    }
+    h->pack = P;
+    return LDPC_OK;
+}
+
+void qcpack_get(const Qc* h, int32_t* frames_per_wave, int32_t* rule_pick) {
+    *frames_per_wave = h->pack;
+    *rule_pick = qc_pack(h->Z, h->lds_bytes);
+}
+
 void qc_info(const Qc* h, double* out4) {
     out4[0] = (double)h->lds_bytes;
+    if (h->pack >= 2) {
+        const int per_cu = pack_groups_per_cu(h, h->pack);
+        out4[1] = 1;
+        out4[2] = (double)h->pack * per_cu;
+        out4[3] = (double)h->num_cu * per_cu;
+        return;
+    }
     out4[1] = h->nw;
     out4[2] = h->frames_per_cu;
     out4[3] = (double)h->num_cu * h->frames_per_cu;
@@ -510,6 +706,18 @@ int qc_decode(Qc* h, int dtype, const void* priors, const uint8_t* y0, int64_t B
     a.iters = iters;
     a.soft = soft;
     LDPC_HIP_TRY(hipMemsetAsync(a.dispenser, 0, 4, st));
+    if (h->pack >= 2) {
+        QcPackArgs pa;
+        pa.a = a;
+        pa.P = h->pack;
+        pa.stride = (int32_t)qc_pack_stride(h->lds_bytes, h->Z);
+        int64_t groups = std::min<int64_t>((B + pa.P - 1) / pa.P, (int64_t)h->num_cu * pack_groups_per_cu(h, pa.P));
+        if (h->pack_grid > 0) groups = std::min<int64_t>(groups, h->pack_grid);
+        const void* kern = dtype == DT_F64 ? pack_kernel_of<double>(h->row_bytes == 8) : pack_kernel_of<float>(h->row_bytes == 8);
+        void* args[] = {(void*)&pa};
+        LDPC_HIP_TRY(hipLaunchKernel(kern, dim3((unsigned)groups), dim3(64u), args, (size_t)pa.P * (size_t)pa.stride, st));
+        return LDPC_OK;
+    }
     const unsigned groups = (unsigned)std::min<int64_t>(B, (int64_t)h->num_cu * h->frames_per_cu);
     const void* kern = dtype == DT_F64 ? kernel_of<double>(h->nw, h->row_bytes == 8) : kernel_of<float>(h->nw, h->row_bytes == 8);
     void* args[] = {(void*)&a};

@@ -43,9 +43,13 @@ def test(args, comm=None):
     code = codes.get_code(args.code)
     if row.quasi_cyclic:  # (the result file carries the lifting size the decoder runs with, not the 0 that asks for it)
         try:
-            args.qc_lift = qc.resolve(code, args.qc_lift)[1]
+            base, args.qc_lift = qc.resolve(code, args.qc_lift)
         except ValueError as e:
             raise SystemExit("QCMSA: %s (LQMSA decodes any code)" % e)
+        try:
+            qc.check_pack(getattr(args, "qc_pack", 0), args.qc_lift, qc.frame_bytes(code, base))
+        except ValueError as e:
+            raise SystemExit("--qc-pack: %s" % e)
     id_keys = ["channel", "code", "decoder", "codeword", "min_wec"] + dec_fac.id_keys
     id_val = [vars(args)[key] for key in id_keys]
     log = logging.getLogger(".".join(utils.strl(id_val)))

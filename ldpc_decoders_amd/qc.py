@@ -4,8 +4,8 @@ unstructured ensembles only, src/codes.py:108-120).
 H is an ``mb x nb`` array of ``Z x Z`` blocks given by a base matrix of shifts: ``-1`` is a zero block, ``0 <= s < Z`` a cyclically
 shifted identity with a one at ``(i Z + r, j Z + (r + s) mod Z)``.  ``expand`` builds the code, ``find_structure`` finds the base again from
 any H (so a code travels in the ordinary parity text format), ``rand_qc_ldpc`` draws shifts on a mask, and ``QCMSA`` decodes with every
-block row one layer: ``layered.LQMSA``'s integer contract, bit for bit, on a kernel that needs no index tables.  The contract is the
-``ldpc_qc_*`` block of include/ldpc_hip.h.
+block row one layer: ``layered.LQMSA``'s integer contract, bit for bit, on a kernel that needs no index tables; for lifting sizes up to 32
+several frames share a wave (``qc_pack``).  The contract is the ``ldpc_qc_*`` block of include/ldpc_hip.h.
 
     python -m ldpc_decoders_amd.qc <count> <mb> <nb> <Z> [--dv 3] [--seed S] [--dir D]
 
@@ -171,6 +171,31 @@ def qc_waves(frames_per_cu, Z):
     return min(layered.lqmsa_waves(frames_per_cu), cap)
 
 
+def qc_pack_stride(lds_bytes_per_frame, Z):
+    """Bytes from one frame slot's image to the next (csrc/ldpc_qc.hpp qc_pack_stride): the smallest multiple of 16 that is >= the frame's
+    bytes and congruent to 2 Z rounded up to 16 modulo 128."""
+    want, s = (2 * Z + 15) // 16 * 16 % 128, (lds_bytes_per_frame + 15) // 16 * 16
+    return s + (want - s % 128) % 128
+
+
+def qc_pack(Z, lds_bytes_per_frame):
+    """Frames per wave (csrc/ldpc_qc.hpp qc_pack): 1 above Z = 32, else as many as the 64 lanes and one CU's LDS take."""
+    if Z > 32:
+        return 1
+    return max(min(64 // Z, layered.LDS_BYTES // qc_pack_stride(lds_bytes_per_frame, Z)), 1)
+
+
+def check_pack(P, Z, lds_bytes_per_frame):
+    """What ``ldpc_qcpack_set`` accepts: 0 (the rule), 1, or P >= 2 frames whose rows fit the wave and whose images fit the LDS.  -> int"""
+    if int(P) != P or P < 0:
+        raise ValueError("qc_pack is 0 (the rule's pick), 1 or a number of frames per wave >= 2 (got %r)" % (P,))
+    stride = qc_pack_stride(lds_bytes_per_frame, Z)
+    if P >= 2 and (P * Z > 64 or P * stride > layered.LDS_BYTES):
+        raise ValueError("QCMSA: %d frames per wave at Z = %d with %d bytes from frame to frame: P Z <= 64 lanes and P times those bytes <= %d of LDS are "
+                         "needed (the rule picks %d)" % (P, Z, stride, layered.LDS_BYTES, qc_pack(Z, lds_bytes_per_frame)))
+    return int(P)
+
+
 def check_order(mb, order):
     """What ``ldpc_qc_set_order`` accepts: a permutation of 0 .. mb - 1.  -> int32 array"""
     o = np.asarray(order)
@@ -186,6 +211,11 @@ def layers_of(Z, order):
     return np.repeat(pos, Z)
 
 
+def frame_bytes(code, base):
+    """LDS bytes of one frame: ``layered.lqmsa_lds_bytes`` with the largest block-row degree."""
+    return layered.lqmsa_lds_bytes(code.m, code.n, code.E, int((np.asarray(base) >= 0).sum(axis=1).max()))
+
+
 def check_code(code, base, Z):
     """ValueError unless ``ldpc_qc_create`` takes the code (checked before the library is loaded)."""
     deg = (np.asarray(base) >= 0).sum(axis=1)
@@ -194,7 +224,7 @@ def check_code(code, base, Z):
         raise ValueError("layered min-sum needs every check to have at least two variables (a block row of degree %d)" % deg.min())
     if dv.max() > layered.MAX_DV:
         raise ValueError("QCMSA: a variable of degree %d: the int16 marginals hold degrees up to %d" % (dv.max(), layered.MAX_DV))
-    need = layered.lqmsa_lds_bytes(code.m, code.n, code.E, int(deg.max()))
+    need = frame_bytes(code, base)
     if need > layered.LDS_BYTES:
         raise ValueError("QCMSA: a frame of a %d x %d code (largest block-row degree %d) needs %d bytes of LDS, above one CU's %d; "
                          "use LMSA (layered min-sum on the streaming kernels) for it" % (code.m, code.n, deg.max(), need, layered.LDS_BYTES))
@@ -212,10 +242,11 @@ def resolve(code, qc_lift=0):
 class QCMSA:
     """Layered fixed-point min-sum on a quasi-cyclic code: ``layered.LQMSA``'s rule and parameters with the block rows of the base matrix
     as layers, processed in ``qc_order`` (a permutation of the block rows; None: natural order).  ``qc_lift``: the lifting size Z (0:
-    ``code.qc``, else detected).  ``decode`` / ``decode_batch`` / ``last_iters`` as ``layered.LQMSA``."""
+    ``code.qc``, else detected).  ``qc_pack``: frames per wave for Z <= 32 (0: the rule ``qc_pack``; 1: one frame per workgroup); it changes
+    the speed and no result, so it is no id key.  ``decode`` / ``decode_batch`` / ``last_iters`` as ``layered.LQMSA``."""
     id_keys = layered.LQMSA.id_keys + ["qc_lift"]
 
-    def __init__(self, parity_mtx, max_iter=10, msa_bits=6, msa_frac_bits=2, msa_scale=0.8125, msa_offset=0, qc_lift=0, qc_order=None, **_):
+    def __init__(self, parity_mtx, max_iter=10, msa_bits=6, msa_frac_bits=2, msa_scale=0.8125, msa_offset=0, qc_lift=0, qc_order=None, qc_pack=0, **_):
         given = (msa_bits, msa_frac_bits, msa_scale, msa_offset)
         values = [d if v is None else v for v, d in zip(given, (6, 2, 0.8125, 0))]
         # (everything is checked before the decoder is created: a bad value never reaches the device)
@@ -228,8 +259,10 @@ class QCMSA:
         if qc_order is not None:
             qc_order = check_order(self.base.shape[0], qc_order)
         check_code(self.code, self.base, self.qc_lift)
+        self.qc_pack = check_pack(qc_pack or 0, self.qc_lift, frame_bytes(self.code, self.base))
         self.precision = "f64" if _.get("precision") == "f64" else "f32"  # the type the priors are quantised in
-        self.handle = QcHandle(self.code, self.qc_lift, _.get("device"), self.msa_bits, self.msa_frac_bits, self.msa_scale, self.msa_offset)
+        self.handle = QcHandle(self.code, self.qc_lift, _.get("device"), self.msa_bits, self.msa_frac_bits, self.msa_scale, self.msa_offset,
+                               self.qc_pack)
         if qc_order is not None:
             self.handle.set_order(qc_order)
         self.last_iters = None

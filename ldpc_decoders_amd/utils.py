@@ -86,6 +86,9 @@ def setup_parser(code_names, channel_names, decoder_names):
     g.add_argument("--qc-lift", type=int, default=0, metavar="Z",
                    help="QCMSA (layered fixed-point min-sum on a quasi-cyclic code, parameters of LQMSA): the lifting size, H is an array of Z x Z blocks "
                         "that are zero or cyclically shifted identities; 0 = the largest Z for which that holds")
+    g.add_argument("--qc-pack", type=int, default=0, metavar="P",
+                   help="QCMSA: frames per wave for lifting sizes up to 32 (P Z <= 64); 0 = as many as the lanes and the LDS take, 1 = one frame "
+                        "per workgroup; changes the speed, no result")
     g.add_argument("--osd-depth", type=int, default=64, metavar="N", help="OSD order 1: how many single flips are tried (N >= 0)")
     return bind_parser_common(p)
 
