@@ -11,21 +11,22 @@
 // LDS queue and emits no cross-wave wait).
 // Graph tables, per layering, in global memory (Lqmsa::lay / vtab / deg, rebuilt by lqmsa_set_layers): a layer of c checks is cut into
 // ceil(c / 64) wave passes; pass k of the layer goes to wave k mod NW; vtab holds the 16-bit variable indices as [pass][edge][64 lanes].
+// The rule itself, a frame's way into and out of the LDS, the frame hand-out and the host-side parameters and refusals are stated in
+// ldpc_layered_fx.hpp for this decoder, QCMSA and SLQMSA; this file adds the tables and the walk over them.
 #include <algorithm>
-#include <cmath>
 #include <cstdlib>
 #include <cstring>
 #include <new>
 
 #include "ldpc_cn.hpp"
+#include "ldpc_layered_fx.hpp"
 #include "ldpc_lqmsa.hpp"
 
 namespace ldpc {
 
 struct Lqmsa {
     Code* code = nullptr;
-    int bits = 6, frac = 2, offset = 0;
-    double scale = 0.8125;
+    FixedPoint fx;
     bool odd_check = false;
     int num_cu = 0, nw = 1, frames_per_cu = 0, row_bytes = 8;
     int64_t lds_bytes = 0;
@@ -35,7 +36,7 @@ struct Lqmsa {
     DevBuf vtab;  // uint16 [wave passes][dc_max][64]: variable of edge j of the check in lane L of the pass
     DevBuf deg;   // uint16 [m]: degree of the check at each position of the processing order
     DevBuf ctl;   // the frame dispenser
-    DevBuf sim_pri, sim_y, sim_bits, sim_iters;  // staging of ldpc_lqmsa_simulate
+    SimStage sim;  // staging of ldpc_lqmsa_simulate
 };
 
 namespace {
@@ -57,78 +58,6 @@ struct LqArgs {
     int16_t* soft;
 };
 
-// |c2v| a minimum m <= V sends
-__device__ __forceinline__ int lq_mag(int m, int scale64, int offset) {
-    const int t = ((scale64 * m) >> 6) - offset;
-    return t > 0 ? t : 0;
-}
-
-// One check: the row of messages of position p, its `deg` variables in vt[j * 64].  ROW8: the row is 8 bytes, held in registers.
-template <bool ROW8>
-__device__ __forceinline__ void lq_check(int16_t* __restrict__ marg, uint8_t* __restrict__ c2v, int p, int deg, const uint16_t* __restrict__ vt, int row_bytes,
-                                         int scale64, int offset, int V) {
-    int min1 = V, min2 = V, arg = -1;  // |v| enters as min(|v|, V), so V is the neutral element
-    uint32_t par = 0;
-    if constexpr (ROW8) {
-        uint2* rowp = (uint2*)(c2v + (size_t)p * 8);
-        const uint2 row = *rowp;
-        const uint32_t rw[2] = {row.x, row.y};
-        int v[8];
-        uint32_t vi[8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            if (j < deg) {
-                vi[j] = vt[j * 64];
-                v[j] = (int)marg[vi[j]] - (int)(int8_t)(rw[j >> 2] >> (8 * (j & 3)));
-                const int a = min(abs(v[j]), V);
-                par ^= (uint32_t)(v[j] < 0);
-                if (a < min1) {
-                    min2 = min1;
-                    min1 = a;
-                    arg = j;
-                } else if (a < min2) {
-                    min2 = a;
-                }
-            }
-        }
-        const int f1 = lq_mag(min1, scale64, offset), f2 = lq_mag(min2, scale64, offset);
-        uint32_t out[2] = {0u, 0u};
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            if (j < deg) {
-                const int mag = j == arg ? f2 : f1;
-                const int c = (par ^ (uint32_t)(v[j] < 0)) ? -mag : mag;
-                marg[vi[j]] = (int16_t)(v[j] + c);
-                out[j >> 2] |= (uint32_t)(uint8_t)(int8_t)c << (8 * (j & 3));
-            }
-        }
-        *rowp = make_uint2(out[0], out[1]);
-    } else {
-        uint8_t* row = c2v + (size_t)p * row_bytes;
-        for (int j = 0; j < deg; ++j) {
-            const int v = (int)marg[vt[j * 64]] - (int)(int8_t)row[j];
-            const int a = min(abs(v), V);
-            par ^= (uint32_t)(v < 0);
-            if (a < min1) {
-                min2 = min1;
-                min1 = a;
-                arg = j;
-            } else if (a < min2) {
-                min2 = a;
-            }
-        }
-        const int f1 = lq_mag(min1, scale64, offset), f2 = lq_mag(min2, scale64, offset);
-        for (int j = 0; j < deg; ++j) {
-            const uint32_t vi = vt[j * 64];
-            const int v = (int)marg[vi] - (int)(int8_t)row[j];
-            const int mag = j == arg ? f2 : f1;
-            const int c = (par ^ (uint32_t)(v < 0)) ? -mag : mag;
-            marg[vi] = (int16_t)(v + c);
-            row[j] = (uint8_t)(int8_t)c;
-        }
-    }
-}
-
 template <typename T, int NW, bool ROW8>
 __global__ __launch_bounds__(64 * NW) void k_lqmsa(const LqArgs a) {
     extern __shared__ __attribute__((aligned(16))) uint32_t lq_sm[];
@@ -144,19 +73,9 @@ __global__ __launch_bounds__(64 * NW) void k_lqmsa(const LqArgs a) {
     const int32_t* __restrict__ lay = a.lay;
     const uint16_t* __restrict__ deg = a.deg;
     for (;;) {
-        __syncthreads();  // the frame before is written out
-        if (tid == 0) {
-            ctl[0] = atomicAdd(a.dispenser, 1u);
-            ctl[1] = 0u;
-            ctl[2] = 0u;
-        }
-        __syncthreads();
-        const int64_t f = ctl[0];
+        const int64_t f = fx_draw_frame(a.dispenser, ctl, tid);
         if (f >= a.B) break;
-        const T* __restrict__ pr = (const T*)a.priors + (size_t)f * n;
-        for (int v = tid; v < n; v += NT) marg[v] = (int16_t)(int)quantise_prior<T>(pr[v], step, vmax);
-        uint32_t* cw = (uint32_t*)c2v;
-        for (int i = tid; i < m * (a.row_bytes / 4); i += NT) cw[i] = 0u;
+        fx_load_frame<NT, T>((const T*)a.priors + (size_t)f * n, step, vmax, marg, (uint32_t*)c2v, n, m * (a.row_bytes / 4), tid);
         __syncthreads();
         const uint8_t* __restrict__ yf = a.y0 ? a.y0 + (size_t)f * n : nullptr;
         int it = 0;
@@ -182,24 +101,27 @@ __global__ __launch_bounds__(64 * NW) void k_lqmsa(const LqArgs a) {
                         bad = __ballot(par != 0u) != 0ull;  // wave-uniform
                     }
                 }
-                if (bad && lane == 0) ctl[1 + (it & 1)] = 1u;
-                __syncthreads();
-                const bool any = ctl[1 + (it & 1)] != 0u;
-                if (tid == 0) ctl[1 + ((it + 1) & 1)] = 0u;  // last read a sweep ago, next written a sweep (and a layer barrier) from now
-                if (!any) break;
+                if (!fx_any_unsatisfied(ctl, bad, it, tid, lane)) break;
             }
             for (int l = 0; l < a.nlayers; ++l) {
                 const int s0 = lay[2 * l], q0 = lay[2 * l + 1], s1 = lay[2 * l + 2];
                 const int np = (s1 - s0 + 63) >> 6;
                 for (int k = w; k < np; k += NW) {
                     const int p = s0 + k * 64 + lane;
-                    if (p < s1)
-                        lq_check<ROW8>(marg, c2v, p, deg[p], a.vtab + ((size_t)(q0 + k) * a.dc_max) * 64 + lane, a.row_bytes, a.scale64, a.offset, a.vmax);
+                    if (p < s1) {  // the check at position p: its row of messages, its deg[p] variables in vt[j * 64]
+                        const uint16_t* __restrict__ vt = a.vtab + ((size_t)(q0 + k) * a.dc_max) * 64 + lane;
+                        const auto var = [vt](int j) -> uint32_t { return vt[j * 64]; };
+                        if constexpr (ROW8)
+                            fx_check_row8<8>(marg, (uint2*)(c2v + (size_t)p * 8), deg[p], var, a.scale64, a.offset, a.vmax);
+                        else
+                            fx_check_loop(marg, c2v + (size_t)p * a.row_bytes, deg[p], var, a.scale64, a.offset, a.vmax);
+                    }
                 }
                 __syncthreads();
             }
         }
-        // it == 0: the frame left at the check of the received word and keeps it (cap >= 1, so y0 was given)
+        // the frame leaves (ldpc_layered_fx.hpp fx_write_frame, kept inline here: see there).  it == 0: it left at the check of the received
+        // word and keeps it (cap >= 1, so y0 was given)
         if (tid == 0) a.iters[f] = it;
         if (a.xhat)
             for (int v = tid; v < n; v += NT) a.xhat[(size_t)f * n + v] = it == 0 ? yf[v] : (uint8_t)(marg[v] < 0);
@@ -277,14 +199,7 @@ int install(Lqmsa* h, const int32_t* layer_of_check) {
 }  // namespace
 
 int lqmsa_create(Code* code, Lqmsa** out) {
-    if (code->min_dc < 2) {
-        set_error("ldpc_lqmsa_create: a check of degree %d: layered min-sum needs every check to have degree >= 2", code->min_dc);
-        return LDPC_E_UNSUPPORTED;
-    }
-    if (code->max_dv > LQMSA_MAX_DV) {
-        set_error("ldpc_lqmsa_create: a variable of degree %d: the int16 marginals hold V (1 + dv) for dv <= %d", code->max_dv, LQMSA_MAX_DV);
-        return LDPC_E_UNSUPPORTED;
-    }
+    LDPC_TRY(fx_check_degrees("ldpc_lqmsa_create", "check", code->min_dc, code->max_dv, LQMSA_MAX_DV));
     const int64_t need = lqmsa_lds_bytes(code->m, code->n, code->E, code->max_dc);
     if (need > LQMSA_LDS_BYTES || code->n > 65536) {
         set_error("ldpc_lqmsa_create: one frame of this code (m = %d, n = %d, dc_max = %d) needs %lld bytes of LDS, above one CU's %lld (and n <= 65536 "
@@ -297,21 +212,13 @@ int lqmsa_create(Code* code, Lqmsa** out) {
     h->code = code;
     h->lds_bytes = need;
     h->row_bytes = lqmsa_row_bytes(code->max_dc);
-    for (int32_t c = 0; c < code->m; ++c) h->odd_check |= ((code->row_ptr[c + 1] - code->row_ptr[c]) & 1) != 0;
+    h->odd_check = fx_odd_check(code);
     const int64_t fit = LQMSA_LDS_BYTES / need;
-    h->nw = lqmsa_waves(fit);
-    if (const char* env = std::getenv("LDPC_LQMSA_NW")) {  // the tests reach every wave count with it
-        const int v = std::atoi(env);
-        if (v == 1 || v == 2 || v == 4 || v == 8) h->nw = v;
-    }
-    h->frames_per_cu = (int)std::min<int64_t>(fit, 32 / h->nw);
+    h->nw = fx_waves(lqmsa_waves(fit), "LDPC_LQMSA_NW");
+    h->frames_per_cu = fx_frames_per_cu(fit, h->nw);
     hipDeviceProp_t prop;
     hipError_t e = hipGetDeviceProperties(&prop, code->device);
-    if (e == hipSuccess && need > 64 * 1024) {  // above 64 KiB a workgroup's LDS has to be asked for
-        const bool row8 = h->row_bytes == 8;
-        e = hipFuncSetAttribute(kernel_of<float>(h->nw, row8), hipFuncAttributeMaxDynamicSharedMemorySize, (int)need);
-        if (e == hipSuccess) e = hipFuncSetAttribute(kernel_of<double>(h->nw, row8), hipFuncAttributeMaxDynamicSharedMemorySize, (int)need);
-    }
+    if (e == hipSuccess) e = fx_allow_lds(kernel_of<float>(h->nw, h->row_bytes == 8), kernel_of<double>(h->nw, h->row_bytes == 8), need);
     if (e != hipSuccess) {
         set_error("ldpc_lqmsa_create: device setup failed: %s", hipGetErrorString(e));
         lqmsa_destroy(h);
@@ -330,31 +237,16 @@ int lqmsa_create(Code* code, Lqmsa** out) {
 
 void lqmsa_destroy(Lqmsa* h) {
     if (!h) return;
-    for (DevBuf* b : {&h->lay, &h->vtab, &h->deg, &h->ctl, &h->sim_pri, &h->sim_y, &h->sim_bits, &h->sim_iters}) b->release();
+    for (DevBuf* b : {&h->lay, &h->vtab, &h->deg, &h->ctl}) b->release();
+    h->sim.release();
     delete h;
 }
 
 int lqmsa_set_fixed_point(Lqmsa* h, int bits, int frac_bits, double scale, int offset) {
-    // (written so that a NaN scale fails; 64 * scale is exact, so the grid test is)
-    if (bits < 2 || bits > 8 || frac_bits < -8 || frac_bits > 8 || !(scale > 0.0 && scale <= 1.0) || 64.0 * scale != (double)(long long)(64.0 * scale) ||
-        offset < 0) {
-        set_error("ldpc_lqmsa_set_fixed_point: 2 <= bits <= 8, -8 <= frac_bits <= 8, scale a multiple of 1/64 in (0, 1] and offset >= 0 are needed "
-                  "(bits=%d frac_bits=%d scale=%g offset=%d)", bits, frac_bits, scale, offset);
-        return LDPC_E_ARG;
-    }
-    h->bits = bits;
-    h->frac = frac_bits;
-    h->scale = scale;
-    h->offset = offset;
-    return LDPC_OK;
+    return h->fx.set("ldpc_lqmsa_set_fixed_point", bits, frac_bits, scale, offset);
 }
 
-void lqmsa_get_fixed_point(const Lqmsa* h, int* bits, int* frac_bits, double* scale, int* offset) {
-    *bits = h->bits;
-    *frac_bits = h->frac;
-    *scale = h->scale;
-    *offset = h->offset;
-}
+void lqmsa_get_fixed_point(const Lqmsa* h, int* bits, int* frac_bits, double* scale, int* offset) { h->fx.get(bits, frac_bits, scale, offset); }
 
 int lqmsa_set_layers(Lqmsa* h, const int32_t* layer_of_check, int32_t m) {
     if (layer_of_check && m != h->code->m) {
@@ -378,44 +270,17 @@ void lqmsa_info(const Lqmsa* h, double* out4) {
 
 int lqmsa_decode(Lqmsa* h, int dtype, const void* priors, const uint8_t* y0, int64_t B, int32_t max_iter, uint32_t flags, uint8_t* xhat,
                  uint32_t* bits, int32_t* iters, int16_t* soft, hipStream_t st) {
-    if (dtype != DT_F32 && dtype != DT_F64) {
-        set_error("ldpc_lqmsa_decode: the priors are LDPC_DTYPE_F32 or LDPC_DTYPE_F64 (got %d)", dtype);
-        return LDPC_E_ARG;
-    }
-    if (flags & ~FLAG_NO_EARLY_EXIT) {
-        set_error("ldpc_lqmsa_decode: the only flag is LDPC_FLAG_NO_EARLY_EXIT (got 0x%x)", flags);
-        return LDPC_E_UNSUPPORTED;
-    }
-    if (B > (int64_t)1 << 31) {
-        set_error("ldpc_lqmsa_decode: at most 2^31 frames per call (got %lld)", (long long)B);
-        return LDPC_E_ARG;
-    }
+    LDPC_TRY(fx_check_decode("ldpc_lqmsa_decode", dtype, flags, B));
     const Code* c = h->code;
     LDPC_HIP_TRY(hipSetDevice(c->device));
     if (B == 0) return LDPC_OK;
     LqArgs a;
-    a.priors = priors;
-    a.y0 = y0;
-    a.B = B;
-    a.n = c->n;
-    a.m = c->m;
-    a.row_bytes = h->row_bytes;
+    fx_fill_args(a, c, h->fx, h->row_bytes, h->ctl.p, priors, y0, B, max_iter, flags, xhat, bits, iters, soft);
     a.dc_max = c->max_dc;
     a.nlayers = (int32_t)h->layer_start.size() - 1;
-    a.cap = max_iter > 0 ? max_iter : 100000;
-    a.no_early = (flags & FLAG_NO_EARLY_EXIT) ? 1 : 0;
-    a.scale64 = (int32_t)(64.0 * h->scale);
-    a.offset = std::min(h->offset, 1 << 20);  // beyond V every message is 0 already
-    a.vmax = (1 << (h->bits - 1)) - 1;
-    a.step = std::ldexp(1.0, h->frac);
     a.lay = (const int32_t*)h->lay.p;
     a.vtab = (const uint16_t*)h->vtab.p;
     a.deg = (const uint16_t*)h->deg.p;
-    a.dispenser = (uint32_t*)h->ctl.p;
-    a.xhat = xhat;
-    a.bits = bits;
-    a.iters = iters;
-    a.soft = soft;
     LDPC_HIP_TRY(hipMemsetAsync(a.dispenser, 0, 4, st));
     const unsigned groups = (unsigned)std::min<int64_t>(B, (int64_t)h->num_cu * h->frames_per_cu);
     const void* kern = dtype == DT_F64 ? kernel_of<double>(h->nw, h->row_bytes == 8) : kernel_of<float>(h->nw, h->row_bytes == 8);
@@ -426,36 +291,10 @@ int lqmsa_decode(Lqmsa* h, int dtype, const void* priors, const uint8_t* y0, int
 
 int lqmsa_simulate(Lqmsa* h, int channel, double param, int codeword, uint64_t seed, uint64_t stream_id, uint64_t frame0, int64_t B, int32_t max_iter,
                    uint32_t flags, int32_t hist_bins, int64_t* counters, hipStream_t st) {
-    if (channel != CH_BIAWGN && channel != CH_BSC) {
-        set_error("ldpc_lqmsa_simulate: LDPC_CH_BIAWGN or LDPC_CH_BSC (min-sum has no magnitudes to work on over the erasure channel)");
-        return LDPC_E_ARG;
-    }
-    if (codeword != 0 && codeword != 1) {
-        set_error("ldpc_lqmsa_simulate: codeword must be 0 or 1");
-        return LDPC_E_ARG;
-    }
-    if (codeword == 1 && h->odd_check) {
-        set_error("ldpc_lqmsa_simulate: codeword 1: the all-ones word is no codeword of this code (a check has odd degree)");
-        return LDPC_E_ARG;
-    }
-    const size_t n = (size_t)h->code->n, W = (n + 31) / 32;
-    // the priors of one pass: about 256 MiB, at most 2^17 frames
-    int64_t cap = std::min<int64_t>(std::max<int64_t>((int64_t)(((size_t)256 << 20) / (n * sizeof(float))), 1), (int64_t)1 << 17);
-    cap = std::min(cap, std::max<int64_t>(B, 1));
-    LDPC_HIP_TRY(hipSetDevice(h->code->device));
-    LDPC_TRY(h->sim_pri.reserve((size_t)cap * n * sizeof(float)));
-    if (channel == CH_BSC) LDPC_TRY(h->sim_y.reserve((size_t)cap * n));
-    LDPC_TRY(h->sim_bits.reserve((size_t)cap * W * 4));
-    LDPC_TRY(h->sim_iters.reserve((size_t)cap * sizeof(int32_t)));
-    uint8_t* y = channel == CH_BSC ? (uint8_t*)h->sim_y.p : nullptr;  // over the BSC the received word takes the iteration-0 check, as upstream
-    for (int64_t b0 = 0; b0 < B; b0 += cap) {
-        const int64_t nb = std::min(cap, B - b0);
-        LDPC_TRY(channel_generate(channel, DT_F32, param, codeword, seed, stream_id, frame0 + (uint64_t)b0, nb, (int32_t)n, h->sim_pri.p, y, st));
-        LDPC_TRY(lqmsa_decode(h, DT_F32, h->sim_pri.p, y, nb, max_iter, flags, nullptr, (uint32_t*)h->sim_bits.p, (int32_t*)h->sim_iters.p, nullptr, st));
-        LDPC_TRY(count_errors_bits((const uint32_t*)h->sim_bits.p, nullptr, nullptr, codeword, (const int32_t*)h->sim_iters.p, nb, (int32_t)n, hist_bins,
-                                   counters, st));
-    }
-    return LDPC_OK;
+    return fx_simulate("ldpc_lqmsa_simulate", h->code, h->odd_check, h->sim, fx_lds_sim_cap(h->code->n), channel, param, codeword, seed, stream_id, frame0, B,
+                       hist_bins, counters, st, [&](const void* pri, const uint8_t* y, int64_t nb, uint32_t* bits, int32_t* iters) {
+                           return lqmsa_decode(h, DT_F32, pri, y, nb, max_iter, flags, nullptr, bits, iters, nullptr, st);
+                       });
 }
 
 }  // namespace ldpc

@@ -2,8 +2,9 @@
 //
 // H is an mb x nb array of Z x Z blocks, each zero or a cyclically shifted identity: check i Z + r meets, in block column j, variable
 // j Z + (r + s_ij) mod Z.  A block row is a layer (its Z checks touch disjoint variables), its degree is the same for all its checks, and a
-// lane's variable index is its row r plus two wave-uniform scalars: there is no index table and no degree table.  The arithmetic is
-// LQMSA's (ldpc_lqmsa.hip), so are the LDS layout (lqmsa_lds_bytes with dc_max = the largest block-row degree) and the frame hand-out:
+// lane's variable index is its row r plus two wave-uniform scalars: there is no index table and no degree table.  The arithmetic, a frame's
+// way in and out and the frame hand-out are those of ldpc_layered_fx.hpp, shared with LQMSA; so is LQMSA's LDS layout (lqmsa_lds_bytes with
+// dc_max = the largest block-row degree):
 //     marg  int16 [n]            the marginals in levels
 //     c2v   int8  [m][row bytes] the check -> variable messages, the row of check c at c, byte j for the block row's j-th nonzero block
 //     ctl   4 words              frame index, two syndrome flags used by alternate sweeps, spare
@@ -13,13 +14,13 @@
 // Table (Qc::tab, rebuilt by qc_set_order), in global memory in processing order and read with wave-uniform addresses through the constant
 // address space, so every entry arrives by a scalar load: per block row {degree, offset of its edges, i Z, 0}, per edge {j Z, shift}.
 #include <algorithm>
-#include <cmath>
 #include <cstdlib>
 #include <cstring>
 #include <new>
 #include <numeric>
 
 #include "ldpc_cn.hpp"
+#include "ldpc_layered_fx.hpp"
 #include "ldpc_qc.hpp"
 
 namespace ldpc {
@@ -27,8 +28,7 @@ namespace ldpc {
 struct Qc {
     Code* code = nullptr;
     int32_t Z = 1, mb = 0, nb = 0, dc_max = 0;
-    int bits = 6, frac = 2, offset = 0;
-    double scale = 0.8125;
+    FixedPoint fx;
     bool odd_check = false;
     int num_cu = 0, nw = 1, frames_per_cu = 0, row_bytes = 8;
     int64_t lds_bytes = 0;
@@ -37,7 +37,7 @@ struct Qc {
     std::vector<int32_t> order;                // block row processed at each position
     DevBuf tab;                                // int32: [mb][4] headers in processing order, then [nonzero blocks][2]
     DevBuf ctl;                                // the frame dispenser
-    DevBuf sim_pri, sim_y, sim_bits, sim_iters;  // staging of ldpc_qc_simulate
+    SimStage sim;                              // staging of ldpc_qc_simulate
 };
 
 namespace {
@@ -59,77 +59,30 @@ struct QcArgs {
     int16_t* soft;
 };
 
-// |c2v| a minimum m <= V sends (LQMSA's rule, step 3 of its contract)
-__device__ __forceinline__ int qc_mag(int m, int scale64, int offset) {
-    const int t = ((scale64 * m) >> 6) - offset;
-    return t > 0 ? t : 0;
-}
-
 // variable of row r in the block {colZ, shift}: e[0] + (r + e[1]) mod Z
 __device__ __forceinline__ int qc_var(int r, int Z, int colZ, int shift) {
     const int t = r + shift;
     return colZ + (t < Z ? t : t - Z);
 }
 
-// One check of a block row of degree D <= 8: its 8-byte row in registers, the D blocks in e[2 j], e[2 j + 1].
-template <int D>
-__device__ __forceinline__ void qc_check8(int16_t* __restrict__ marg, uint2* __restrict__ rowp, int r, int Z, qc_tab_t e, int scale64, int offset, int V) {
-    int min1 = V, min2 = V, arg = -1;  // |v| enters as min(|v|, V), so V is the neutral element
-    uint32_t par = 0;
-    const uint2 row = *rowp;
-    const uint32_t rw[2] = {row.x, row.y};
-    int v[D], vi[D];
-#pragma unroll
-    for (int j = 0; j < D; ++j) {
-        vi[j] = qc_var(r, Z, e[2 * j], e[2 * j + 1]);
-        v[j] = (int)marg[vi[j]] - (int)(int8_t)(rw[j >> 2] >> (8 * (j & 3)));
-        const int a = min(abs(v[j]), V);
-        par ^= (uint32_t)(v[j] < 0);
-        if (a < min1) {
-            min2 = min1;
-            min1 = a;
-            arg = j;
-        } else if (a < min2) {
-            min2 = a;
+// One check of a block row: row r of its Z, the message row `row` of the frame, the `deg` blocks in e[2 j], e[2 j + 1].  deg is wave-uniform: the
+// dispatch is a scalar branch.
+template <bool ROW8>
+__device__ __forceinline__ void qc_check(int16_t* __restrict__ marg, uint8_t* __restrict__ c2v, int row, int r, int Z, int deg, qc_tab_t e, const QcArgs& a) {
+    const auto var = [=](int j) { return qc_var(r, Z, e[2 * j], e[2 * j + 1]); };
+    if constexpr (ROW8) {
+        uint2* rowp = (uint2*)(c2v + (size_t)row * 8);
+        switch (deg) {
+            case 2: fx_check_row8<2>(marg, rowp, 2, var, a.scale64, a.offset, a.vmax); break;
+            case 3: fx_check_row8<3>(marg, rowp, 3, var, a.scale64, a.offset, a.vmax); break;
+            case 4: fx_check_row8<4>(marg, rowp, 4, var, a.scale64, a.offset, a.vmax); break;
+            case 5: fx_check_row8<5>(marg, rowp, 5, var, a.scale64, a.offset, a.vmax); break;
+            case 6: fx_check_row8<6>(marg, rowp, 6, var, a.scale64, a.offset, a.vmax); break;
+            case 7: fx_check_row8<7>(marg, rowp, 7, var, a.scale64, a.offset, a.vmax); break;
+            default: fx_check_row8<8>(marg, rowp, 8, var, a.scale64, a.offset, a.vmax); break;
         }
-    }
-    const int f1 = qc_mag(min1, scale64, offset), f2 = qc_mag(min2, scale64, offset);
-    uint32_t out[2] = {0u, 0u};
-#pragma unroll
-    for (int j = 0; j < D; ++j) {
-        const int mag = j == arg ? f2 : f1;
-        const int c = (par ^ (uint32_t)(v[j] < 0)) ? -mag : mag;
-        marg[vi[j]] = (int16_t)(v[j] + c);
-        out[j >> 2] |= (uint32_t)(uint8_t)(int8_t)c << (8 * (j & 3));
-    }
-    *rowp = make_uint2(out[0], out[1]);
-}
-
-// The loop form, any degree: the row stays in the LDS and is read twice.
-__device__ __forceinline__ void qc_check_loop(int16_t* __restrict__ marg, uint8_t* __restrict__ row, int deg, int r, int Z, qc_tab_t e, int scale64, int offset,
-                                              int V) {
-    int min1 = V, min2 = V, arg = -1;
-    uint32_t par = 0;
-    for (int j = 0; j < deg; ++j) {
-        const int v = (int)marg[qc_var(r, Z, e[2 * j], e[2 * j + 1])] - (int)(int8_t)row[j];
-        const int a = min(abs(v), V);
-        par ^= (uint32_t)(v < 0);
-        if (a < min1) {
-            min2 = min1;
-            min1 = a;
-            arg = j;
-        } else if (a < min2) {
-            min2 = a;
-        }
-    }
-    const int f1 = qc_mag(min1, scale64, offset), f2 = qc_mag(min2, scale64, offset);
-    for (int j = 0; j < deg; ++j) {
-        const int vi = qc_var(r, Z, e[2 * j], e[2 * j + 1]);
-        const int v = (int)marg[vi] - (int)(int8_t)row[j];
-        const int mag = j == arg ? f2 : f1;
-        const int c = (par ^ (uint32_t)(v < 0)) ? -mag : mag;
-        marg[vi] = (int16_t)(v + c);
-        row[j] = (uint8_t)(int8_t)c;
+    } else {
+        fx_check_loop(marg, c2v + (size_t)row * a.row_bytes, deg, var, a.scale64, a.offset, a.vmax);
     }
 }
 
@@ -148,19 +101,9 @@ __global__ __launch_bounds__(64 * NW) void k_qc(const QcArgs a) {
     const T step = (T)a.step, vmax = (T)a.vmax;
     const qc_tab_t tab = (qc_tab_t)a.tab;
     for (;;) {
-        __syncthreads();  // the frame before is written out
-        if (tid == 0) {
-            ctl[0] = atomicAdd(a.dispenser, 1u);
-            ctl[1] = 0u;
-            ctl[2] = 0u;
-        }
-        __syncthreads();
-        const int64_t f = ctl[0];
+        const int64_t f = fx_draw_frame(a.dispenser, ctl, tid);
         if (f >= a.B) break;
-        const T* __restrict__ pr = (const T*)a.priors + (size_t)f * n;
-        for (int v = tid; v < n; v += NT) marg[v] = (int16_t)(int)quantise_prior<T>(pr[v], step, vmax);
-        uint32_t* cw = (uint32_t*)c2v;
-        for (int i = tid; i < m * (a.row_bytes / 4); i += NT) cw[i] = 0u;
+        fx_load_frame<NT, T>((const T*)a.priors + (size_t)f * n, step, vmax, marg, (uint32_t*)c2v, n, m * (a.row_bytes / 4), tid);
         __syncthreads();
         const uint8_t* __restrict__ yf = a.y0 ? a.y0 + (size_t)f * n : nullptr;
         int it = 0;
@@ -183,11 +126,7 @@ __global__ __launch_bounds__(64 * NW) void k_qc(const QcArgs a) {
                         bad = __ballot(par != 0u) != 0ull;  // wave-uniform
                     }
                 }
-                if (bad && lane == 0) ctl[1 + (it & 1)] = 1u;
-                __syncthreads();
-                const bool any = ctl[1 + (it & 1)] != 0u;
-                if (tid == 0) ctl[1 + ((it + 1) & 1)] = 0u;  // last read a sweep ago, next written a sweep (and a layer barrier) from now
-                if (!any) break;
+                if (!fx_any_unsatisfied(ctl, bad, it, tid, lane)) break;
             }
             for (int l = 0; l < mb; ++l) {
                 const int deg = tab[4 * l];  // wave-uniform: the dispatch below is a scalar branch
@@ -195,27 +134,13 @@ __global__ __launch_bounds__(64 * NW) void k_qc(const QcArgs a) {
                 const int row0 = tab[4 * l + 2];
                 for (int k = w; k < np; k += NW) {
                     const int r = k * 64 + lane;
-                    if (r < Z) {
-                        if constexpr (ROW8) {
-                            uint2* rowp = (uint2*)(c2v + (size_t)(row0 + r) * 8);
-                            switch (deg) {
-                                case 2: qc_check8<2>(marg, rowp, r, Z, e, a.scale64, a.offset, a.vmax); break;
-                                case 3: qc_check8<3>(marg, rowp, r, Z, e, a.scale64, a.offset, a.vmax); break;
-                                case 4: qc_check8<4>(marg, rowp, r, Z, e, a.scale64, a.offset, a.vmax); break;
-                                case 5: qc_check8<5>(marg, rowp, r, Z, e, a.scale64, a.offset, a.vmax); break;
-                                case 6: qc_check8<6>(marg, rowp, r, Z, e, a.scale64, a.offset, a.vmax); break;
-                                case 7: qc_check8<7>(marg, rowp, r, Z, e, a.scale64, a.offset, a.vmax); break;
-                                default: qc_check8<8>(marg, rowp, r, Z, e, a.scale64, a.offset, a.vmax); break;
-                            }
-                        } else {
-                            qc_check_loop(marg, c2v + (size_t)(row0 + r) * a.row_bytes, deg, r, Z, e, a.scale64, a.offset, a.vmax);
-                        }
-                    }
+                    if (r < Z) qc_check<ROW8>(marg, c2v, row0 + r, r, Z, deg, e, a);
                 }
                 __syncthreads();
             }
         }
-        // it == 0: the frame left at the check of the received word and keeps it (cap >= 1, so y0 was given)
+        // the frame leaves (ldpc_layered_fx.hpp fx_write_frame, kept inline here: see there).  it == 0: it left at the check of the received
+        // word and keeps it (cap >= 1, so y0 was given)
         if (tid == 0) a.iters[f] = it;
         if (a.xhat)
             for (int v = tid; v < n; v += NT) a.xhat[(size_t)f * n + v] = it == 0 ? yf[v] : (uint8_t)(marg[v] < 0);
@@ -264,28 +189,6 @@ struct QcPackArgs {
 
 constexpr uint32_t QC_NO_FRAME = 0xffffffffu;  // frame indices stay below 2^31
 
-// frame f of sweep count it leaves the image at marg: xhat, iters, soft and the packed words as k_qc writes them (it == 0: the received word)
-__device__ __forceinline__ void qc_pack_write(const QcArgs& a, const int16_t* marg, uint32_t f, int it, int lane) {
-    const int n = a.n, Wd = (n + 31) / 32;
-    const uint8_t* __restrict__ yf = a.y0 ? a.y0 + (size_t)f * n : nullptr;
-    if (lane == 0) a.iters[f] = it;
-    if (a.xhat)
-        for (int v = lane; v < n; v += 64) a.xhat[(size_t)f * n + v] = it == 0 ? yf[v] : (uint8_t)(marg[v] < 0);
-    if (a.soft)
-        for (int v = lane; v < n; v += 64) a.soft[(size_t)f * n + v] = it == 0 ? (int16_t)0 : marg[v];
-    if (a.bits)
-        for (int v0 = 0; v0 < n; v0 += 64) {
-            const int v = v0 + lane;
-            const bool bit = v < n && (it == 0 ? (yf[v] & 1u) != 0u : marg[v] < 0);
-            const unsigned long long b = __ballot(bit);
-            if (lane == 0) {
-                uint32_t* out = a.bits + (size_t)f * Wd + (v0 >> 5);
-                out[0] = (uint32_t)b;
-                if ((v0 >> 5) + 1 < Wd) out[1] = (uint32_t)(b >> 32);
-            }
-        }
-}
-
 template <typename T, bool ROW8>
 __global__ __launch_bounds__(64) void k_qc_pack(const QcPackArgs pa) {
     extern __shared__ __attribute__((aligned(16))) uint32_t qc_sm[];
@@ -314,7 +217,8 @@ __global__ __launch_bounds__(64) void k_qc_pack(const QcPackArgs pa) {
                 const int g0 = __builtin_amdgcn_readlane(g, lead);
                 const uint32_t f0 = (uint32_t)__builtin_amdgcn_readlane((int)f, lead);
                 if (f0 != QC_NO_FRAME)
-                    qc_pack_write(a, (const int16_t*)((uint8_t*)qc_sm + (size_t)g0 * pa.stride), f0, __builtin_amdgcn_readlane(it, lead), lane);
+                    fx_write_frame<64>(a.y0, a.xhat, a.soft, a.bits, a.iters, n, (const int16_t*)((uint8_t*)qc_sm + (size_t)g0 * pa.stride), f0,
+                                       __builtin_amdgcn_readlane(it, lead), lane, lane, 0);
                 t &= ~(slot0 << (g0 * Z));
             }
             uint32_t drawn = 0u;
@@ -345,11 +249,9 @@ __global__ __launch_bounds__(64) void k_qc_pack(const QcPackArgs pa) {
                         }
                     }
                     if (bad) {
-                        const T* __restrict__ pr = (const T*)a.priors + (size_t)f0 * n;
                         int16_t* const marg0 = (int16_t*)((uint8_t*)qc_sm + (size_t)g0 * pa.stride);
-                        uint32_t* const cw0 = (uint32_t*)((uint8_t*)marg0 + c2v_at);
-                        for (int v = lane; v < n; v += 64) marg0[v] = (int16_t)(int)quantise_prior<T>(pr[v], step, vmax);
-                        for (int i = lane; i < m * (a.row_bytes / 4); i += 64) cw0[i] = 0u;
+                        fx_load_frame<64, T>((const T*)a.priors + (size_t)f0 * n, step, vmax, marg0, (uint32_t*)((uint8_t*)marg0 + c2v_at), n,
+                                             m * (a.row_bytes / 4), lane);
                     } else {
                         again |= lanes0;  // written out with 0 sweeps in the next round
                     }
@@ -368,22 +270,7 @@ __global__ __launch_bounds__(64) void k_qc_pack(const QcPackArgs pa) {
             const int deg = tab[4 * l];  // wave-uniform: the dispatch below is a scalar branch
             const qc_tab_t e = tab + tab[4 * l + 1];
             const int row0 = tab[4 * l + 2];
-            if (active) {
-                if constexpr (ROW8) {
-                    uint2* rowp = (uint2*)(c2v + (size_t)(row0 + r) * 8);
-                    switch (deg) {
-                        case 2: qc_check8<2>(marg, rowp, r, Z, e, a.scale64, a.offset, a.vmax); break;
-                        case 3: qc_check8<3>(marg, rowp, r, Z, e, a.scale64, a.offset, a.vmax); break;
-                        case 4: qc_check8<4>(marg, rowp, r, Z, e, a.scale64, a.offset, a.vmax); break;
-                        case 5: qc_check8<5>(marg, rowp, r, Z, e, a.scale64, a.offset, a.vmax); break;
-                        case 6: qc_check8<6>(marg, rowp, r, Z, e, a.scale64, a.offset, a.vmax); break;
-                        case 7: qc_check8<7>(marg, rowp, r, Z, e, a.scale64, a.offset, a.vmax); break;
-                        default: qc_check8<8>(marg, rowp, r, Z, e, a.scale64, a.offset, a.vmax); break;
-                    }
-                } else {
-                    qc_check_loop(marg, c2v + (size_t)(row0 + r) * a.row_bytes, deg, r, Z, e, a.scale64, a.offset, a.vmax);
-                }
-            }
+            if (active) qc_check<ROW8>(marg, c2v, row0 + r, r, Z, deg, e, a);
             __syncthreads();  // one wave: orders the block rows' LDS accesses, no hardware barrier
         }
         if (active) ++it;
@@ -507,13 +394,8 @@ int qc_create(Code* code, int32_t Z, Qc** out) {
         h->odd_check |= (d & 1) != 0;
     }
     const int64_t need = lqmsa_lds_bytes(code->m, code->n, code->E, h->dc_max);
-    if (dmin < 2) {
-        set_error("ldpc_qc_create: a block row of degree %d: layered min-sum needs every check to have degree >= 2", dmin);
-        rc = LDPC_E_UNSUPPORTED;
-    } else if (code->max_dv > LQMSA_MAX_DV) {
-        set_error("ldpc_qc_create: a variable of degree %d: the int16 marginals hold V (1 + dv) for dv <= %d", code->max_dv, LQMSA_MAX_DV);
-        rc = LDPC_E_UNSUPPORTED;
-    } else if (need > LQMSA_LDS_BYTES) {
+    rc = fx_check_degrees("ldpc_qc_create", "block row", dmin, code->max_dv, LQMSA_MAX_DV);
+    if (rc == LDPC_OK && need > LQMSA_LDS_BYTES) {
         set_error("ldpc_qc_create: one frame of this code (m = %d, n = %d, largest block-row degree %d) needs %lld bytes of LDS, above one CU's %lld; "
                   "use LDPC_ALG_LMSA (layered min-sum on the streaming kernels) for it",
                   code->m, code->n, h->dc_max, (long long)need, (long long)LQMSA_LDS_BYTES);
@@ -527,20 +409,12 @@ int qc_create(Code* code, int32_t Z, Qc** out) {
     h->lds_bytes = need;
     h->row_bytes = lqmsa_row_bytes(h->dc_max);
     const int64_t fit = LQMSA_LDS_BYTES / need;
-    h->nw = qc_waves(fit, Z);
-    if (const char* env = std::getenv("LDPC_QC_NW")) {  // the tests and the wave table reach every wave count with it
-        const int v = std::atoi(env);
-        if (v == 1 || v == 2 || v == 4 || v == 8) h->nw = v;
-    }
-    h->frames_per_cu = (int)std::min<int64_t>(fit, 32 / h->nw);
+    h->nw = fx_waves(qc_waves(fit, Z), "LDPC_QC_NW");  // (the wave table of the rate tool reaches every wave count with it too)
+    h->frames_per_cu = fx_frames_per_cu(fit, h->nw);
     if (const char* env = std::getenv("LDPC_QC_PACK_GRID")) h->pack_grid = std::max(std::atoi(env), 0);  // the tests put chosen frames into one wave's slots
     hipDeviceProp_t prop;
     if (e == hipSuccess) e = hipGetDeviceProperties(&prop, code->device);
-    if (e == hipSuccess && need > 64 * 1024) {  // above 64 KiB a workgroup's LDS has to be asked for
-        const bool row8 = h->row_bytes == 8;
-        e = hipFuncSetAttribute(kernel_of<float>(h->nw, row8), hipFuncAttributeMaxDynamicSharedMemorySize, (int)need);
-        if (e == hipSuccess) e = hipFuncSetAttribute(kernel_of<double>(h->nw, row8), hipFuncAttributeMaxDynamicSharedMemorySize, (int)need);
-    }
+    if (e == hipSuccess) e = fx_allow_lds(kernel_of<float>(h->nw, h->row_bytes == 8), kernel_of<double>(h->nw, h->row_bytes == 8), need);
     if (e != hipSuccess) {
         set_error("ldpc_qc_create: device setup failed: %s", hipGetErrorString(e));
         qc_destroy(h);
@@ -563,31 +437,16 @@ int qc_create(Code* code, int32_t Z, Qc** out) {
 
 void qc_destroy(Qc* h) {
     if (!h) return;
-    for (DevBuf* b : {&h->tab, &h->ctl, &h->sim_pri, &h->sim_y, &h->sim_bits, &h->sim_iters}) b->release();
+    for (DevBuf* b : {&h->tab, &h->ctl}) b->release();
+    h->sim.release();
     delete h;
 }
 
 int qc_set_fixed_point(Qc* h, int bits, int frac_bits, double scale, int offset) {
-    // (written so that a NaN scale fails; 64 * scale is exact, so the grid test is)
-    if (bits < 2 || bits > 8 || frac_bits < -8 || frac_bits > 8 || !(scale > 0.0 && scale <= 1.0) || 64.0 * scale != (double)(long long)(64.0 * scale) ||
-        offset < 0) {
-        set_error("ldpc_qc_set_fixed_point: 2 <= bits <= 8, -8 <= frac_bits <= 8, scale a multiple of 1/64 in (0, 1] and offset >= 0 are needed "
-                  "(bits=%d frac_bits=%d scale=%g offset=%d)", bits, frac_bits, scale, offset);
-        return LDPC_E_ARG;
-    }
-    h->bits = bits;
-    h->frac = frac_bits;
-    h->scale = scale;
-    h->offset = offset;
-    return LDPC_OK;
+    return h->fx.set("ldpc_qc_set_fixed_point", bits, frac_bits, scale, offset);
 }
 
-void qc_get_fixed_point(const Qc* h, int* bits, int* frac_bits, double* scale, int* offset) {
-    *bits = h->bits;
-    *frac_bits = h->frac;
-    *scale = h->scale;
-    *offset = h->offset;
-}
+void qc_get_fixed_point(const Qc* h, int* bits, int* frac_bits, double* scale, int* offset) { h->fx.get(bits, frac_bits, scale, offset); }
 
 void qc_get_base(const Qc* h, int32_t* mb, int32_t* nb, int32_t* Z, int32_t* shifts) {
     *mb = h->mb;
@@ -638,11 +497,9 @@ int qcpack_set(Qc* h, int32_t P) {
                   P, h->Z, (long long)stride, (long long)h->lds_bytes, (long long)LQMSA_LDS_BYTES, qc_pack(h->Z, h->lds_bytes));
         return LDPC_E_ARG;
     }
-    if (P >= 2 && P * stride > 64 * 1024) {  // above 64 KiB a workgroup's LDS has to be asked for
-        const bool row8 = h->row_bytes == 8;
+    if (P >= 2 && P * stride > 64 * 1024) {
         LDPC_HIP_TRY(hipSetDevice(h->code->device));
-        LDPC_HIP_TRY(hipFuncSetAttribute(pack_kernel_of<float>(row8), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LQMSA_LDS_BYTES));
-        LDPC_HIP_TRY(hipFuncSetAttribute(pack_kernel_of<double>(row8), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LQMSA_LDS_BYTES));
+        LDPC_HIP_TRY(fx_allow_lds(pack_kernel_of<float>(h->row_bytes == 8), pack_kernel_of<double>(h->row_bytes == 8), LQMSA_LDS_BYTES));
     }
     h->pack = P;
     return LDPC_OK;
@@ -669,42 +526,15 @@ void qc_info(const Qc* h, double* out4) {
 
 int qc_decode(Qc* h, int dtype, const void* priors, const uint8_t* y0, int64_t B, int32_t max_iter, uint32_t flags, uint8_t* xhat, uint32_t* bits,
               int32_t* iters, int16_t* soft, hipStream_t st) {
-    if (dtype != DT_F32 && dtype != DT_F64) {
-        set_error("ldpc_qc_decode: the priors are LDPC_DTYPE_F32 or LDPC_DTYPE_F64 (got %d)", dtype);
-        return LDPC_E_ARG;
-    }
-    if (flags & ~FLAG_NO_EARLY_EXIT) {
-        set_error("ldpc_qc_decode: the only flag is LDPC_FLAG_NO_EARLY_EXIT (got 0x%x)", flags);
-        return LDPC_E_UNSUPPORTED;
-    }
-    if (B > (int64_t)1 << 31) {
-        set_error("ldpc_qc_decode: at most 2^31 frames per call (got %lld)", (long long)B);
-        return LDPC_E_ARG;
-    }
+    LDPC_TRY(fx_check_decode("ldpc_qc_decode", dtype, flags, B));
     const Code* c = h->code;
     LDPC_HIP_TRY(hipSetDevice(c->device));
     if (B == 0) return LDPC_OK;
     QcArgs a;
-    a.priors = priors;
-    a.y0 = y0;
-    a.B = B;
-    a.n = c->n;
-    a.m = c->m;
+    fx_fill_args(a, c, h->fx, h->row_bytes, h->ctl.p, priors, y0, B, max_iter, flags, xhat, bits, iters, soft);
     a.Z = h->Z;
     a.mb = h->mb;
-    a.row_bytes = h->row_bytes;
-    a.cap = max_iter > 0 ? max_iter : 100000;
-    a.no_early = (flags & FLAG_NO_EARLY_EXIT) ? 1 : 0;
-    a.scale64 = (int32_t)(64.0 * h->scale);
-    a.offset = std::min(h->offset, 1 << 20);  // beyond V every message is 0 already
-    a.vmax = (1 << (h->bits - 1)) - 1;
-    a.step = std::ldexp(1.0, h->frac);
     a.tab = (const int32_t*)h->tab.p;
-    a.dispenser = (uint32_t*)h->ctl.p;
-    a.xhat = xhat;
-    a.bits = bits;
-    a.iters = iters;
-    a.soft = soft;
     LDPC_HIP_TRY(hipMemsetAsync(a.dispenser, 0, 4, st));
     if (h->pack >= 2) {
         QcPackArgs pa;
@@ -727,36 +557,10 @@ int qc_decode(Qc* h, int dtype, const void* priors, const uint8_t* y0, int64_t B
 
 int qc_simulate(Qc* h, int channel, double param, int codeword, uint64_t seed, uint64_t stream_id, uint64_t frame0, int64_t B, int32_t max_iter,
                 uint32_t flags, int32_t hist_bins, int64_t* counters, hipStream_t st) {
-    if (channel != CH_BIAWGN && channel != CH_BSC) {
-        set_error("ldpc_qc_simulate: LDPC_CH_BIAWGN or LDPC_CH_BSC (min-sum has no magnitudes to work on over the erasure channel)");
-        return LDPC_E_ARG;
-    }
-    if (codeword != 0 && codeword != 1) {
-        set_error("ldpc_qc_simulate: codeword must be 0 or 1");
-        return LDPC_E_ARG;
-    }
-    if (codeword == 1 && h->odd_check) {
-        set_error("ldpc_qc_simulate: codeword 1: the all-ones word is no codeword of this code (a check has odd degree)");
-        return LDPC_E_ARG;
-    }
-    const size_t n = (size_t)h->code->n, W = (n + 31) / 32;
-    // the priors of one pass: about 256 MiB, at most 2^17 frames
-    int64_t cap = std::min<int64_t>(std::max<int64_t>((int64_t)(((size_t)256 << 20) / (n * sizeof(float))), 1), (int64_t)1 << 17);
-    cap = std::min(cap, std::max<int64_t>(B, 1));
-    LDPC_HIP_TRY(hipSetDevice(h->code->device));
-    LDPC_TRY(h->sim_pri.reserve((size_t)cap * n * sizeof(float)));
-    if (channel == CH_BSC) LDPC_TRY(h->sim_y.reserve((size_t)cap * n));
-    LDPC_TRY(h->sim_bits.reserve((size_t)cap * W * 4));
-    LDPC_TRY(h->sim_iters.reserve((size_t)cap * sizeof(int32_t)));
-    uint8_t* y = channel == CH_BSC ? (uint8_t*)h->sim_y.p : nullptr;  // over the BSC the received word takes the iteration-0 check, as upstream
-    for (int64_t b0 = 0; b0 < B; b0 += cap) {
-        const int64_t nb = std::min(cap, B - b0);
-        LDPC_TRY(channel_generate(channel, DT_F32, param, codeword, seed, stream_id, frame0 + (uint64_t)b0, nb, (int32_t)n, h->sim_pri.p, y, st));
-        LDPC_TRY(qc_decode(h, DT_F32, h->sim_pri.p, y, nb, max_iter, flags, nullptr, (uint32_t*)h->sim_bits.p, (int32_t*)h->sim_iters.p, nullptr, st));
-        LDPC_TRY(count_errors_bits((const uint32_t*)h->sim_bits.p, nullptr, nullptr, codeword, (const int32_t*)h->sim_iters.p, nb, (int32_t)n, hist_bins,
-                                   counters, st));
-    }
-    return LDPC_OK;
+    return fx_simulate("ldpc_qc_simulate", h->code, h->odd_check, h->sim, fx_lds_sim_cap(h->code->n), channel, param, codeword, seed, stream_id, frame0, B,
+                       hist_bins, counters, st, [&](const void* pri, const uint8_t* y, int64_t nb, uint32_t* bits, int32_t* iters) {
+                           return qc_decode(h, DT_F32, pri, y, nb, max_iter, flags, nullptr, bits, iters, nullptr, st);
+                       });
 }
 
 }  // namespace ldpc

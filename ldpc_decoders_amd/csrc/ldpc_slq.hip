@@ -1,5 +1,5 @@
-// Streaming layered fixed-point min-sum (include/ldpc_hip.h, ldpc_slq_*): LQMSA's integer contract (ldpc_lqmsa.hip)
-// on LMSA's streaming machinery (ldpc_stream.hip), for codes whose frame does not fit the LDS.
+// Streaming layered fixed-point min-sum (include/ldpc_hip.h, ldpc_slq_*): the integer rule of ldpc_layered_fx.hpp,
+// which LQMSA and QCMSA run in the LDS, on LMSA's streaming machinery (ldpc_stream.hip), for codes whose frame does not fit the LDS.
 //
 // State per tile of 64 frames (lane == frame), in HBM:
 //     marg  [tile][n][64]   int16  the marginals in levels; the priors are quantised on load (quantise_prior: LDPC_ALG_QMSA's quantiser)
@@ -7,7 +7,7 @@
 //     xbits [tile/8][n][8]  u64    decision bit planes, eight tiles interleaved per variable (the layout of ldpc_stream.hip)
 //     live  [tile]          u64    frames that are still iterating
 // Every H index is wave-uniform (scalar loads, 32-bit); a marginal row is 128 bytes, a message row 64 bytes.
-// One sweep = one layer pass per layer (k_slq_layer: v = marg - c2v_old, the integer rule on the row, c2v = the new message, marg = v + c2v,
+// One sweep = one layer pass per layer (k_slq_layer: v = marg - c2v_old, the rule (FxCheck) on the row, c2v = the new message, marg = v + c2v,
 // in place; the checks of a layer share no variable) and a decision pass (k_slq_decide: sign -> planes).  Model bytes per frame-sweep:
 // 6E (2 + 2 + 1 + 1 per edge) + 2n.  Early termination per frame: syndrome of the planes before every sweep, polls of the live counters
 // that the host reads one behind, and a repack of the live frames into dense tiles (k_slq_repack) under the policy and the knobs of the
@@ -21,6 +21,7 @@
 #include <new>
 
 #include "ldpc_cn.hpp"
+#include "ldpc_layered_fx.hpp"
 #include "ldpc_repack.hpp"
 #include "ldpc_slq.hpp"
 
@@ -34,8 +35,7 @@ struct SlqSet {
 
 struct Slq {
     Code* code = nullptr;
-    int bits = 6, frac = 2, offset = 0;
-    double scale = 0.8125;
+    FixedPoint fx;
     bool odd_check = false;
     std::vector<int32_t> layer_of_check, layer_start;
     DevBuf order;  // int32 [m]: the checks sorted by (layer, index), the processing order
@@ -44,7 +44,7 @@ struct Slq {
     DevBuf flags;   // per-tile syndrome words + the device poll ring behind them
     void* pinned = nullptr;  // page-locked poll ring
     hipEvent_t poll_ev[SLQ_POLL_RING] = {};
-    DevBuf sim_pri, sim_y, sim_bits, sim_iters;  // staging of ldpc_slq_simulate
+    SimStage sim;   // staging of ldpc_slq_simulate
     // ldpc_slq_profile: [0] the layer passes of a sweep, [1] its decision pass, [2] a whole decode
     bool profile = false;
     std::vector<hipEvent_t> ev_pool;
@@ -137,12 +137,6 @@ __global__ __launch_bounds__(256) void k_slq_load(const T* __restrict__ priors, 
 }
 
 // ---- the layer pass ---------------------------------------------------------------------------------------------------------------------
-// |c2v| a minimum m <= V sends (LQMSA's rule, step 3 of its contract)
-__device__ __forceinline__ int slq_mag(int m, int scale64, int offset) {
-    const int t = ((scale64 * m) >> 6) - offset;
-    return t > 0 ? t : 0;
-}
-
 // A wave takes (tile, run of the layer's checks) out of `order`; `c0` .. `c1` is the layer's range in that list; UNR checks are in flight
 // together (all of one layer, hence independent).  Per edge: one marginal row (128 B) and one message row (64 B) read, one each written.
 // FIRST: the first sweep, where every old message is 0: nothing is read.  `freeze`: a soft-output decode keeps the marginals of a frame
@@ -205,29 +199,17 @@ __global__ __launch_bounds__(256) void k_slq_layer(const int32_t* __restrict__ r
         }
 #pragma unroll
         for (int u = 0; u < UNR; ++u) {
-            int min1 = V, min2 = V, arg = -1;  // |v| enters as min(|v|, V), so V is the neutral element
-            uint32_t par = 0;
+            FxCheck k(V);
 #pragma unroll
             for (int j = 0; j < DCMAX; ++j) {
                 if constexpr (!FIRST) v[u][j] -= w[u][j];
-                if (j < deg[u]) {
-                    const int a = min(abs(v[u][j]), V);
-                    par ^= (uint32_t)(v[u][j] < 0);
-                    if (a < min1) {
-                        min2 = min1;
-                        min1 = a;
-                        arg = j;
-                    } else if (a < min2) {
-                        min2 = a;
-                    }
-                }
+                if (j < deg[u]) k.take(j, v[u][j], V);
             }
-            const int f1 = slq_mag(min1, scale64, offset), f2 = slq_mag(min2, scale64, offset);
+            k.finish(scale64, offset);
 #pragma unroll
             for (int j = 0; j < DCMAX; ++j) {
                 if (j < deg[u]) {
-                    const int mag = j == arg ? f2 : f1;
-                    const int c = (par ^ (uint32_t)(v[u][j] < 0)) ? -mag : mag;
+                    const int c = k.out(j, v[u][j]);
                     __builtin_nontemporal_store((int8_t)c, ct + (int64_t)(k0[u] + j) * 64);
                     mt[(int64_t)edge_var[k0[u] + j] * 64] = (int16_t)(v[u][j] + c);
                 }
@@ -255,28 +237,18 @@ __global__ __launch_bounds__(256) void k_slq_layer_wide(const int32_t* __restric
     for (int i = c0 + chunk * cpw; i < i_end; ++i) {
         const int cc = order[i];
         const int k0 = row_ptr[cc], deg = row_ptr[cc + 1] - k0;
-        int min1 = V, min2 = V, arg = -1;
-        uint32_t par = 0;
+        FxCheck k(V);
         for (int j = 0; j < deg; ++j) {
             int v = mt[(int64_t)edge_var[k0 + j] * 64];
             if constexpr (!FIRST) v -= (int)ct[(int64_t)(k0 + j) * 64];
-            const int a = min(abs(v), V);
-            par ^= (uint32_t)(v < 0);
-            if (a < min1) {
-                min2 = min1;
-                min1 = a;
-                arg = j;
-            } else if (a < min2) {
-                min2 = a;
-            }
+            k.take(j, v, V);
         }
-        const int f1 = slq_mag(min1, scale64, offset), f2 = slq_mag(min2, scale64, offset);
+        k.finish(scale64, offset);
         for (int j = 0; j < deg; ++j) {
             int16_t* mp = mt + (int64_t)edge_var[k0 + j] * 64;
             int v = *mp;
             if constexpr (!FIRST) v -= (int)ct[(int64_t)(k0 + j) * 64];
-            const int mag = j == arg ? f2 : f1;
-            const int c = (par ^ (uint32_t)(v < 0)) ? -mag : mag;
+            const int c = k.out(j, v);
             ct[(int64_t)(k0 + j) * 64] = (int8_t)c;
             *mp = (int16_t)(v + c);
         }
@@ -607,9 +579,9 @@ int run_chunk(Slq* h, const SlqCall& k, size_t* prof_next, std::vector<hipEvent_
     SlqGeometry g;
     g.tiles = tiles;
     g.freeze = k.soft != nullptr ? 1 : 0;
-    g.scale64 = (int)(64.0 * h->scale);
-    g.offset = std::min(h->offset, 1 << 20);  // beyond V every message is 0 already
-    g.vmax = (1 << (h->bits - 1)) - 1;
+    g.scale64 = h->fx.scale64();
+    g.offset = h->fx.clamped_offset();
+    g.vmax = h->fx.vmax();
     // nodes per wave: many short wave tasks in tile-major order, as measured for the floating-point passes; longer runs only beyond 2^22
     // tasks per launch (measured here too, 32 768 frames of (3,6) n = 64 800, ten sweeps: 4 / 8 / 16 checks per wave 73.1 / 74.9 / 76.0 ms of
     // layer passes; 16 .. 128 variables per wave 12.8 .. 12.6 ms of decision passes)
@@ -626,8 +598,7 @@ int run_chunk(Slq* h, const SlqCall& k, size_t* prof_next, std::vector<hipEvent_
     LDPC_HIP_TRY(hipMemsetAsync(xbits, 0, plane_words(tiles, n) * 8, st));
     LDPC_HIP_TRY(hipMemsetAsync(tflags, 0, (size_t)tiles * 16 + 64 + SLQ_POLL_RING * 16, st));
     LDPC_HIP_TRY(hipMemsetAsync(k.iters, 0, (size_t)B * sizeof(int32_t), st));
-    const double step = std::ldexp(1.0, h->frac);
-    hipLaunchKernelGGL((k_slq_load<T>), dim3((n + 63) / 64, tiles), dim3(256), 0, st, (const T*)k.priors, k.y0, B, n, (T)step, (T)g.vmax, marg, xbits);
+    hipLaunchKernelGGL((k_slq_load<T>), dim3((n + 63) / 64, tiles), dim3(256), 0, st, (const T*)k.priors, k.y0, B, n, (T)h->fx.step(), (T)g.vmax, marg, xbits);
     hipLaunchKernelGGL(k_slq_init_live, dim3((tiles + 255) / 256), dim3(256), 0, st, live, B, tiles);
 
     const int cap = k.max_iter > 0 ? k.max_iter : 100000;
@@ -737,18 +708,11 @@ int install(Slq* h, const int32_t* layer_of_check) {
 }  // namespace
 
 int slq_create(Code* code, Slq** out) {
-    if (code->min_dc < 2) {
-        set_error("ldpc_slq_create: a check of degree %d: layered min-sum needs every check to have degree >= 2", code->min_dc);
-        return LDPC_E_UNSUPPORTED;
-    }
-    if (code->max_dv > SLQ_MAX_DV) {
-        set_error("ldpc_slq_create: a variable of degree %d: the int16 marginals hold V (1 + dv) for dv <= %d", code->max_dv, SLQ_MAX_DV);
-        return LDPC_E_UNSUPPORTED;
-    }
+    LDPC_TRY(fx_check_degrees("ldpc_slq_create", "check", code->min_dc, code->max_dv, SLQ_MAX_DV));
     LDPC_HIP_TRY(hipSetDevice(code->device));
     Slq* h = new Slq();
     h->code = code;
-    for (int32_t c = 0; c < code->m; ++c) h->odd_check |= ((code->row_ptr[c + 1] - code->row_ptr[c]) & 1) != 0;
+    h->odd_check = fx_odd_check(code);
     hipError_t e = hipHostMalloc(&h->pinned, 256, hipHostMallocDefault);
     for (int i = 0; i < SLQ_POLL_RING && e == hipSuccess; ++i) e = hipEventCreateWithFlags(&h->poll_ev[i], hipEventDisableTiming);
     if (e != hipSuccess) {
@@ -769,7 +733,8 @@ void slq_destroy(Slq* h) {
     if (!h) return;
     for (SlqSet& s : h->set)
         for (DevBuf* b : {&s.c2v, &s.marg, &s.planes, &s.live, &s.fmap}) b->release();
-    for (DevBuf* b : {&h->order, &h->rbase, &h->flags, &h->sim_pri, &h->sim_y, &h->sim_bits, &h->sim_iters}) b->release();
+    for (DevBuf* b : {&h->order, &h->rbase, &h->flags}) b->release();
+    h->sim.release();
     for (hipEvent_t e : h->poll_ev)
         if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : h->ev_pool) (void)hipEventDestroy(e);
@@ -778,26 +743,10 @@ void slq_destroy(Slq* h) {
 }
 
 int slq_set_fixed_point(Slq* h, int bits, int frac_bits, double scale, int offset) {
-    // (written so that a NaN scale fails; 64 * scale is exact, so the grid test is)
-    if (bits < 2 || bits > 8 || frac_bits < -8 || frac_bits > 8 || !(scale > 0.0 && scale <= 1.0) || 64.0 * scale != (double)(long long)(64.0 * scale) ||
-        offset < 0) {
-        set_error("ldpc_slq_set_fixed_point: 2 <= bits <= 8, -8 <= frac_bits <= 8, scale a multiple of 1/64 in (0, 1] and offset >= 0 are needed "
-                  "(bits=%d frac_bits=%d scale=%g offset=%d)", bits, frac_bits, scale, offset);
-        return LDPC_E_ARG;
-    }
-    h->bits = bits;
-    h->frac = frac_bits;
-    h->scale = scale;
-    h->offset = offset;
-    return LDPC_OK;
+    return h->fx.set("ldpc_slq_set_fixed_point", bits, frac_bits, scale, offset);
 }
 
-void slq_get_fixed_point(const Slq* h, int* bits, int* frac_bits, double* scale, int* offset) {
-    *bits = h->bits;
-    *frac_bits = h->frac;
-    *scale = h->scale;
-    *offset = h->offset;
-}
+void slq_get_fixed_point(const Slq* h, int* bits, int* frac_bits, double* scale, int* offset) { h->fx.get(bits, frac_bits, scale, offset); }
 
 int slq_set_layers(Slq* h, const int32_t* layer_of_check, int32_t m) {
     if (layer_of_check && m != h->code->m) {
@@ -839,18 +788,7 @@ void slq_last_stats(const Slq* h, int32_t* out3) {
 
 int slq_decode(Slq* h, int dtype, const void* priors, const uint8_t* y0, int64_t B, int32_t max_iter, uint32_t flags, uint8_t* xhat, uint32_t* bits,
                int32_t* iters, int16_t* soft, hipStream_t st) {
-    if (dtype != DT_F32 && dtype != DT_F64) {
-        set_error("ldpc_slq_decode: the priors are LDPC_DTYPE_F32 or LDPC_DTYPE_F64 (got %d)", dtype);
-        return LDPC_E_ARG;
-    }
-    if (flags & ~FLAG_NO_EARLY_EXIT) {
-        set_error("ldpc_slq_decode: the only flag is LDPC_FLAG_NO_EARLY_EXIT (got 0x%x)", flags);
-        return LDPC_E_UNSUPPORTED;
-    }
-    if (B > (int64_t)1 << 31) {
-        set_error("ldpc_slq_decode: at most 2^31 frames per call (got %lld)", (long long)B);
-        return LDPC_E_ARG;
-    }
+    LDPC_TRY(fx_check_decode("ldpc_slq_decode", dtype, flags, B));
     const Code* c = h->code;
     LDPC_HIP_TRY(hipSetDevice(c->device));
     h->last_sweeps = h->last_repacks = h->last_chunks = 0;
@@ -904,37 +842,12 @@ int slq_decode(Slq* h, int dtype, const void* priors, const uint8_t* y0, int64_t
 
 int slq_simulate(Slq* h, int channel, double param, int codeword, uint64_t seed, uint64_t stream_id, uint64_t frame0, int64_t B, int32_t max_iter,
                  uint32_t flags, int32_t hist_bins, int64_t* counters, hipStream_t st) {
-    if (channel != CH_BIAWGN && channel != CH_BSC) {
-        set_error("ldpc_slq_simulate: LDPC_CH_BIAWGN or LDPC_CH_BSC (min-sum has no magnitudes to work on over the erasure channel)");
-        return LDPC_E_ARG;
-    }
-    if (codeword != 0 && codeword != 1) {
-        set_error("ldpc_slq_simulate: codeword must be 0 or 1");
-        return LDPC_E_ARG;
-    }
-    if (codeword == 1 && h->odd_check) {
-        set_error("ldpc_slq_simulate: codeword 1: the all-ones word is no codeword of this code (a check has odd degree)");
-        return LDPC_E_ARG;
-    }
-    const size_t n = (size_t)h->code->n, W = (n + 31) / 32;
-    // the fp32 priors of one pass: a third of the workspace bound, whole state chunks where one fits, at most 2^17 frames
-    const int64_t fit = std::max<int64_t>(workspace_bytes() / 3 / (int64_t)(n * sizeof(float)), 1), ct = (int64_t)chunk_tiles(h->code) * 64;
-    int64_t cap = std::min<int64_t>(fit >= ct ? fit / ct * ct : fit, (int64_t)1 << 17);
-    cap = std::min(cap, std::max<int64_t>(B, 1));
-    LDPC_HIP_TRY(hipSetDevice(h->code->device));
-    LDPC_TRY(h->sim_pri.reserve((size_t)cap * n * sizeof(float)));
-    if (channel == CH_BSC) LDPC_TRY(h->sim_y.reserve((size_t)cap * n));
-    LDPC_TRY(h->sim_bits.reserve((size_t)cap * W * 4));
-    LDPC_TRY(h->sim_iters.reserve((size_t)cap * sizeof(int32_t)));
-    uint8_t* y = channel == CH_BSC ? (uint8_t*)h->sim_y.p : nullptr;  // over the BSC the received word takes the iteration-0 check, as upstream
-    for (int64_t b0 = 0; b0 < B; b0 += cap) {
-        const int64_t nb = std::min(cap, B - b0);
-        LDPC_TRY(channel_generate(channel, DT_F32, param, codeword, seed, stream_id, frame0 + (uint64_t)b0, nb, (int32_t)n, h->sim_pri.p, y, st));
-        LDPC_TRY(slq_decode(h, DT_F32, h->sim_pri.p, y, nb, max_iter, flags, nullptr, (uint32_t*)h->sim_bits.p, (int32_t*)h->sim_iters.p, nullptr, st));
-        LDPC_TRY(count_errors_bits((const uint32_t*)h->sim_bits.p, nullptr, nullptr, codeword, (const int32_t*)h->sim_iters.p, nb, (int32_t)n, hist_bins,
-                                   counters, st));
-    }
-    return LDPC_OK;
+    // the fp32 priors of one pass: a third of the workspace bound, whole state chunks where one fits
+    const int64_t fit = std::max<int64_t>(workspace_bytes() / 3 / (int64_t)((size_t)h->code->n * sizeof(float)), 1), ct = (int64_t)chunk_tiles(h->code) * 64;
+    return fx_simulate("ldpc_slq_simulate", h->code, h->odd_check, h->sim, fit >= ct ? fit / ct * ct : fit, channel, param, codeword, seed, stream_id, frame0, B,
+                       hist_bins, counters, st, [&](const void* pri, const uint8_t* y, int64_t nb, uint32_t* bits, int32_t* iters) {
+                           return slq_decode(h, DT_F32, pri, y, nb, max_iter, flags, nullptr, bits, iters, nullptr, st);
+                       });
 }
 
 }  // namespace ldpc
