@@ -70,23 +70,104 @@ def check_layers(code, layers):
     return lay
 
 
-class CodeHandle:
-    def __init__(self, code, device):
-        lib = _lib.load()
-        self.code, self.device = code, device
+class FamilyHandle:
+    """A handle of one ``<family>_*`` block of the C ABI: ``h`` is made by ``<family>_create(*args, &h)`` and given back to
+    ``<family>_destroy`` with the object; ``_fn(name)`` is the library's ``<family>_<name>``."""
+    family = None
+
+    def _fn(self, name):
+        return getattr(_lib.load(), "%s_%s" % (self.family, name))
+
+    def _create(self, *args):
         h = ctypes.c_void_p()
-        chk = np.ascontiguousarray(code.edge_chk, dtype=np.int32)
-        var = np.ascontiguousarray(code.edge_var, dtype=np.int32)
-        _lib.check(lib.ldpc_code_create(device, code.m, code.n, code.E, chk.ctypes.data, var.ctypes.data, ctypes.byref(h)))
+        _lib.check(self._fn("create")(*args, ctypes.byref(h)))
         self.h = h
+
+    def _create_on_code(self, code, device, *args):
+        """``_create`` for a family that lives on a code: ``<family>_create(code handle, *args, &h)``; sets code_handle, code and device."""
+        self.code_handle = code_handle(code, device)
+        self.code, self.device = code, self.code_handle.device
+        self._create(self.code_handle.h, *args)
 
     def __del__(self):
         try:
             if getattr(self, "h", None):
-                _lib.load().ldpc_code_destroy(self.h)
+                self._fn("destroy")(self.h)
                 self.h = None
         except Exception:
             pass
+
+
+class FixedPointLayers:
+    """The fixed-point parameters and the layering of a ``FamilyHandle`` whose family has ``set/get_fixed_point`` and ``set/get_layers``
+    (``ldpc_decoder``, ``ldpc_lqmsa``, ``ldpc_slq``; ``ldpc_qc`` has the first pair).  Handle state, in force from the next call; the
+    library refuses what is out of range with an ``LdpcHipError`` that names the entry point."""
+
+    def set_fixed_point(self, bits, frac_bits, scale, offset=0):
+        _lib.check(self._fn("set_fixed_point")(self.h, int(bits), int(frac_bits), float(scale), int(offset)))
+
+    def fixed_point(self):
+        b, k, o, s = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0), ctypes.c_double(0)
+        _lib.check(self._fn("get_fixed_point")(self.h, ctypes.byref(b), ctypes.byref(k), ctypes.byref(s), ctypes.byref(o)))
+        return b.value, k.value, s.value, o.value
+
+    def set_layers(self, layers=None):
+        """``layers``: one non-negative int per check (two checks of one layer share no variable), or None for the greedy layering."""
+        if layers is None:
+            _lib.check(self._fn("set_layers")(self.h, None, 0))
+            return
+        lay = np.ascontiguousarray(check_layers(self.code, layers), dtype=np.int32)
+        _lib.check(self._fn("set_layers")(self.h, lay.ctypes.data, lay.size))
+
+    def layers(self):
+        """-> (number of layers, layer of every check as int32 [m])"""
+        nl, lay = ctypes.c_int32(0), np.empty(self.code.m, dtype=np.int32)
+        _lib.check(self._fn("get_layers")(self.h, ctypes.byref(nl), lay.ctypes.data))
+        return nl.value, lay
+
+
+def channel_sent(channel, precision, param, sent, seed, stream_id, frame0, priors=True):
+    """``ldpc_channel_sent``: the channel of ``DecoderHandle.channel_device`` for the given words ``sent`` (CUDA uint8 [B, n]), one per frame
+    of [frame0, frame0 + B).  -> (priors in ``precision`` or None, y or None); ``priors=False`` asks for the received word alone."""
+    import torch
+
+    B, n = sent.shape
+    dt = torch.float64 if precision == "f64" else torch.float32
+    pri = torch.empty((B, n), dtype=dt, device=sent.device) if priors and channel != "bec" else None
+    y = None if channel == "biawgn" else torch.empty((B, n), dtype=torch.uint8, device=sent.device)
+    st = torch.cuda.current_stream(sent.device).cuda_stream
+    _lib.check(_lib.load().ldpc_channel_sent(_lib.CHANNEL[channel], _lib.IO_DTYPE[precision], float(param), sent.data_ptr(), int(seed),
+                                             int(stream_id), int(frame0), B, n, None if pri is None else pri.data_ptr(),
+                                             None if y is None else y.data_ptr(), st))
+    return pri, y
+
+
+def simulate_random_codewords(code, device, seed, stream_id, frame0, B, chunk, counters, hist_bins, decode):
+    """``codeword == -1`` for a code without a code book, stated once for every handle class: frames [frame0, frame0 + B) in chunks of
+    ``chunk`` (the class's ``words_chunk``), each a random codeword from the systematic encoder (``Code.encoder()``) ->
+    ``decode(sent, first frame of the chunk)`` -> (xhat uint8 [nb, n], iters or None), which sends the words through ``channel_sent`` and
+    decodes them -> counted against the sent words into ``counters``."""
+    import torch
+
+    lib, n = _lib.load(), code.n
+    enc = code.encoder().handle(device)
+    st = torch.cuda.current_stream(counters.device).cuda_stream
+    for b0 in range(0, int(B), int(chunk)):
+        nb = min(int(chunk), int(B) - b0)
+        sent = enc.encode_random(seed, stream_id, int(frame0) + b0, nb)
+        xhat, iters = decode(sent, int(frame0) + b0)
+        _lib.check(lib.ldpc_count_errors_words(xhat.data_ptr(), sent.data_ptr(), None if iters is None else iters.data_ptr(), nb, n, hist_bins,
+                                               counters.data_ptr(), st))
+
+
+class CodeHandle(FamilyHandle):
+    family = "ldpc_code"
+
+    def __init__(self, code, device):
+        self.code, self.device = code, device
+        chk = np.ascontiguousarray(code.edge_chk, dtype=np.int32)
+        var = np.ascontiguousarray(code.edge_var, dtype=np.int32)
+        self._create(device, code.m, code.n, code.E, chk.ctypes.data, var.ctypes.data)
 
 
 def code_handle(code, device=None):
@@ -97,26 +178,15 @@ def code_handle(code, device=None):
     return hd
 
 
-class DecoderHandle:
+class DecoderHandle(FixedPointLayers, FamilyHandle):
     """One (graph, algorithm, arithmetic, backend) decoder with its HBM workspace."""
+    family = "ldpc_decoder"
 
     def __init__(self, code, alg, precision="f32", backend="auto", device=None):
-        lib = _lib.load()
         self.code_handle = code_handle(code, device)
         self.code, self.alg, self.precision, self.backend = code, alg, precision, backend
         self.np_dtype = np.float64 if precision == "f64" else np.float32
-        h = ctypes.c_void_p()
-        _lib.check(lib.ldpc_decoder_create(self.code_handle.h, _lib.ALG[alg], _lib.DTYPE[precision], _lib.BACKEND[backend],
-                                           ctypes.byref(h)))
-        self.h = h
-
-    def __del__(self):
-        try:
-            if getattr(self, "h", None):
-                _lib.load().ldpc_decoder_destroy(self.h)
-                self.h = None
-        except Exception:
-            pass
+        self._create(self.code_handle.h, _lib.ALG[alg], _lib.DTYPE[precision], _lib.BACKEND[backend])
 
     # ---- corrected min-sum (alg="NMSA"): c2v = sign * max(scale * min - offset, 0); decoder state, in force from the next call
     def set_correction(self, scale, offset=0.0):
@@ -129,30 +199,11 @@ class DecoderHandle:
         return s.value, o.value
 
     # ---- fixed-point min-sum (alg="QMSA"): q-bit levels, c2v = sign * max(floor(scale * min(m, V)) - offset, 0); decoder state, in force
-    # from the next call
+    # from the next call (``fixed_point()`` reads it back); checked here first, so what is out of range raises ValueError
     def set_fixed_point(self, bits, frac_bits, scale, offset=0):
-        bits, frac_bits, scale, offset = check_fixed_point(bits, frac_bits, scale, offset)
-        _lib.check(_lib.load().ldpc_decoder_set_fixed_point(self.h, bits, frac_bits, scale, offset))
+        super().set_fixed_point(*check_fixed_point(bits, frac_bits, scale, offset))
 
-    def fixed_point(self):
-        b, k, o, s = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0), ctypes.c_double(0)
-        _lib.check(_lib.load().ldpc_decoder_get_fixed_point(self.h, ctypes.byref(b), ctypes.byref(k), ctypes.byref(s), ctypes.byref(o)))
-        return b.value, k.value, s.value, o.value
-
-    # ---- layered min-sum (alg="LMSA"): the layer of every check; decoder state, in force from the next call
-    def set_layers(self, layers=None):
-        """``layers``: one non-negative int per check (two checks of one layer share no variable), or None for the greedy layering."""
-        if layers is None:
-            _lib.check(_lib.load().ldpc_decoder_set_layers(self.h, None, 0))
-            return
-        lay = np.ascontiguousarray(check_layers(self.code, layers), dtype=np.int32)
-        _lib.check(_lib.load().ldpc_decoder_set_layers(self.h, lay.ctypes.data, lay.size))
-
-    def layers(self):
-        """-> (number of layers, layer of every check as int32 [m])"""
-        nl, lay = ctypes.c_int32(0), np.empty(self.code.m, dtype=np.int32)
-        _lib.check(_lib.load().ldpc_decoder_get_layers(self.h, ctypes.byref(nl), lay.ctypes.data))
-        return nl.value, lay
+    # ---- layered min-sum (alg="LMSA"): the layer of every check, ``set_layers`` / ``layers`` of FixedPointLayers
 
     # ---- host (numpy) buffers
     def decode_host(self, priors, y0, max_iter, flags=0):
@@ -320,7 +371,12 @@ class DecoderHandle:
         if getattr(self, "_cb_dev", None) is None:
             cb = getattr(self.code, "cb", None)
             if cb is None:
-                return self._simulate_encoded_words(channel, param, seed, stream_id, frame0, B, max_iter, counters, flags, hist_bins, st)
+                def decode(sent, first):
+                    pri, y = self.channel_sent_device(channel, param, sent, seed, stream_id, first)
+                    return self.decode_device(pri, y, max_iter, flags)
+
+                return simulate_random_codewords(self.code, self.code_handle.device, seed, stream_id, frame0, B, self.words_chunk(channel),
+                                                 counters, hist_bins, decode)
             self._cb_dev = torch.from_numpy(np.ascontiguousarray(cb, dtype=np.uint8)).cuda()
         n, K = self.code.n, int(self._cb_dev.shape[0])
         dt = torch.float64 if self.precision == "f64" else torch.float32
@@ -338,39 +394,15 @@ class DecoderHandle:
 
     WORDS_BYTES = 1 << 30  # what the sent words and the channel output of one chunk of the encoded-word path may occupy together
 
-    def _simulate_encoded_words(self, channel, param, seed, stream_id, frame0, B, max_iter, counters, flags, hist_bins, st):
-        import torch
-
-        lib, n = _lib.load(), self.code.n
-        enc = self.code.encoder().handle(self.code_handle.device)
-        dt = torch.float64 if self.precision == "f64" else torch.float32
-        per_frame = n * (1 + (0 if channel == "bec" else dt.itemsize) + (0 if channel == "biawgn" else 1))
-        step = max(64, min(int(B), self.WORDS_BYTES // per_frame))
-        for b0 in range(0, int(B), step):
-            nb = min(step, int(B) - b0)
-            sent = enc.encode_random(seed, stream_id, int(frame0) + b0, nb)
-            pri = None if channel == "bec" else torch.empty((nb, n), dtype=dt, device="cuda")
-            y = None if channel == "biawgn" else torch.empty((nb, n), dtype=torch.uint8, device="cuda")
-            _lib.check(lib.ldpc_channel_sent(_lib.CHANNEL[channel], _lib.IO_DTYPE[self.precision], float(param), sent.data_ptr(), int(seed),
-                                             int(stream_id), int(frame0) + b0, nb, n, None if pri is None else pri.data_ptr(),
-                                             None if y is None else y.data_ptr(), st))
-            xhat, iters = self.decode_device(pri, y, max_iter, flags)
-            _lib.check(lib.ldpc_count_errors_words(xhat.data_ptr(), sent.data_ptr(), iters.data_ptr(), nb, n, hist_bins, counters.data_ptr(), st))
+    def words_chunk(self, channel):
+        """Frames per chunk of the random-codeword path: what WORDS_BYTES holds of sent words and channel output."""
+        esz = 8 if self.precision == "f64" else 4
+        per_frame = self.code.n * (1 + (0 if channel == "bec" else esz) + (0 if channel == "biawgn" else 1))
+        return max(64, self.WORDS_BYTES // per_frame)
 
     def channel_sent_device(self, channel, param, sent, seed, stream_id, frame0):
-        """``ldpc_channel_sent``: the channel of ``channel_device`` for the given words ``sent`` (CUDA uint8 [B, n]), one per frame of
-        [frame0, frame0 + B).  -> (priors or None, y or None)."""
-        import torch
-
-        n, B = self.code.n, sent.shape[0]
-        dt = torch.float64 if self.precision == "f64" else torch.float32
-        pri = None if channel == "bec" else torch.empty((B, n), dtype=dt, device=sent.device)
-        y = None if channel == "biawgn" else torch.empty((B, n), dtype=torch.uint8, device=sent.device)
-        st = torch.cuda.current_stream(sent.device).cuda_stream
-        _lib.check(_lib.load().ldpc_channel_sent(_lib.CHANNEL[channel], _lib.IO_DTYPE[self.precision], float(param), sent.data_ptr(), int(seed),
-                                                 int(stream_id), int(frame0), B, n, None if pri is None else pri.data_ptr(),
-                                                 None if y is None else y.data_ptr(), st))
-        return pri, y
+        """``channel_sent`` in this decoder's precision.  -> (priors or None, y or None)."""
+        return channel_sent(channel, self.precision, param, sent, seed, stream_id, frame0)
 
     def fused_info(self):
         out = (ctypes.c_double * 8)()
@@ -493,27 +525,17 @@ class DecoderHandle:
         return c.value, r.value
 
 
-class MlHandle:
+class MlHandle(FamilyHandle):
     """Codebook of a short code resident in HBM + the exhaustive-search kernels (``ldpc_ml_*``)."""
+    family = "ldpc_ml"
 
     def __init__(self, codebook, channel, precision="f64", device=None):
-        lib = _lib.load()
         self.cb = np.ascontiguousarray(codebook, dtype=np.uint8)
         self.K, self.n = self.cb.shape
         self.W = (self.K + 31) // 32
         self.channel, self.precision = channel, precision
         self.device = current_device() if device is None else device
-        h = ctypes.c_void_p()
-        _lib.check(lib.ldpc_ml_create(self.device, self.cb.ctypes.data, self.K, self.n, ctypes.byref(h)))
-        self.h = h
-
-    def __del__(self):
-        try:
-            if getattr(self, "h", None):
-                _lib.load().ldpc_ml_destroy(self.h)
-                self.h = None
-        except Exception:
-            pass
+        self._create(self.device, self.cb.ctypes.data, self.K, self.n)
 
     def obs_dtype(self):
         import torch
@@ -553,25 +575,16 @@ class MlHandle:
                                                 int(seed), int(stream_id), int(frame0), int(B), counters.data_ptr(), st))
 
 
-class BecMlHandle:
+class BecMlHandle(FamilyHandle):
     """ML decoding over the BEC for a code without a code book (``ldpc_bec_ml_*``): peeling, then GF(2) elimination of the residual
     system on the device, one wave per frame that keeps erasures."""
+    family = "ldpc_bec_ml"
 
     def __init__(self, code, device=None):
-        lib = _lib.load()
-        self.code_handle = code_handle(code, device)
-        self.code, self.device = code, self.code_handle.device
-        h = ctypes.c_void_p()
-        _lib.check(lib.ldpc_bec_ml_create(self.code_handle.h, ctypes.byref(h)))
-        self.h = h
+        self._create_on_code(code, device)
 
-    def __del__(self):
-        try:
-            if getattr(self, "h", None):
-                _lib.load().ldpc_bec_ml_destroy(self.h)
-                self.h = None
-        except Exception:
-            pass
+    def words_chunk(self, channel):
+        return 1 << 17
 
     def decode_device(self, y, seed, stream_id=0, frame0=0):
         """y: contiguous CUDA uint8 tensor [B, n] of symbols {0, 1, 2} -> (xhat uint8 [B, n], nullity int32 [B]) for frames
@@ -619,39 +632,28 @@ class BecMlHandle:
             _lib.check(lib.ldpc_bec_ml_simulate(self.h, float(param), int(codeword), int(seed), int(stream_id), int(frame0), int(B),
                                                 counters.data_ptr(), st))
             return
-        n, enc = self.code.n, self.code.encoder().handle(self.device)
-        step = 1 << 17
-        for b0 in range(0, int(B), step):
-            nb = min(step, int(B) - b0)
-            sent = enc.encode_random(seed, stream_id, int(frame0) + b0, nb)
-            y = torch.empty((nb, n), dtype=torch.uint8, device=counters.device)
-            _lib.check(lib.ldpc_channel_sent(_lib.CHANNEL["bec"], 0, float(param), sent.data_ptr(), int(seed), int(stream_id), int(frame0) + b0,
-                                             nb, n, None, y.data_ptr(), st))
-            xhat, _ = self.decode_device(y, seed, stream_id, int(frame0) + b0)
-            _lib.check(lib.ldpc_count_errors_words(xhat.data_ptr(), sent.data_ptr(), None, nb, n, 0, counters.data_ptr(), st))
+
+        def decode(sent, first):
+            y = channel_sent("bec", "f32", param, sent, seed, stream_id, first)[1]
+            return self.decode_device(y, seed, stream_id, first)[0], None
+
+        simulate_random_codewords(self.code, self.device, seed, stream_id, frame0, B, self.words_chunk(channel), counters, 0, decode)
 
 
-class OsdHandle:
+class OsdHandle(FamilyHandle):
     """Ordered-statistics post-processing of an LLR decoder (``ldpc_osd_*``): the frames BP leaves without a codeword are decoded again
     from its soft output, one wave per frame.  ``bp`` is the ``DecoderHandle`` (fp32 / fp64 MSA, SPA, NMSA or QMSA, same code) that runs in
     front; ``order`` in {0, 1} and ``depth`` >= 0 are read at every call."""
+    family = "ldpc_osd"
 
     def __init__(self, bp, order=0, depth=64):
-        lib = _lib.load()
         self.bp, self.code, self.code_handle = bp, bp.code, bp.code_handle
         self.device, self.precision = bp.code_handle.device, bp.precision
         self.order, self.depth = int(order), int(depth)
-        h = ctypes.c_void_p()
-        _lib.check(lib.ldpc_osd_create(self.code_handle.h, ctypes.byref(h)))
-        self.h = h
+        self._create(self.code_handle.h)
 
-    def __del__(self):
-        try:
-            if getattr(self, "h", None):
-                _lib.load().ldpc_osd_destroy(self.h)
-                self.h = None
-        except Exception:
-            pass
+    def words_chunk(self, channel):
+        return 1 << 17
 
     def solve(self, post, prior, order=None, depth=None, want_cost=True):
         """``ldpc_osd_solve``: post / prior contiguous CUDA tensors [B, n] of one dtype (float32 or float64) -> (words int32 [B, ceil(n/32)]
@@ -712,37 +714,24 @@ class OsdHandle:
             _lib.check(lib.ldpc_osd_simulate(self.h, self.bp.h, _lib.CHANNEL[channel], float(param), int(codeword), int(seed), int(stream_id),
                                              int(frame0), int(B), int(max_iter), flags, self.order, self.depth, hist_bins, counters.data_ptr(), st))
             return
-        n, enc = self.code.n, self.code.encoder().handle(self.device)
-        step = 1 << 17
-        for b0 in range(0, int(B), step):
-            nb = min(step, int(B) - b0)
-            sent = enc.encode_random(seed, stream_id, int(frame0) + b0, nb)
-            pri, y = self.bp.channel_sent_device(channel, param, sent, seed, stream_id, int(frame0) + b0)
-            xhat, iters, _ = self.decode_device(pri, y, max_iter, flags)
-            _lib.check(lib.ldpc_count_errors_words(xhat.data_ptr(), sent.data_ptr(), iters.data_ptr(), nb, n, hist_bins, counters.data_ptr(), st))
+
+        def decode(sent, first):
+            pri, y = self.bp.channel_sent_device(channel, param, sent, seed, stream_id, first)
+            return self.decode_device(pri, y, max_iter, flags)[:2]
+
+        simulate_random_codewords(self.code, self.device, seed, stream_id, frame0, B, self.words_chunk(channel), counters, hist_bins, decode)
 
 
-class HardHandle:
+class HardHandle(FamilyHandle):
     """Bit-sliced Gallager-B hard-decision decoder (``ldpc_hard_*``): one bit per message, 32 frames per machine word.  ``backend``:
     "stream" (planes in HBM, any code), "fused" (one slab per workgroup in the LDS; refused for a code that does not fit) or "auto"."""
+    family = "ldpc_hard"
 
     def __init__(self, code, backend="auto", device=None, threshold=0):
-        lib = _lib.load()
-        self.code_handle = code_handle(code, device)
-        self.code, self.device, self.backend = code, self.code_handle.device, backend
-        h = ctypes.c_void_p()
-        _lib.check(lib.ldpc_hard_create(self.code_handle.h, _lib.BACKEND[backend], ctypes.byref(h)))
-        self.h = h
+        self.backend = backend
+        self._create_on_code(code, device, _lib.BACKEND[backend])
         if threshold:
             self.set_threshold(threshold)
-
-    def __del__(self):
-        try:
-            if getattr(self, "h", None):
-                _lib.load().ldpc_hard_destroy(self.h)
-                self.h = None
-        except Exception:
-            pass
 
     def set_threshold(self, t):
         _lib.check(_lib.load().ldpc_hard_set_threshold(self.h, int(t)))
@@ -810,67 +799,27 @@ class HardHandle:
             _lib.check(lib.ldpc_hard_simulate(self.h, _lib.CHANNEL[channel], float(param), int(codeword), int(seed), int(stream_id), int(frame0),
                                               int(B), int(max_iter), flags, hist_bins, counters.data_ptr(), st))
             return
-        n, enc = self.code.n, self.code.encoder().handle(self.device)
-        step = max(2048, min(1 << 17, (1 << 28) // n))
-        for b0 in range(0, int(B), step):
-            nb = min(step, int(B) - b0)
-            sent = enc.encode_random(seed, stream_id, int(frame0) + b0, nb)
-            pri = torch.empty((nb, n), dtype=torch.float32, device=sent.device) if channel == "biawgn" else None
-            y = torch.empty((nb, n), dtype=torch.uint8, device=sent.device) if channel == "bsc" else None
-            _lib.check(lib.ldpc_channel_sent(_lib.CHANNEL[channel], _lib.DTYPE["f32"], float(param), sent.data_ptr(), int(seed), int(stream_id),
-                                             int(frame0) + b0, nb, n, None if pri is None else pri.data_ptr(), None if y is None else y.data_ptr(), st))
+
+        def decode(sent, first):
+            pri, y = channel_sent(channel, "f32", param, sent, seed, stream_id, first, priors=channel == "biawgn")
             if y is None:
                 y = (pri < 0).to(torch.uint8)  # the word sliced at prior < 0
-            xhat, iters = self.decode_device(y, max_iter, flags)
-            _lib.check(lib.ldpc_count_errors_words(xhat.data_ptr(), sent.data_ptr(), iters.data_ptr(), nb, n, hist_bins, counters.data_ptr(), st))
+            return self.decode_device(y, max_iter, flags)
+
+        simulate_random_codewords(self.code, self.device, seed, stream_id, frame0, B, self.words_chunk(channel), counters, hist_bins, decode)
+
+    def words_chunk(self, channel):
+        return max(2048, min(1 << 17, (1 << 28) // self.code.n))
 
 
-class LqmsaHandle:
+class LqmsaHandle(FixedPointLayers, FamilyHandle):
     """Layered fixed-point min-sum with the frame resident in the LDS as integers (``ldpc_lqmsa_*``): one workgroup per frame, int16
     marginals, int8 check messages; priors in fp32 or fp64, quantised on load."""
     family = "ldpc_lqmsa"  # the handle family of the C ABI the calls below go to (QcHandle: the same call shapes under ldpc_qc_*)
 
-    def _fn(self, name):
-        return getattr(_lib.load(), "%s_%s" % (self.family, name))
-
     def __init__(self, code, device=None, bits=6, frac_bits=2, scale=0.8125, offset=0):
-        _lib.load()
-        self.code_handle = code_handle(code, device)
-        self.code, self.device = code, self.code_handle.device
-        h = ctypes.c_void_p()
-        _lib.check(self._fn("create")(self.code_handle.h, ctypes.byref(h)))
-        self.h = h
+        self._create_on_code(code, device)
         self.set_fixed_point(bits, frac_bits, scale, offset)
-
-    def __del__(self):
-        try:
-            if getattr(self, "h", None):
-                self._fn("destroy")(self.h)
-                self.h = None
-        except Exception:
-            pass
-
-    def set_fixed_point(self, bits, frac_bits, scale, offset=0):
-        _lib.check(self._fn("set_fixed_point")(self.h, int(bits), int(frac_bits), float(scale), int(offset)))
-
-    def fixed_point(self):
-        b, k, o, s = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0), ctypes.c_double(0)
-        _lib.check(self._fn("get_fixed_point")(self.h, ctypes.byref(b), ctypes.byref(k), ctypes.byref(s), ctypes.byref(o)))
-        return b.value, k.value, s.value, o.value
-
-    def set_layers(self, layers=None):
-        """``layers``: one non-negative int per check (two checks of one layer share no variable), or None for the greedy layering."""
-        if layers is None:
-            _lib.check(self._fn("set_layers")(self.h, None, 0))
-            return
-        lay = np.ascontiguousarray(check_layers(self.code, layers), dtype=np.int32)
-        _lib.check(self._fn("set_layers")(self.h, lay.ctypes.data, lay.size))
-
-    def layers(self):
-        """-> (number of layers, layer of every check as int32 [m])"""
-        nl, lay = ctypes.c_int32(0), np.empty(self.code.m, dtype=np.int32)
-        _lib.check(self._fn("get_layers")(self.h, ctypes.byref(nl), lay.ctypes.data))
-        return nl.value, lay
 
     def info(self):
         out = (ctypes.c_double * 4)()
@@ -917,17 +866,15 @@ class LqmsaHandle:
             _lib.check(self._fn("simulate")(self.h, _lib.CHANNEL[channel], float(param), int(codeword), int(seed), int(stream_id), int(frame0),
                                             int(B), int(max_iter), flags, hist_bins, counters.data_ptr(), st))
             return
-        n, enc = self.code.n, self.code.encoder().handle(self.device)
-        step = max(2048, min(1 << 17, (1 << 26) // n))
-        for b0 in range(0, int(B), step):
-            nb = min(step, int(B) - b0)
-            sent = enc.encode_random(seed, stream_id, int(frame0) + b0, nb)
-            pri = torch.empty((nb, n), dtype=torch.float32, device=sent.device)
-            y = torch.empty((nb, n), dtype=torch.uint8, device=sent.device) if channel == "bsc" else None
-            _lib.check(lib.ldpc_channel_sent(_lib.CHANNEL[channel], _lib.DTYPE["f32"], float(param), sent.data_ptr(), int(seed), int(stream_id),
-                                             int(frame0) + b0, nb, n, pri.data_ptr(), None if y is None else y.data_ptr(), st))
-            xhat, iters = self.decode_device(pri, y, max_iter, flags)
-            _lib.check(lib.ldpc_count_errors_words(xhat.data_ptr(), sent.data_ptr(), iters.data_ptr(), nb, n, hist_bins, counters.data_ptr(), st))
+
+        def decode(sent, first):
+            pri, y = channel_sent(channel, "f32", param, sent, seed, stream_id, first)
+            return self.decode_device(pri, y, max_iter, flags)
+
+        simulate_random_codewords(self.code, self.device, seed, stream_id, frame0, B, self.words_chunk(channel), counters, hist_bins, decode)
+
+    def words_chunk(self, channel):
+        return max(2048, min(1 << 17, (1 << 26) // self.code.n))
 
 
 class QcHandle(LqmsaHandle):
@@ -936,12 +883,7 @@ class QcHandle(LqmsaHandle):
     family = "ldpc_qc"
 
     def __init__(self, code, Z, device=None, bits=6, frac_bits=2, scale=0.8125, offset=0, pack=1):
-        lib = _lib.load()
-        self.code_handle = code_handle(code, device)
-        self.code, self.device = code, self.code_handle.device
-        h = ctypes.c_void_p()
-        _lib.check(lib.ldpc_qc_create(self.code_handle.h, int(Z), ctypes.byref(h)))
-        self.h = h
+        self._create_on_code(code, device, int(Z))
         self.set_fixed_point(bits, frac_bits, scale, offset)
         if pack != 1:
             self.set_pack(pack)
@@ -1013,24 +955,12 @@ class SlqHandle(LqmsaHandle):
         return tuple(out)
 
 
-class AdmmHandle:
+class AdmmHandle(FamilyHandle):
     """ADMM LP decoder workspace on one GPU (``ldpc_admm_*``)."""
+    family = "ldpc_admm"
 
     def __init__(self, code, device=None):
-        lib = _lib.load()
-        self.code_handle = code_handle(code, device)
-        self.code = code
-        h = ctypes.c_void_p()
-        _lib.check(lib.ldpc_admm_create(self.code_handle.h, ctypes.byref(h)))
-        self.h = h
-
-    def __del__(self):
-        try:
-            if getattr(self, "h", None):
-                _lib.load().ldpc_admm_destroy(self.h)
-                self.h = None
-        except Exception:
-            pass
+        self._create_on_code(code, device)
 
     def decode_device(self, gamma, mu, eps, max_iter):
         """gamma: contiguous CUDA float64 [B,n] -> (x float64 [B,n] before pseudo_to_cw, iters int32 [B], converged uint8 [B])."""

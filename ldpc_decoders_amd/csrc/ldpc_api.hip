@@ -18,6 +18,7 @@
 #include "ldpc_lqmsa.hpp"
 #include "ldpc_osd.hpp"
 #include "ldpc_qc.hpp"
+#include "ldpc_sim.hpp"
 #include "ldpc_slq.hpp"
 
 namespace ldpc {
@@ -297,6 +298,7 @@ int code_build_host(int32_t m, int32_t n, int64_t E, const int32_t* chk, const i
         c->min_dc = d < c->min_dc ? d : c->min_dc;
         c->row_ptr[i + 1] += c->row_ptr[i];
     }
+    c->odd_check = has_odd_check(c->row_ptr);
     for (int i = 0; i < n; ++i) {
         const int d = c->col_ptr[i + 1];
         c->max_dv = d > c->max_dv ? d : c->max_dv;
@@ -333,6 +335,101 @@ static int guarded(const char* who, F&& f) noexcept {
     }
 }
 
+// ---- the entry points of the auxiliary handle families (ldpc_ml_* ... ldpc_admm_*, at the end of this file) ----
+// H is the family's handle struct, T its opaque ABI type.  Every refusal names its entry point: "<entry>: <what>".
+static const char* const BAD_ARGS = "bad arguments";
+
+// runs f(handle) inside the guard; a null handle, or `ok` false (the call's other required arguments), is refused with `what`
+template <class H, class T, class F>
+static int handle_entry(const char* entry, T h, bool ok, const char* what, F&& f) {
+    return guarded(entry, [&]() -> int {
+        if (!h || !ok) {
+            set_error("%s: %s", entry, what);
+            return LDPC_E_ARG;
+        }
+        return f((H*)h);
+    });
+}
+
+// *_create of a family that lives on a code: create(code, &handle)
+template <class H, class T, class F>
+static int create_entry(const char* entry, ldpc_code_t code, T* out, F&& create) {
+    return guarded(entry, [&]() -> int {
+        if (!code || !out) {
+            set_error("%s: %s", entry, BAD_ARGS);
+            return LDPC_E_ARG;
+        }
+        H* h = nullptr;
+        LDPC_TRY(create((Code*)code, &h));
+        *out = (T)h;
+        return LDPC_OK;
+    });
+}
+
+// *_destroy (null is allowed)
+template <class H, class T>
+static int destroy_entry(const char* entry, T h, void (*destroy)(H*)) {
+    return guarded(entry, [&]() -> int {
+        destroy((H*)h);
+        return LDPC_OK;
+    });
+}
+
+// the entry points whose call shape several families share (Hard, Lqmsa, Qc, Slq); each family's own definition below is one call
+template <class H, class T>
+static int simulate_entry(const char* entry, T h, int (*simulate)(H*, int, double, int, uint64_t, uint64_t, uint64_t, int64_t, int32_t, uint32_t, int32_t, int64_t*, hipStream_t),
+                          int channel, double param, int codeword, uint64_t seed, uint64_t stream_id, uint64_t frame0, int64_t B, int32_t max_iter,
+                          uint32_t flags, int32_t hist_bins, int64_t* counters, void* stream) {
+    return handle_entry<H>(entry, h, counters && B >= 0 && hist_bins >= 0, BAD_ARGS, [&](H* d) {
+        return simulate(d, channel, param, codeword, seed, stream_id, frame0, B, max_iter, flags, hist_bins, counters, (hipStream_t)stream);
+    });
+}
+
+template <class H, class T>
+static int info_entry(const char* entry, T h, void (*info)(const H*, double*), double* out4) {
+    return handle_entry<H>(entry, h, out4 != nullptr, BAD_ARGS, [&](H* d) {
+        info(d, out4);
+        return LDPC_OK;
+    });
+}
+
+// ... and those of the layered fixed-point families (Lqmsa, Qc, Slq)
+template <class H, class T>
+static int fx_decode_entry(const char* entry, T h, int (*decode)(H*, int, const void*, const uint8_t*, int64_t, int32_t, uint32_t, uint8_t*, uint32_t*, int32_t*, int16_t*, hipStream_t),
+                           int dtype, const void* priors, const uint8_t* y0, int64_t B, int32_t max_iter, uint32_t flags, uint8_t* xhat, uint32_t* bits,
+                           int32_t* iters, int16_t* soft, void* stream) {
+    return handle_entry<H>(entry, h, priors && (xhat || bits) && iters && B >= 0,
+                           "bad arguments (priors, iters and at least one of xhat / xhat_bits are required)", [&](H* d) {
+                               return decode(d, dtype, priors, y0, B, max_iter, flags, xhat, bits, iters, soft, (hipStream_t)stream);
+                           });
+}
+
+template <class H, class T>
+static int fx_set_fixed_point_entry(const char* entry, T h, int (*set)(H*, int, int, double, int), int bits, int frac_bits, double scale, int offset) {
+    return handle_entry<H>(entry, h, true, BAD_ARGS, [&](H* d) { return set(d, bits, frac_bits, scale, offset); });
+}
+
+template <class H, class T>
+static int fx_get_fixed_point_entry(const char* entry, T h, void (*get)(const H*, int*, int*, double*, int*), int* bits, int* frac_bits, double* scale,
+                                    int* offset) {
+    return handle_entry<H>(entry, h, bits && frac_bits && scale && offset, "a handle and four result pointers are needed", [&](H* d) {
+        get(d, bits, frac_bits, scale, offset);
+        return LDPC_OK;
+    });
+}
+
+template <class H, class T>
+static int fx_set_layers_entry(const char* entry, T h, int (*set)(H*, const int32_t*, int32_t), const int32_t* layer_of_check, int32_t m) {
+    return handle_entry<H>(entry, h, true, BAD_ARGS, [&](H* d) { return set(d, layer_of_check, m); });
+}
+
+template <class H, class T>
+static int fx_get_layers_entry(const char* entry, T h, void (*get)(const H*, int32_t*, int32_t*), int32_t* nlayers, int32_t* layer_of_check) {
+    return handle_entry<H>(entry, h, nlayers != nullptr, "a handle and a result pointer are needed", [&](H* d) {
+        get(d, nlayers, layer_of_check);
+        return LDPC_OK;
+    });
+}
 
 extern "C" {
 
@@ -1185,135 +1282,70 @@ int ldpc_ml_create(int device, const uint8_t* codebook, int64_t K, int32_t n, ld
     });
 }
 
-int ldpc_ml_destroy(ldpc_ml_t h) {
-    return guarded("ldpc_ml_destroy", [&]() -> int {
-        ml_destroy((MlDecoder*)h);
-        return LDPC_OK;
-    });
-}
+int ldpc_ml_destroy(ldpc_ml_t h) { return destroy_entry("ldpc_ml_destroy", h, ml_destroy); }
 
 int ldpc_ml_decode(ldpc_ml_t h, int channel, int dtype, const double* coef2, const void* y_dev, int64_t B,
                    const uint32_t* pick_dev, int32_t* index_dev, int32_t* ties_dev, uint32_t* tie_mask_dev, double* best_dev,
                    uint8_t* xhat_dev, void* stream) {
-    return guarded("ldpc_ml_decode", [&]() -> int {
-        if (!h || !coef2 || !y_dev || B < 0 || dtype < 0 || dtype > 1) {
-            set_error("ldpc_ml_decode: bad arguments");
-            return LDPC_E_ARG;
-        }
-        return ml_decode((MlDecoder*)h, channel, dtype, coef2, y_dev, B, pick_dev, index_dev, ties_dev, tie_mask_dev, best_dev, xhat_dev,
-                         (hipStream_t)stream);
+    return handle_entry<MlDecoder>("ldpc_ml_decode", h, coef2 && y_dev && B >= 0 && dtype >= 0 && dtype <= 1, BAD_ARGS, [&](MlDecoder* d) {
+        return ml_decode(d, channel, dtype, coef2, y_dev, B, pick_dev, index_dev, ties_dev, tie_mask_dev, best_dev, xhat_dev, (hipStream_t)stream);
     });
 }
 
 int ldpc_ml_simulate(ldpc_ml_t h, int channel, int dtype, double param, int codeword, uint64_t seed, uint64_t stream_id,
                      uint64_t frame0, int64_t B, int64_t* counters_dev, void* stream) {
-    return guarded("ldpc_ml_simulate", [&]() -> int {
-        if (!h || !counters_dev || B < 0 || dtype < 0 || dtype > 1 || (codeword != 0 && codeword != 1)) {
-            set_error("ldpc_ml_simulate: bad arguments");
-            return LDPC_E_ARG;
-        }
-        return ml_simulate((MlDecoder*)h, channel, dtype, param, codeword, seed, stream_id, frame0, B, counters_dev, (hipStream_t)stream);
-    });
+    return handle_entry<MlDecoder>("ldpc_ml_simulate", h, counters_dev && B >= 0 && dtype >= 0 && dtype <= 1 && (codeword == 0 || codeword == 1), BAD_ARGS,
+                                   [&](MlDecoder* d) {
+                                       return ml_simulate(d, channel, dtype, param, codeword, seed, stream_id, frame0, B, counters_dev, (hipStream_t)stream);
+                                   });
 }
 
 // ---- ML erasure decoder of every code (ldpc_bec_ml.hip) ----
-int ldpc_bec_ml_create(ldpc_code_t code, ldpc_bec_ml_t* out) {
-    return guarded("ldpc_bec_ml_create", [&]() -> int {
-        if (!code || !out) {
-            set_error("ldpc_bec_ml_create: bad arguments");
-            return LDPC_E_ARG;
-        }
-        BecMl* h = nullptr;
-        LDPC_TRY(bec_ml_create((Code*)code, &h));
-        *out = (ldpc_bec_ml_t)h;
-        return LDPC_OK;
-    });
-}
+int ldpc_bec_ml_create(ldpc_code_t code, ldpc_bec_ml_t* out) { return create_entry<BecMl>("ldpc_bec_ml_create", code, out, bec_ml_create); }
 
-int ldpc_bec_ml_destroy(ldpc_bec_ml_t h) {
-    return guarded("ldpc_bec_ml_destroy", [&]() -> int {
-        bec_ml_destroy((BecMl*)h);
-        return LDPC_OK;
-    });
-}
+int ldpc_bec_ml_destroy(ldpc_bec_ml_t h) { return destroy_entry("ldpc_bec_ml_destroy", h, bec_ml_destroy); }
 
 int ldpc_bec_ml_solve(ldpc_bec_ml_t h, const uint32_t* bits_dev, const uint32_t* erased_bits_dev, int64_t B, uint64_t seed, uint64_t stream_id,
                       uint64_t frame0, uint32_t* out_bits_dev, int32_t* nullity_dev, void* stream) {
-    return guarded("ldpc_bec_ml_solve", [&]() -> int {
-        if (!h || !bits_dev || !erased_bits_dev || !out_bits_dev || !nullity_dev || B < 0) {
-            set_error("ldpc_bec_ml_solve: bad arguments");
-            return LDPC_E_ARG;
-        }
-        return bec_ml_solve((BecMl*)h, bits_dev, erased_bits_dev, B, seed, stream_id, frame0, out_bits_dev, nullity_dev, (hipStream_t)stream);
+    return handle_entry<BecMl>("ldpc_bec_ml_solve", h, bits_dev && erased_bits_dev && out_bits_dev && nullity_dev && B >= 0, BAD_ARGS, [&](BecMl* d) {
+        return bec_ml_solve(d, bits_dev, erased_bits_dev, B, seed, stream_id, frame0, out_bits_dev, nullity_dev, (hipStream_t)stream);
     });
 }
 
 int ldpc_bec_ml_decode(ldpc_bec_ml_t h, const uint8_t* y_dev, int64_t B, uint64_t seed, uint64_t stream_id, uint64_t frame0, uint8_t* xhat_dev,
                        int32_t* nullity_dev, void* stream) {
-    return guarded("ldpc_bec_ml_decode", [&]() -> int {
-        if (!h || !y_dev || !xhat_dev || !nullity_dev || B < 0) {
-            set_error("ldpc_bec_ml_decode: bad arguments");
-            return LDPC_E_ARG;
-        }
-        return bec_ml_decode((BecMl*)h, y_dev, B, seed, stream_id, frame0, xhat_dev, nullity_dev, (hipStream_t)stream);
+    return handle_entry<BecMl>("ldpc_bec_ml_decode", h, y_dev && xhat_dev && nullity_dev && B >= 0, BAD_ARGS, [&](BecMl* d) {
+        return bec_ml_decode(d, y_dev, B, seed, stream_id, frame0, xhat_dev, nullity_dev, (hipStream_t)stream);
     });
 }
 
 int ldpc_bec_ml_simulate(ldpc_bec_ml_t h, double param, int codeword, uint64_t seed, uint64_t stream_id, uint64_t frame0, int64_t B,
                          int64_t* counters_dev, void* stream) {
-    return guarded("ldpc_bec_ml_simulate", [&]() -> int {
-        if (!h || !counters_dev || B < 0) {
-            set_error("ldpc_bec_ml_simulate: bad arguments");
-            return LDPC_E_ARG;
-        }
-        return bec_ml_simulate((BecMl*)h, param, codeword, seed, stream_id, frame0, B, counters_dev, (hipStream_t)stream);
+    return handle_entry<BecMl>("ldpc_bec_ml_simulate", h, counters_dev && B >= 0, BAD_ARGS, [&](BecMl* d) {
+        return bec_ml_simulate(d, param, codeword, seed, stream_id, frame0, B, counters_dev, (hipStream_t)stream);
     });
 }
 
 // ---- ordered-statistics post-processing of the LLR decoders (ldpc_osd.hip) ----
 // adds to BPA.decode (src/bpa.py:17-63; no upstream counterpart)
-int ldpc_osd_create(ldpc_code_t code, ldpc_osd_t* out) {
-    return guarded("ldpc_osd_create", [&]() -> int {
-        if (!code || !out) {
-            set_error("ldpc_osd_create: bad arguments");
-            return LDPC_E_ARG;
-        }
-        Osd* h = nullptr;
-        LDPC_TRY(osd_create((Code*)code, &h));
-        *out = (ldpc_osd_t)h;
-        return LDPC_OK;
-    });
-}
+int ldpc_osd_create(ldpc_code_t code, ldpc_osd_t* out) { return create_entry<Osd>("ldpc_osd_create", code, out, osd_create); }
 
 // adds to BPA.decode (src/bpa.py:17-63; no upstream counterpart)
-int ldpc_osd_destroy(ldpc_osd_t h) {
-    return guarded("ldpc_osd_destroy", [&]() -> int {
-        osd_destroy((Osd*)h);
-        return LDPC_OK;
-    });
-}
+int ldpc_osd_destroy(ldpc_osd_t h) { return destroy_entry("ldpc_osd_destroy", h, osd_destroy); }
 
 // adds to BPA.decode (src/bpa.py:17-63; no upstream counterpart): the post-processing of given soft values
 int ldpc_osd_solve(ldpc_osd_t h, int dtype, const void* post_dev, const void* prior_dev, int64_t B, int32_t order, int64_t depth,
                    uint32_t* out_bits_dev, int32_t* pick_dev, double* cost_dev, void* stream) {
-    return guarded("ldpc_osd_solve", [&]() -> int {
-        if (!h || !post_dev || !prior_dev || !out_bits_dev || !pick_dev || B < 0) {
-            set_error("ldpc_osd_solve: bad arguments");
-            return LDPC_E_ARG;
-        }
-        return osd_solve((Osd*)h, dtype, post_dev, prior_dev, B, order, depth, out_bits_dev, pick_dev, cost_dev, (hipStream_t)stream);
+    return handle_entry<Osd>("ldpc_osd_solve", h, post_dev && prior_dev && out_bits_dev && pick_dev && B >= 0, BAD_ARGS, [&](Osd* d) {
+        return osd_solve(d, dtype, post_dev, prior_dev, B, order, depth, out_bits_dev, pick_dev, cost_dev, (hipStream_t)stream);
     });
 }
 
 // adds to BPA.decode (src/bpa.py:17-63; no upstream counterpart): BP, then the frames it left without a codeword
 int ldpc_osd_decode(ldpc_osd_t h, ldpc_decoder_t dec, const void* priors_dev, const uint8_t* y0_dev, int64_t B, int32_t max_iter, uint32_t flags,
                     int32_t order, int64_t depth, uint8_t* xhat_dev, int32_t* iters_dev, int32_t* pick_dev, void* stream) {
-    return guarded("ldpc_osd_decode", [&]() -> int {
-        if (!h || !dec || !priors_dev || !xhat_dev || !iters_dev || !pick_dev || B < 0) {
-            set_error("ldpc_osd_decode: bad arguments");
-            return LDPC_E_ARG;
-        }
-        return osd_decode((Osd*)h, dec, priors_dev, y0_dev, B, max_iter, flags, order, depth, xhat_dev, iters_dev, pick_dev, (hipStream_t)stream);
+    return handle_entry<Osd>("ldpc_osd_decode", h, dec && priors_dev && xhat_dev && iters_dev && pick_dev && B >= 0, BAD_ARGS, [&](Osd* d) {
+        return osd_decode(d, dec, priors_dev, y0_dev, B, max_iter, flags, order, depth, xhat_dev, iters_dev, pick_dev, (hipStream_t)stream);
     });
 }
 
@@ -1321,479 +1353,227 @@ int ldpc_osd_decode(ldpc_osd_t h, ldpc_decoder_t dec, const void* priors_dev, co
 int ldpc_osd_simulate(ldpc_osd_t h, ldpc_decoder_t dec, int channel, double param, int codeword, uint64_t seed, uint64_t stream_id, uint64_t frame0,
                       int64_t B, int32_t max_iter, uint32_t flags, int32_t order, int64_t depth, int32_t hist_bins, int64_t* counters_dev,
                       void* stream) {
-    return guarded("ldpc_osd_simulate", [&]() -> int {
-        if (!h || !dec || !counters_dev || B < 0 || hist_bins < 0) {
-            set_error("ldpc_osd_simulate: bad arguments");
-            return LDPC_E_ARG;
-        }
-        return osd_simulate((Osd*)h, dec, channel, param, codeword, seed, stream_id, frame0, B, max_iter, flags, order, depth, hist_bins,
-                            counters_dev, (hipStream_t)stream);
+    return handle_entry<Osd>("ldpc_osd_simulate", h, dec && counters_dev && B >= 0 && hist_bins >= 0, BAD_ARGS, [&](Osd* d) {
+        return osd_simulate(d, dec, channel, param, codeword, seed, stream_id, frame0, B, max_iter, flags, order, depth, hist_bins, counters_dev,
+                            (hipStream_t)stream);
     });
 }
 
 // ---- bit-sliced Gallager-B hard-decision decoder (ldpc_hard.hip) ----
 // no upstream counterpart (the reference decodes soft values, src/bpa.py, or erasures, src/bec.py)
 int ldpc_hard_create(ldpc_code_t code, int backend, ldpc_hard_t* out) {
-    return guarded("ldpc_hard_create", [&]() -> int {
-        if (!code || !out) {
-            set_error("ldpc_hard_create: bad arguments");
-            return LDPC_E_ARG;
-        }
-        Hard* h = nullptr;
-        LDPC_TRY(hard_create((Code*)code, backend, &h));
-        *out = (ldpc_hard_t)h;
-        return LDPC_OK;
-    });
+    return create_entry<Hard>("ldpc_hard_create", code, out, [&](Code* c, Hard** h) { return hard_create(c, backend, h); });
 }
 
-int ldpc_hard_destroy(ldpc_hard_t h) {
-    return guarded("ldpc_hard_destroy", [&]() -> int {
-        hard_destroy((Hard*)h);
-        return LDPC_OK;
-    });
-}
+int ldpc_hard_destroy(ldpc_hard_t h) { return destroy_entry("ldpc_hard_destroy", h, hard_destroy); }
 
 int ldpc_hard_set_threshold(ldpc_hard_t h, int t) {
-    return guarded("ldpc_hard_set_threshold", [&]() -> int {
-        if (!h) {
-            set_error("ldpc_hard_set_threshold: bad arguments");
-            return LDPC_E_ARG;
-        }
-        return hard_set_threshold((Hard*)h, t);
-    });
+    return handle_entry<Hard>("ldpc_hard_set_threshold", h, true, BAD_ARGS, [&](Hard* d) { return hard_set_threshold(d, t); });
 }
 
 int ldpc_hard_get_threshold(ldpc_hard_t h, int* t) {
-    return guarded("ldpc_hard_get_threshold", [&]() -> int {
-        if (!h || !t) {
-            set_error("ldpc_hard_get_threshold: bad arguments");
-            return LDPC_E_ARG;
-        }
-        *t = hard_get_threshold((const Hard*)h);
+    return handle_entry<Hard>("ldpc_hard_get_threshold", h, t != nullptr, BAD_ARGS, [&](const Hard* d) {
+        *t = hard_get_threshold(d);
         return LDPC_OK;
     });
 }
 
 int ldpc_hard_decode(ldpc_hard_t h, const uint8_t* y_dev, int64_t B, int32_t max_iter, uint32_t flags, uint8_t* xhat_dev, uint32_t* xhat_bits_dev,
                      int32_t* iters_dev, void* stream) {
-    return guarded("ldpc_hard_decode", [&]() -> int {
-        if (!h || !y_dev || (!xhat_dev && !xhat_bits_dev) || !iters_dev || B < 0) {
-            set_error("ldpc_hard_decode: bad arguments (y, iters and at least one of xhat / xhat_bits are required)");
-            return LDPC_E_ARG;
-        }
-        return hard_decode((Hard*)h, y_dev, B, max_iter, flags, xhat_dev, xhat_bits_dev, iters_dev, (hipStream_t)stream);
-    });
+    return handle_entry<Hard>("ldpc_hard_decode", h, y_dev && (xhat_dev || xhat_bits_dev) && iters_dev && B >= 0,
+                              "bad arguments (y, iters and at least one of xhat / xhat_bits are required)", [&](Hard* d) {
+                                  return hard_decode(d, y_dev, B, max_iter, flags, xhat_dev, xhat_bits_dev, iters_dev, (hipStream_t)stream);
+                              });
 }
 
 // inside the loop of main.test (src/main.py:37-45)
 int ldpc_hard_simulate(ldpc_hard_t h, int channel, double param, int codeword, uint64_t seed, uint64_t stream_id, uint64_t frame0, int64_t B,
                        int32_t max_iter, uint32_t flags, int32_t hist_bins, int64_t* counters_dev, void* stream) {
-    return guarded("ldpc_hard_simulate", [&]() -> int {
-        if (!h || !counters_dev || B < 0 || hist_bins < 0) {
-            set_error("ldpc_hard_simulate: bad arguments");
-            return LDPC_E_ARG;
-        }
-        return hard_simulate((Hard*)h, channel, param, codeword, seed, stream_id, frame0, B, max_iter, flags, hist_bins, counters_dev,
-                             (hipStream_t)stream);
-    });
+    return simulate_entry("ldpc_hard_simulate", h, hard_simulate, channel, param, codeword, seed, stream_id, frame0, B, max_iter, flags, hist_bins,
+                          counters_dev, stream);
 }
 
 int ldpc_hard_last_backend(ldpc_hard_t h, int* backend) {
-    return guarded("ldpc_hard_last_backend", [&]() -> int {
-        if (!h || !backend) return LDPC_E_ARG;
-        *backend = hard_last_backend((const Hard*)h);
+    return handle_entry<Hard>("ldpc_hard_last_backend", h, backend != nullptr, BAD_ARGS, [&](const Hard* d) {
+        *backend = hard_last_backend(d);
         return LDPC_OK;
     });
 }
 
-int ldpc_hard_info(ldpc_hard_t h, double* out4) {
-    return guarded("ldpc_hard_info", [&]() -> int {
-        if (!h || !out4) return LDPC_E_ARG;
-        hard_info((const Hard*)h, out4);
-        return LDPC_OK;
-    });
-}
+int ldpc_hard_info(ldpc_hard_t h, double* out4) { return info_entry("ldpc_hard_info", h, hard_info, out4); }
 
 // ---- layered fixed-point min-sum, LDS-resident (ldpc_lqmsa.hip) ----
 // no upstream counterpart (BPA.decode, src/bpa.py:17-63, runs the flooding schedule in floating point)
-int ldpc_lqmsa_create(ldpc_code_t code, ldpc_lqmsa_t* out) {
-    return guarded("ldpc_lqmsa_create", [&]() -> int {
-        if (!code || !out) {
-            set_error("ldpc_lqmsa_create: bad arguments");
-            return LDPC_E_ARG;
-        }
-        Lqmsa* h = nullptr;
-        LDPC_TRY(lqmsa_create((Code*)code, &h));
-        *out = (ldpc_lqmsa_t)h;
-        return LDPC_OK;
-    });
-}
+int ldpc_lqmsa_create(ldpc_code_t code, ldpc_lqmsa_t* out) { return create_entry<Lqmsa>("ldpc_lqmsa_create", code, out, lqmsa_create); }
 
-int ldpc_lqmsa_destroy(ldpc_lqmsa_t h) {
-    return guarded("ldpc_lqmsa_destroy", [&]() -> int {
-        lqmsa_destroy((Lqmsa*)h);
-        return LDPC_OK;
-    });
-}
+int ldpc_lqmsa_destroy(ldpc_lqmsa_t h) { return destroy_entry("ldpc_lqmsa_destroy", h, lqmsa_destroy); }
 
 int ldpc_lqmsa_set_fixed_point(ldpc_lqmsa_t h, int bits, int frac_bits, double scale, int offset) {
-    return guarded("ldpc_lqmsa_set_fixed_point", [&]() -> int {
-        if (!h) {
-            set_error("ldpc_lqmsa_set_fixed_point: bad arguments");
-            return LDPC_E_ARG;
-        }
-        return lqmsa_set_fixed_point((Lqmsa*)h, bits, frac_bits, scale, offset);
-    });
+    return fx_set_fixed_point_entry("ldpc_lqmsa_set_fixed_point", h, lqmsa_set_fixed_point, bits, frac_bits, scale, offset);
 }
 
 int ldpc_lqmsa_get_fixed_point(ldpc_lqmsa_t h, int* bits, int* frac_bits, double* scale, int* offset) {
-    return guarded("ldpc_lqmsa_get_fixed_point", [&]() -> int {
-        if (!h || !bits || !frac_bits || !scale || !offset) {
-            set_error("ldpc_lqmsa_get_fixed_point: a handle and four result pointers are needed");
-            return LDPC_E_ARG;
-        }
-        lqmsa_get_fixed_point((const Lqmsa*)h, bits, frac_bits, scale, offset);
-        return LDPC_OK;
-    });
+    return fx_get_fixed_point_entry("ldpc_lqmsa_get_fixed_point", h, lqmsa_get_fixed_point, bits, frac_bits, scale, offset);
 }
 
 int ldpc_lqmsa_set_layers(ldpc_lqmsa_t h, const int32_t* layer_of_check_host, int32_t m) {
-    return guarded("ldpc_lqmsa_set_layers", [&]() -> int {
-        if (!h) {
-            set_error("ldpc_lqmsa_set_layers: bad arguments");
-            return LDPC_E_ARG;
-        }
-        return lqmsa_set_layers((Lqmsa*)h, layer_of_check_host, m);
-    });
+    return fx_set_layers_entry("ldpc_lqmsa_set_layers", h, lqmsa_set_layers, layer_of_check_host, m);
 }
 
 int ldpc_lqmsa_get_layers(ldpc_lqmsa_t h, int32_t* nlayers, int32_t* layer_of_check_host) {
-    return guarded("ldpc_lqmsa_get_layers", [&]() -> int {
-        if (!h || !nlayers) {
-            set_error("ldpc_lqmsa_get_layers: a handle and a result pointer are needed");
-            return LDPC_E_ARG;
-        }
-        lqmsa_get_layers((const Lqmsa*)h, nlayers, layer_of_check_host);
-        return LDPC_OK;
-    });
+    return fx_get_layers_entry("ldpc_lqmsa_get_layers", h, lqmsa_get_layers, nlayers, layer_of_check_host);
 }
 
 int ldpc_lqmsa_decode(ldpc_lqmsa_t h, int dtype, const void* priors_dev, const uint8_t* y0_dev, int64_t B, int32_t max_iter, uint32_t flags,
                       uint8_t* xhat_dev, uint32_t* xhat_bits_dev, int32_t* iters_dev, int16_t* soft_dev, void* stream) {
-    return guarded("ldpc_lqmsa_decode", [&]() -> int {
-        if (!h || !priors_dev || (!xhat_dev && !xhat_bits_dev) || !iters_dev || B < 0) {
-            set_error("ldpc_lqmsa_decode: bad arguments (priors, iters and at least one of xhat / xhat_bits are required)");
-            return LDPC_E_ARG;
-        }
-        return lqmsa_decode((Lqmsa*)h, dtype, priors_dev, y0_dev, B, max_iter, flags, xhat_dev, xhat_bits_dev, iters_dev, soft_dev, (hipStream_t)stream);
-    });
+    return fx_decode_entry("ldpc_lqmsa_decode", h, lqmsa_decode, dtype, priors_dev, y0_dev, B, max_iter, flags, xhat_dev, xhat_bits_dev, iters_dev,
+                           soft_dev, stream);
 }
 
 // inside the loop of main.test (src/main.py:37-45)
 int ldpc_lqmsa_simulate(ldpc_lqmsa_t h, int channel, double param, int codeword, uint64_t seed, uint64_t stream_id, uint64_t frame0, int64_t B,
                         int32_t max_iter, uint32_t flags, int32_t hist_bins, int64_t* counters_dev, void* stream) {
-    return guarded("ldpc_lqmsa_simulate", [&]() -> int {
-        if (!h || !counters_dev || B < 0 || hist_bins < 0) {
-            set_error("ldpc_lqmsa_simulate: bad arguments");
-            return LDPC_E_ARG;
-        }
-        return lqmsa_simulate((Lqmsa*)h, channel, param, codeword, seed, stream_id, frame0, B, max_iter, flags, hist_bins, counters_dev,
-                              (hipStream_t)stream);
-    });
+    return simulate_entry("ldpc_lqmsa_simulate", h, lqmsa_simulate, channel, param, codeword, seed, stream_id, frame0, B, max_iter, flags, hist_bins,
+                          counters_dev, stream);
 }
 
-int ldpc_lqmsa_info(ldpc_lqmsa_t h, double* out4) {
-    return guarded("ldpc_lqmsa_info", [&]() -> int {
-        if (!h || !out4) return LDPC_E_ARG;
-        lqmsa_info((const Lqmsa*)h, out4);
-        return LDPC_OK;
-    });
-}
+int ldpc_lqmsa_info(ldpc_lqmsa_t h, double* out4) { return info_entry("ldpc_lqmsa_info", h, lqmsa_info, out4); }
 
 // ---- quasi-cyclic layered fixed-point min-sum, shift-addressed (ldpc_qc.hip) ----
 // no upstream counterpart (the reference knows no structured codes)
 int ldpc_qc_create(ldpc_code_t code, int32_t Z, ldpc_qc_t* out) {
-    return guarded("ldpc_qc_create", [&]() -> int {
-        if (!code || !out) {
-            set_error("ldpc_qc_create: bad arguments");
-            return LDPC_E_ARG;
-        }
-        Qc* h = nullptr;
-        LDPC_TRY(qc_create((Code*)code, Z, &h));
-        *out = (ldpc_qc_t)h;
-        return LDPC_OK;
-    });
+    return create_entry<Qc>("ldpc_qc_create", code, out, [&](Code* c, Qc** h) { return qc_create(c, Z, h); });
 }
 
-int ldpc_qc_destroy(ldpc_qc_t h) {
-    return guarded("ldpc_qc_destroy", [&]() -> int {
-        qc_destroy((Qc*)h);
-        return LDPC_OK;
-    });
-}
+int ldpc_qc_destroy(ldpc_qc_t h) { return destroy_entry("ldpc_qc_destroy", h, qc_destroy); }
 
 int ldpc_qc_set_fixed_point(ldpc_qc_t h, int bits, int frac_bits, double scale, int offset) {
-    return guarded("ldpc_qc_set_fixed_point", [&]() -> int {
-        if (!h) {
-            set_error("ldpc_qc_set_fixed_point: bad arguments");
-            return LDPC_E_ARG;
-        }
-        return qc_set_fixed_point((Qc*)h, bits, frac_bits, scale, offset);
-    });
+    return fx_set_fixed_point_entry("ldpc_qc_set_fixed_point", h, qc_set_fixed_point, bits, frac_bits, scale, offset);
 }
 
 int ldpc_qc_get_fixed_point(ldpc_qc_t h, int* bits, int* frac_bits, double* scale, int* offset) {
-    return guarded("ldpc_qc_get_fixed_point", [&]() -> int {
-        if (!h || !bits || !frac_bits || !scale || !offset) {
-            set_error("ldpc_qc_get_fixed_point: a handle and four result pointers are needed");
-            return LDPC_E_ARG;
-        }
-        qc_get_fixed_point((const Qc*)h, bits, frac_bits, scale, offset);
-        return LDPC_OK;
-    });
+    return fx_get_fixed_point_entry("ldpc_qc_get_fixed_point", h, qc_get_fixed_point, bits, frac_bits, scale, offset);
 }
 
 int ldpc_qc_get_base(ldpc_qc_t h, int32_t* mb, int32_t* nb, int32_t* Z, int32_t* shifts_host) {
-    return guarded("ldpc_qc_get_base", [&]() -> int {
-        if (!h || !mb || !nb || !Z) {
-            set_error("ldpc_qc_get_base: a handle and three result pointers are needed");
-            return LDPC_E_ARG;
-        }
-        qc_get_base((const Qc*)h, mb, nb, Z, shifts_host);
+    return handle_entry<Qc>("ldpc_qc_get_base", h, mb && nb && Z, "a handle and three result pointers are needed", [&](const Qc* d) {
+        qc_get_base(d, mb, nb, Z, shifts_host);
         return LDPC_OK;
     });
 }
 
 int ldpc_qc_set_order(ldpc_qc_t h, const int32_t* order_host, int32_t mb) {
-    return guarded("ldpc_qc_set_order", [&]() -> int {
-        if (!h) {
-            set_error("ldpc_qc_set_order: bad arguments");
-            return LDPC_E_ARG;
-        }
-        return qc_set_order((Qc*)h, order_host, mb);
-    });
+    return handle_entry<Qc>("ldpc_qc_set_order", h, true, BAD_ARGS, [&](Qc* d) { return qc_set_order(d, order_host, mb); });
 }
 
 int ldpc_qc_get_order(ldpc_qc_t h, int32_t* mb, int32_t* order_host) {
-    return guarded("ldpc_qc_get_order", [&]() -> int {
-        if (!h || !mb) {
-            set_error("ldpc_qc_get_order: a handle and a result pointer are needed");
-            return LDPC_E_ARG;
-        }
-        qc_get_order((const Qc*)h, mb, order_host);
+    return handle_entry<Qc>("ldpc_qc_get_order", h, mb != nullptr, "a handle and a result pointer are needed", [&](const Qc* d) {
+        qc_get_order(d, mb, order_host);
         return LDPC_OK;
     });
 }
 
 int ldpc_qc_decode(ldpc_qc_t h, int dtype, const void* priors_dev, const uint8_t* y0_dev, int64_t B, int32_t max_iter, uint32_t flags,
                    uint8_t* xhat_dev, uint32_t* xhat_bits_dev, int32_t* iters_dev, int16_t* soft_dev, void* stream) {
-    return guarded("ldpc_qc_decode", [&]() -> int {
-        if (!h || !priors_dev || (!xhat_dev && !xhat_bits_dev) || !iters_dev || B < 0) {
-            set_error("ldpc_qc_decode: bad arguments (priors, iters and at least one of xhat / xhat_bits are required)");
-            return LDPC_E_ARG;
-        }
-        return qc_decode((Qc*)h, dtype, priors_dev, y0_dev, B, max_iter, flags, xhat_dev, xhat_bits_dev, iters_dev, soft_dev, (hipStream_t)stream);
-    });
+    return fx_decode_entry("ldpc_qc_decode", h, qc_decode, dtype, priors_dev, y0_dev, B, max_iter, flags, xhat_dev, xhat_bits_dev, iters_dev, soft_dev,
+                           stream);
 }
 
 // inside the loop of main.test (src/main.py:37-45)
 int ldpc_qc_simulate(ldpc_qc_t h, int channel, double param, int codeword, uint64_t seed, uint64_t stream_id, uint64_t frame0, int64_t B,
                      int32_t max_iter, uint32_t flags, int32_t hist_bins, int64_t* counters_dev, void* stream) {
-    return guarded("ldpc_qc_simulate", [&]() -> int {
-        if (!h || !counters_dev || B < 0 || hist_bins < 0) {
-            set_error("ldpc_qc_simulate: bad arguments");
-            return LDPC_E_ARG;
-        }
-        return qc_simulate((Qc*)h, channel, param, codeword, seed, stream_id, frame0, B, max_iter, flags, hist_bins, counters_dev, (hipStream_t)stream);
-    });
+    return simulate_entry("ldpc_qc_simulate", h, qc_simulate, channel, param, codeword, seed, stream_id, frame0, B, max_iter, flags, hist_bins,
+                          counters_dev, stream);
 }
 
-int ldpc_qc_info(ldpc_qc_t h, double* out4) {
-    return guarded("ldpc_qc_info", [&]() -> int {
-        if (!h || !out4) return LDPC_E_ARG;
-        qc_info((const Qc*)h, out4);
-        return LDPC_OK;
-    });
-}
+int ldpc_qc_info(ldpc_qc_t h, double* out4) { return info_entry("ldpc_qc_info", h, qc_info, out4); }
 
 // several frames per wave for Z <= 32 (ldpc_qc.hip k_qc_pack); the prefix differs, the handle is ldpc_qc_*'s
 int ldpc_qcpack_set(ldpc_qc_t h, int32_t frames_per_wave) {
-    return guarded("ldpc_qcpack_set", [&]() -> int {
-        if (!h) {
-            set_error("ldpc_qcpack_set: bad arguments");
-            return LDPC_E_ARG;
-        }
-        return qcpack_set((Qc*)h, frames_per_wave);
-    });
+    return handle_entry<Qc>("ldpc_qcpack_set", h, true, BAD_ARGS, [&](Qc* d) { return qcpack_set(d, frames_per_wave); });
 }
 
 int ldpc_qcpack_get(ldpc_qc_t h, int32_t* frames_per_wave, int32_t* rule_pick) {
-    return guarded("ldpc_qcpack_get", [&]() -> int {
-        if (!h || !frames_per_wave || !rule_pick) {
-            set_error("ldpc_qcpack_get: a handle and two result pointers are needed");
-            return LDPC_E_ARG;
-        }
-        qcpack_get((const Qc*)h, frames_per_wave, rule_pick);
+    return handle_entry<Qc>("ldpc_qcpack_get", h, frames_per_wave && rule_pick, "a handle and two result pointers are needed", [&](const Qc* d) {
+        qcpack_get(d, frames_per_wave, rule_pick);
         return LDPC_OK;
     });
 }
 
 // ---- streaming layered fixed-point min-sum (ldpc_slq.hip) ----
 // no upstream counterpart: ldpc_lqmsa_*'s contract with the integer state in HBM tiles, for codes beyond the LDS
-int ldpc_slq_create(ldpc_code_t code, ldpc_slq_t* out) {
-    return guarded("ldpc_slq_create", [&]() -> int {
-        if (!code || !out) {
-            set_error("ldpc_slq_create: bad arguments");
-            return LDPC_E_ARG;
-        }
-        Slq* h = nullptr;
-        LDPC_TRY(slq_create((Code*)code, &h));
-        *out = (ldpc_slq_t)h;
-        return LDPC_OK;
-    });
-}
+int ldpc_slq_create(ldpc_code_t code, ldpc_slq_t* out) { return create_entry<Slq>("ldpc_slq_create", code, out, slq_create); }
 
-int ldpc_slq_destroy(ldpc_slq_t h) {
-    return guarded("ldpc_slq_destroy", [&]() -> int {
-        slq_destroy((Slq*)h);
-        return LDPC_OK;
-    });
-}
+int ldpc_slq_destroy(ldpc_slq_t h) { return destroy_entry("ldpc_slq_destroy", h, slq_destroy); }
 
 int ldpc_slq_set_fixed_point(ldpc_slq_t h, int bits, int frac_bits, double scale, int offset) {
-    return guarded("ldpc_slq_set_fixed_point", [&]() -> int {
-        if (!h) {
-            set_error("ldpc_slq_set_fixed_point: bad arguments");
-            return LDPC_E_ARG;
-        }
-        return slq_set_fixed_point((Slq*)h, bits, frac_bits, scale, offset);
-    });
+    return fx_set_fixed_point_entry("ldpc_slq_set_fixed_point", h, slq_set_fixed_point, bits, frac_bits, scale, offset);
 }
 
 int ldpc_slq_get_fixed_point(ldpc_slq_t h, int* bits, int* frac_bits, double* scale, int* offset) {
-    return guarded("ldpc_slq_get_fixed_point", [&]() -> int {
-        if (!h || !bits || !frac_bits || !scale || !offset) {
-            set_error("ldpc_slq_get_fixed_point: a handle and four result pointers are needed");
-            return LDPC_E_ARG;
-        }
-        slq_get_fixed_point((const Slq*)h, bits, frac_bits, scale, offset);
-        return LDPC_OK;
-    });
+    return fx_get_fixed_point_entry("ldpc_slq_get_fixed_point", h, slq_get_fixed_point, bits, frac_bits, scale, offset);
 }
 
 int ldpc_slq_set_layers(ldpc_slq_t h, const int32_t* layer_of_check_host, int32_t m) {
-    return guarded("ldpc_slq_set_layers", [&]() -> int {
-        if (!h) {
-            set_error("ldpc_slq_set_layers: bad arguments");
-            return LDPC_E_ARG;
-        }
-        return slq_set_layers((Slq*)h, layer_of_check_host, m);
-    });
+    return fx_set_layers_entry("ldpc_slq_set_layers", h, slq_set_layers, layer_of_check_host, m);
 }
 
 int ldpc_slq_get_layers(ldpc_slq_t h, int32_t* nlayers, int32_t* layer_of_check_host) {
-    return guarded("ldpc_slq_get_layers", [&]() -> int {
-        if (!h || !nlayers) {
-            set_error("ldpc_slq_get_layers: a handle and a result pointer are needed");
-            return LDPC_E_ARG;
-        }
-        slq_get_layers((const Slq*)h, nlayers, layer_of_check_host);
-        return LDPC_OK;
-    });
+    return fx_get_layers_entry("ldpc_slq_get_layers", h, slq_get_layers, nlayers, layer_of_check_host);
 }
 
 int ldpc_slq_decode(ldpc_slq_t h, int dtype, const void* priors_dev, const uint8_t* y0_dev, int64_t B, int32_t max_iter, uint32_t flags,
                     uint8_t* xhat_dev, uint32_t* xhat_bits_dev, int32_t* iters_dev, int16_t* soft_dev, void* stream) {
-    return guarded("ldpc_slq_decode", [&]() -> int {
-        if (!h || !priors_dev || (!xhat_dev && !xhat_bits_dev) || !iters_dev || B < 0) {
-            set_error("ldpc_slq_decode: bad arguments (priors, iters and at least one of xhat / xhat_bits are required)");
-            return LDPC_E_ARG;
-        }
-        return slq_decode((Slq*)h, dtype, priors_dev, y0_dev, B, max_iter, flags, xhat_dev, xhat_bits_dev, iters_dev, soft_dev, (hipStream_t)stream);
-    });
+    return fx_decode_entry("ldpc_slq_decode", h, slq_decode, dtype, priors_dev, y0_dev, B, max_iter, flags, xhat_dev, xhat_bits_dev, iters_dev, soft_dev,
+                           stream);
 }
 
 // inside the loop of main.test (src/main.py:37-45)
 int ldpc_slq_simulate(ldpc_slq_t h, int channel, double param, int codeword, uint64_t seed, uint64_t stream_id, uint64_t frame0, int64_t B,
                       int32_t max_iter, uint32_t flags, int32_t hist_bins, int64_t* counters_dev, void* stream) {
-    return guarded("ldpc_slq_simulate", [&]() -> int {
-        if (!h || !counters_dev || B < 0 || hist_bins < 0) {
-            set_error("ldpc_slq_simulate: bad arguments");
-            return LDPC_E_ARG;
-        }
-        return slq_simulate((Slq*)h, channel, param, codeword, seed, stream_id, frame0, B, max_iter, flags, hist_bins, counters_dev, (hipStream_t)stream);
-    });
+    return simulate_entry("ldpc_slq_simulate", h, slq_simulate, channel, param, codeword, seed, stream_id, frame0, B, max_iter, flags, hist_bins,
+                          counters_dev, stream);
 }
 
-int ldpc_slq_info(ldpc_slq_t h, double* out4) {
-    return guarded("ldpc_slq_info", [&]() -> int {
-        if (!h || !out4) return LDPC_E_ARG;
-        slq_info((const Slq*)h, out4);
-        return LDPC_OK;
-    });
-}
+int ldpc_slq_info(ldpc_slq_t h, double* out4) { return info_entry("ldpc_slq_info", h, slq_info, out4); }
 
 int ldpc_slq_profile(ldpc_slq_t h, int enable, double* ms3, int64_t* launches3, int reset) {
-    return guarded("ldpc_slq_profile", [&]() -> int {
-        if (!h) return LDPC_E_ARG;
-        slq_profile((Slq*)h, enable, ms3, launches3, reset);
+    return handle_entry<Slq>("ldpc_slq_profile", h, true, BAD_ARGS, [&](Slq* d) {
+        slq_profile(d, enable, ms3, launches3, reset);
         return LDPC_OK;
     });
 }
 
 int ldpc_slq_last_stats(ldpc_slq_t h, int32_t* out3) {
-    return guarded("ldpc_slq_last_stats", [&]() -> int {
-        if (!h || !out3) return LDPC_E_ARG;
-        slq_last_stats((const Slq*)h, out3);
+    return handle_entry<Slq>("ldpc_slq_last_stats", h, out3 != nullptr, BAD_ARGS, [&](const Slq* d) {
+        slq_last_stats(d, out3);
         return LDPC_OK;
     });
 }
 
 // ---- ADMM LP decoder (ldpc_admm.hip) ----
-int ldpc_admm_create(ldpc_code_t code, ldpc_admm_t* out) {
-    return guarded("ldpc_admm_create", [&]() -> int {
-        if (!code || !out) {
-            set_error("ldpc_admm_create: bad arguments");
-            return LDPC_E_ARG;
-        }
-        AdmmDecoder* d = nullptr;
-        LDPC_TRY(admm_create((Code*)code, &d));
-        *out = (ldpc_admm_t)d;
-        return LDPC_OK;
-    });
-}
+int ldpc_admm_create(ldpc_code_t code, ldpc_admm_t* out) { return create_entry<AdmmDecoder>("ldpc_admm_create", code, out, admm_create); }
 
-int ldpc_admm_destroy(ldpc_admm_t h) {
-    return guarded("ldpc_admm_destroy", [&]() -> int {
-        admm_destroy((AdmmDecoder*)h);
-        return LDPC_OK;
-    });
-}
+int ldpc_admm_destroy(ldpc_admm_t h) { return destroy_entry("ldpc_admm_destroy", h, admm_destroy); }
 
 int ldpc_admm_last_backend(ldpc_admm_t h, int* backend) {
-    return guarded("ldpc_admm_last_backend", [&]() -> int {
-        if (!h || !backend) return LDPC_E_ARG;
-        *backend = admm_last_backend((AdmmDecoder*)h);
+    return handle_entry<AdmmDecoder>("ldpc_admm_last_backend", h, backend != nullptr, BAD_ARGS, [&](const AdmmDecoder* d) {
+        *backend = admm_last_backend(d);
         return LDPC_OK;
     });
 }
 
 int ldpc_admm_last_repacks(ldpc_admm_t h, int* repacks) {
-    return guarded("ldpc_admm_last_repacks", [&]() -> int {
-        if (!h || !repacks) return LDPC_E_ARG;
-        *repacks = admm_last_repacks((AdmmDecoder*)h);
+    return handle_entry<AdmmDecoder>("ldpc_admm_last_repacks", h, repacks != nullptr, BAD_ARGS, [&](const AdmmDecoder* d) {
+        *repacks = admm_last_repacks(d);
         return LDPC_OK;
     });
 }
 
 int ldpc_admm_decode(ldpc_admm_t h, const double* gamma_dev, int64_t B, double mu, double eps, int32_t max_iter, double* x_dev,
                      int32_t* iters_dev, uint8_t* converged_dev, void* stream) {
-    return guarded("ldpc_admm_decode", [&]() -> int {
-        if (!h || !gamma_dev || !x_dev || !iters_dev || B < 0) {
-            set_error("ldpc_admm_decode: bad arguments");
-            return LDPC_E_ARG;
-        }
-        return admm_decode((AdmmDecoder*)h, gamma_dev, B, mu, eps, max_iter, x_dev, iters_dev, converged_dev, (hipStream_t)stream);
+    return handle_entry<AdmmDecoder>("ldpc_admm_decode", h, gamma_dev && x_dev && iters_dev && B >= 0, BAD_ARGS, [&](AdmmDecoder* d) {
+        return admm_decode(d, gamma_dev, B, mu, eps, max_iter, x_dev, iters_dev, converged_dev, (hipStream_t)stream);
     });
 }
 

@@ -19,6 +19,7 @@
 #include <new>
 
 #include "ldpc_bec_ml.hpp"
+#include "ldpc_sim.hpp"
 #include "ldpc_rng.hpp"
 
 namespace ldpc {
@@ -27,7 +28,6 @@ struct BecMl {
     Code* code = nullptr;
     ldpc_decoder_t peel = nullptr;  // the erasure decoder whose stopping-set exit leaves the residual set
     int num_cu = 0;
-    bool odd_check = false;         // some check has odd degree: the all-ones word is no codeword
     DevBuf bits, era, iters, y, ctr, list, ovf, nul;
 };
 
@@ -269,7 +269,6 @@ int bec_ml_create(Code* code, BecMl** out) {
     LDPC_HIP_TRY(hipSetDevice(code->device));
     BecMl* h = new BecMl();
     h->code = code;
-    for (int32_t c = 0; c < code->m; ++c) h->odd_check |= ((code->row_ptr[c + 1] - code->row_ptr[c]) & 1) != 0;
     hipDeviceProp_t prop;
     int rc = LDPC_OK;
     if (hipGetDeviceProperties(&prop, code->device) != hipSuccess ||
@@ -354,25 +353,19 @@ int bec_ml_decode(BecMl* h, const uint8_t* y, int64_t B, uint64_t seed, uint64_t
 
 int bec_ml_simulate(BecMl* h, double param, int codeword, uint64_t seed, uint64_t stream_id, uint64_t frame0, int64_t B, int64_t* counters,
                     hipStream_t st) {
-    if (codeword != 0 && codeword != 1) {
-        set_error("ldpc_bec_ml_simulate: codeword must be 0 or 1");
-        return LDPC_E_ARG;
-    }
-    if (codeword == 1 && h->odd_check) {
-        set_error("ldpc_bec_ml_simulate: codeword 1: the all-ones word is no codeword of this code (a check has odd degree)");
-        return LDPC_E_ARG;
-    }
     const int n = h->code->n;
-    LDPC_HIP_TRY(hipSetDevice(h->code->device));
-    LDPC_TRY(h->y.reserve((size_t)(B < CHUNK ? B : CHUNK) * n));
-    LDPC_TRY(h->nul.reserve((size_t)CHUNK * sizeof(int32_t)));
-    for (int64_t b0 = 0; b0 < B; b0 += CHUNK) {
-        const int64_t nb = B - b0 < CHUNK ? B - b0 : CHUNK;
-        LDPC_TRY(channel_generate(CH_BEC, DT_F32, param, codeword, seed, stream_id, frame0 + (uint64_t)b0, nb, n, nullptr, (uint8_t*)h->y.p, st));
-        LDPC_TRY(peel_solve(h, (const uint8_t*)h->y.p, nb, seed, stream_id, frame0 + (uint64_t)b0, (int32_t*)h->nul.p, st));
-        LDPC_TRY(count_errors_bits((const uint32_t*)h->bits.p, nullptr, nullptr, codeword, nullptr, nb, n, 0, counters, st));
-    }
-    return LDPC_OK;
+    return sim_passes(
+        SimCall{"ldpc_bec_ml_simulate", h->code, codeword, frame0, B, 0, counters, st}, nullptr, CHUNK,
+        [&](int64_t cap) -> int {
+            LDPC_TRY(h->y.reserve((size_t)cap * n));
+            return h->nul.reserve((size_t)cap * sizeof(int32_t));
+        },
+        [&](uint64_t first, int64_t nb, const uint32_t*& bits, const int32_t*&) -> int {
+            LDPC_TRY(channel_generate(CH_BEC, DT_F32, param, codeword, seed, stream_id, first, nb, n, nullptr, (uint8_t*)h->y.p, st));
+            LDPC_TRY(peel_solve(h, (const uint8_t*)h->y.p, nb, seed, stream_id, first, (int32_t*)h->nul.p, st));
+            bits = (const uint32_t*)h->bits.p;  // (reserved by peel_solve)
+            return LDPC_OK;
+        });
 }
 
 }  // namespace ldpc

@@ -103,6 +103,7 @@ struct Code {
     int32_t m = 0, n = 0;
     int64_t E = 0;
     int32_t max_dc = 0, min_dc = 0, max_dv = 0, min_dv = 0;
+    bool odd_check = false;  // some check has odd degree (has_odd_check, ldpc_sim.hpp)
     // device arrays
     int32_t* d_row_ptr = nullptr;   // [m+1]
     int32_t* d_edge_var = nullptr;  // [E]  variable of edge k (row-major edge order)

@@ -26,6 +26,7 @@
 
 #include "ldpc_bec_planes.hpp"
 #include "ldpc_hard.hpp"
+#include "ldpc_sim.hpp"
 
 namespace ldpc {
 
@@ -35,7 +36,6 @@ struct Hard {
     bool use_lds = false;   // what it resolved to
     int t = 0;              // threshold parameter (ldpc_hard_set_threshold)
     int last_backend = BK_STREAM;
-    bool odd_check = false;
     int num_cu = 0, slabs_per_cu = 0;
     int64_t lds_bytes = 0;   // the LDS-fit rule's left side
     bool tab_lds = false;    // measurement variant (LDPC_HARD_TABLES=lds): graph tables as 16-bit words in the LDS
@@ -44,8 +44,8 @@ struct Hard {
     DevBuf chk_of_pos;  // [E] check of variable-major position p
     DevBuf state;       // streaming planes
     DevBuf ctl;         // streaming: live [S][64], unsat [S][64], stlive [S]; then 2 words: live supertiles, slab dispenser
-    DevBuf sim_y, sim_pri, sim_bits, sim_iters;  // staging of ldpc_hard_simulate
-    uint32_t* pinned = nullptr;                  // host poll word
+    SimStage sim;       // staging of ldpc_hard_simulate
+    uint32_t* pinned = nullptr;  // host poll word
 };
 
 namespace {
@@ -398,7 +398,6 @@ int hard_create(Code* code, int backend, Hard** out) {
     h->lds_bytes = need;
     h->use_lds = fits && backend != BK_STREAM;
     h->last_backend = h->use_lds ? BK_FUSED : BK_STREAM;
-    for (int32_t c = 0; c < code->m; ++c) h->odd_check |= ((code->row_ptr[c + 1] - code->row_ptr[c]) & 1) != 0;
     std::vector<int32_t> vpos((size_t)code->E), chk((size_t)code->E);
     for (int32_t v = 0; v < code->n; ++v)
         for (int32_t p = code->col_ptr[v]; p < code->col_ptr[v + 1]; ++p) {
@@ -438,7 +437,8 @@ int hard_create(Code* code, int backend, Hard** out) {
 
 void hard_destroy(Hard* h) {
     if (!h) return;
-    for (DevBuf* b : {&h->vpos, &h->chk_of_pos, &h->state, &h->ctl, &h->sim_y, &h->sim_pri, &h->sim_bits, &h->sim_iters}) b->release();
+    for (DevBuf* b : {&h->vpos, &h->chk_of_pos, &h->state, &h->ctl}) b->release();
+    h->sim.release();
     if (h->pinned) (void)hipHostFree(h->pinned);
     delete h;
 }
@@ -503,48 +503,31 @@ int hard_decode(Hard* h, const uint8_t* y, int64_t B, int32_t max_iter, uint32_t
 
 int hard_simulate(Hard* h, int channel, double param, int codeword, uint64_t seed, uint64_t stream_id, uint64_t frame0, int64_t B, int32_t max_iter,
                   uint32_t flags, int32_t hist_bins, int64_t* counters, hipStream_t st) {
-    if (channel != CH_BIAWGN && channel != CH_BSC) {
-        set_error("ldpc_hard_simulate: LDPC_CH_BSC or LDPC_CH_BIAWGN (a hard-decision decoder has no erasures to work on)");
-        return LDPC_E_ARG;
-    }
-    if (codeword != 0 && codeword != 1) {
-        set_error("ldpc_hard_simulate: codeword must be 0 or 1");
-        return LDPC_E_ARG;
-    }
-    if (codeword == 1 && h->odd_check) {
-        set_error("ldpc_hard_simulate: codeword 1: the all-ones word is no codeword of this code (a check has odd degree)");
-        return LDPC_E_ARG;
-    }
     if (max_iter <= 0) {
         set_error("ldpc_hard_simulate: max_iter must be >= 1 (got %d)", max_iter);
         return LDPC_E_ARG;
     }
-    const size_t n = (size_t)h->code->n, W = (n + 31) / 32;
-    // the received bytes of one pass: about 256 MiB, whole supertiles, at most 2^17 frames
-    int64_t cap = (int64_t)((((size_t)256 << 20) / n) / HARD_SUPER * HARD_SUPER);
-    cap = std::min<int64_t>(std::max<int64_t>(cap, HARD_SUPER), (int64_t)1 << 17);
-    cap = std::min(cap, std::max<int64_t>(B, 1));
-    LDPC_HIP_TRY(hipSetDevice(h->code->device));
-    LDPC_TRY(h->sim_y.reserve((size_t)cap * n));
-    if (channel == CH_BIAWGN) LDPC_TRY(h->sim_pri.reserve((size_t)cap * n * sizeof(float)));
-    LDPC_TRY(h->sim_bits.reserve((size_t)cap * W * 4));
-    LDPC_TRY(h->sim_iters.reserve((size_t)cap * sizeof(int32_t)));
-    uint8_t* y = (uint8_t*)h->sim_y.p;
-    for (int64_t b0 = 0; b0 < B; b0 += cap) {
-        const int64_t nb = std::min(cap, B - b0);
-        if (channel == CH_BSC) {
-            LDPC_TRY(channel_generate(CH_BSC, DT_F32, param, codeword, seed, stream_id, frame0 + (uint64_t)b0, nb, (int32_t)n, nullptr, y, st));
-        } else {
-            LDPC_TRY(channel_generate(CH_BIAWGN, DT_F32, param, codeword, seed, stream_id, frame0 + (uint64_t)b0, nb, (int32_t)n, h->sim_pri.p, nullptr, st));
-            const int64_t total = nb * (int64_t)n;
-            hipLaunchKernelGGL(k_hard_slice, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, (const float*)h->sim_pri.p, total, y);
-            LDPC_HIP_TRY(hipGetLastError());
-        }
-        LDPC_TRY(hard_decode(h, y, nb, max_iter, flags, nullptr, (uint32_t*)h->sim_bits.p, (int32_t*)h->sim_iters.p, st));
-        LDPC_TRY(count_errors_bits((const uint32_t*)h->sim_bits.p, nullptr, nullptr, codeword, (const int32_t*)h->sim_iters.p, nb, (int32_t)n, hist_bins,
-                                   counters, st));
-    }
-    return LDPC_OK;
+    const bool awgn = channel == CH_BIAWGN;
+    const int32_t n = h->code->n;
+    SimStage& s = h->sim;
+    // the received bytes of one pass: about 256 MiB, whole supertiles
+    const int64_t cap = std::max<int64_t>((int64_t)((((size_t)256 << 20) / (size_t)n) / HARD_SUPER * HARD_SUPER), HARD_SUPER);
+    return sim_passes(
+        SimCall{"ldpc_hard_simulate", h->code, codeword, frame0, B, hist_bins, counters, st},
+        awgn || channel == CH_BSC ? nullptr : "LDPC_CH_BSC or LDPC_CH_BIAWGN (a hard-decision decoder has no erasures to work on)", cap,
+        [&](int64_t frames) -> int { return s.reserve(frames, (size_t)n, awgn, true); },
+        [&](uint64_t first, int64_t nb, const uint32_t*& bits, const int32_t*& iters) -> int {
+            uint8_t* y = (uint8_t*)s.y.p;
+            LDPC_TRY(channel_generate(channel, DT_F32, param, codeword, seed, stream_id, first, nb, n, awgn ? s.pri.p : nullptr, awgn ? nullptr : y, st));
+            if (awgn) {  // the word sliced at prior < 0
+                const int64_t total = nb * (int64_t)n;
+                hipLaunchKernelGGL(k_hard_slice, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, (const float*)s.pri.p, total, y);
+                LDPC_HIP_TRY(hipGetLastError());
+            }
+            bits = (const uint32_t*)s.bits.p;
+            iters = (const int32_t*)s.iters.p;
+            return hard_decode(h, y, nb, max_iter, flags, nullptr, (uint32_t*)s.bits.p, (int32_t*)s.iters.p, st);
+        });
 }
 
 }  // namespace ldpc

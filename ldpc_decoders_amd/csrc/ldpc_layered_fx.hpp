@@ -25,6 +25,7 @@
 
 #include "ldpc_cn.hpp"
 #include "ldpc_common.hpp"
+#include "ldpc_sim.hpp"
 
 namespace ldpc {
 
@@ -208,13 +209,6 @@ inline int fx_check_degrees(const char* entry, const char* rows, int min_dc, int
     return LDPC_OK;
 }
 
-// does a check of the code have odd degree (then the all-ones word is no codeword)
-inline bool fx_odd_check(const Code* code) {
-    bool odd = false;
-    for (int32_t c = 0; c < code->m; ++c) odd |= ((code->row_ptr[c + 1] - code->row_ptr[c]) & 1) != 0;
-    return odd;
-}
-
 // *_decode: the arguments every family refuses
 inline int fx_check_decode(const char* entry, int dtype, uint32_t flags, int64_t B) {
     if (dtype != DT_F32 && dtype != DT_F64) {
@@ -232,46 +226,24 @@ inline int fx_check_decode(const char* entry, int dtype, uint32_t flags, int64_t
     return LDPC_OK;
 }
 
-// staging of *_simulate
-struct SimStage {
-    DevBuf pri, y, bits, iters;
-    void release() {
-        for (DevBuf* b : {&pri, &y, &bits, &iters}) b->release();
-    }
-};
-
-// *_simulate: passes of at most `cap` frames (the family's bound on the fp32 priors of one pass), each generate -> decode -> count;
-// decode(priors, y, frames, bits, iters) is the family's *_decode on fp32 priors.
+// *_simulate: the pass loop of ldpc_sim.hpp on fp32 priors, in passes of at most `cap` frames (the family's bound on the priors of one pass);
+// decode(priors, y, frames, bits, iters) is the family's *_decode.
 template <class Decode>
-int fx_simulate(const char* entry, const Code* code, bool odd_check, SimStage& s, int64_t cap, int channel, double param, int codeword, uint64_t seed,
-                uint64_t stream_id, uint64_t frame0, int64_t B, int32_t hist_bins, int64_t* counters, hipStream_t st, Decode&& decode) {
-    if (channel != CH_BIAWGN && channel != CH_BSC) {
-        set_error("%s: LDPC_CH_BIAWGN or LDPC_CH_BSC (min-sum has no magnitudes to work on over the erasure channel)", entry);
-        return LDPC_E_ARG;
-    }
-    if (codeword != 0 && codeword != 1) {
-        set_error("%s: codeword must be 0 or 1", entry);
-        return LDPC_E_ARG;
-    }
-    if (codeword == 1 && odd_check) {
-        set_error("%s: codeword 1: the all-ones word is no codeword of this code (a check has odd degree)", entry);
-        return LDPC_E_ARG;
-    }
-    const size_t n = (size_t)code->n, W = (n + 31) / 32;
-    cap = std::min(std::min<int64_t>(cap, (int64_t)1 << 17), std::max<int64_t>(B, 1));  // at most 2^17 frames a pass
-    LDPC_HIP_TRY(hipSetDevice(code->device));
-    LDPC_TRY(s.pri.reserve((size_t)cap * n * sizeof(float)));
-    if (channel == CH_BSC) LDPC_TRY(s.y.reserve((size_t)cap * n));
-    LDPC_TRY(s.bits.reserve((size_t)cap * W * 4));
-    LDPC_TRY(s.iters.reserve((size_t)cap * sizeof(int32_t)));
-    uint8_t* y = channel == CH_BSC ? (uint8_t*)s.y.p : nullptr;  // over the BSC the received word takes the iteration-0 check, as upstream
-    for (int64_t b0 = 0; b0 < B; b0 += cap) {
-        const int64_t nb = std::min(cap, B - b0);
-        LDPC_TRY(channel_generate(channel, DT_F32, param, codeword, seed, stream_id, frame0 + (uint64_t)b0, nb, (int32_t)n, s.pri.p, y, st));
-        LDPC_TRY(decode(s.pri.p, y, nb, (uint32_t*)s.bits.p, (int32_t*)s.iters.p));
-        LDPC_TRY(count_errors_bits((const uint32_t*)s.bits.p, nullptr, nullptr, codeword, (const int32_t*)s.iters.p, nb, (int32_t)n, hist_bins, counters, st));
-    }
-    return LDPC_OK;
+int fx_simulate(const char* entry, const Code* code, SimStage& s, int64_t cap, int channel, double param, int codeword, uint64_t seed, uint64_t stream_id,
+                uint64_t frame0, int64_t B, int32_t hist_bins, int64_t* counters, hipStream_t st, Decode&& decode) {
+    const bool llr = channel == CH_BIAWGN || channel == CH_BSC;
+    const bool bsc = channel == CH_BSC;  // over the BSC the received word takes the iteration-0 check, as upstream
+    return sim_passes(
+        SimCall{entry, code, codeword, frame0, B, hist_bins, counters, st},
+        llr ? nullptr : "LDPC_CH_BIAWGN or LDPC_CH_BSC (min-sum has no magnitudes to work on over the erasure channel)", cap,
+        [&](int64_t frames) -> int { return s.reserve(frames, (size_t)code->n, true, bsc); },
+        [&](uint64_t first, int64_t nb, const uint32_t*& bits, const int32_t*& iters) -> int {
+            uint8_t* y = bsc ? (uint8_t*)s.y.p : nullptr;
+            LDPC_TRY(channel_generate(channel, DT_F32, param, codeword, seed, stream_id, first, nb, code->n, s.pri.p, y, st));
+            bits = (const uint32_t*)s.bits.p;
+            iters = (const int32_t*)s.iters.p;
+            return decode(s.pri.p, y, nb, (uint32_t*)s.bits.p, (int32_t*)s.iters.p);
+        });
 }
 
 // the LDS decoders' bound on one pass of fp32 priors: about 256 MiB

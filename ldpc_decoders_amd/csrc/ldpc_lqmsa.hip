@@ -27,7 +27,6 @@ namespace ldpc {
 struct Lqmsa {
     Code* code = nullptr;
     FixedPoint fx;
-    bool odd_check = false;
     int num_cu = 0, nw = 1, frames_per_cu = 0, row_bytes = 8;
     int64_t lds_bytes = 0;
     std::vector<int32_t> layer_of_check, layer_start;
@@ -212,7 +211,6 @@ int lqmsa_create(Code* code, Lqmsa** out) {
     h->code = code;
     h->lds_bytes = need;
     h->row_bytes = lqmsa_row_bytes(code->max_dc);
-    h->odd_check = fx_odd_check(code);
     const int64_t fit = LQMSA_LDS_BYTES / need;
     h->nw = fx_waves(lqmsa_waves(fit), "LDPC_LQMSA_NW");
     h->frames_per_cu = fx_frames_per_cu(fit, h->nw);
@@ -291,7 +289,7 @@ int lqmsa_decode(Lqmsa* h, int dtype, const void* priors, const uint8_t* y0, int
 
 int lqmsa_simulate(Lqmsa* h, int channel, double param, int codeword, uint64_t seed, uint64_t stream_id, uint64_t frame0, int64_t B, int32_t max_iter,
                    uint32_t flags, int32_t hist_bins, int64_t* counters, hipStream_t st) {
-    return fx_simulate("ldpc_lqmsa_simulate", h->code, h->odd_check, h->sim, fx_lds_sim_cap(h->code->n), channel, param, codeword, seed, stream_id, frame0, B,
+    return fx_simulate("ldpc_lqmsa_simulate", h->code, h->sim, fx_lds_sim_cap(h->code->n), channel, param, codeword, seed, stream_id, frame0, B,
                        hist_bins, counters, st, [&](const void* pri, const uint8_t* y, int64_t nb, uint32_t* bits, int32_t* iters) {
                            return lqmsa_decode(h, DT_F32, pri, y, nb, max_iter, flags, nullptr, bits, iters, nullptr, st);
                        });

@@ -19,6 +19,7 @@
 #include <new>
 
 #include "ldpc_osd.hpp"
+#include "ldpc_sim.hpp"
 
 namespace ldpc {
 
@@ -26,7 +27,6 @@ struct Osd {
     Code* code = nullptr;
     int num_cu = 0, rank = 0, groups = 0;  // rank(H); workgroups of k_osd_solve = num_cu * (slabs that fit one CU's LDS)
     int64_t slab = 0;                      // bytes of LDS one frame takes
-    bool odd_check = false;                // some check has odd degree: the all-ones word is no codeword
     DevBuf ctr, list, marg, bits, pri, y, xh, iters, pick;
 };
 
@@ -389,7 +389,6 @@ int osd_create(Code* code, Osd** out) {
     h->code = code;
     h->slab = need;
     h->rank = host_rank(code);
-    for (int32_t c = 0; c < code->m; ++c) h->odd_check |= ((code->row_ptr[c + 1] - code->row_ptr[c]) & 1) != 0;
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, code->device) != hipSuccess ||
         hipFuncSetAttribute((const void*)k_osd_solve<float>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)OSD_LDS_BYTES) != hipSuccess ||
@@ -469,40 +468,31 @@ int osd_simulate(Osd* h, ldpc_decoder_t dec, int channel, double param, int code
                  int32_t max_iter, uint32_t flags, int32_t order, int64_t depth, int32_t hist_bins, int64_t* counters, hipStream_t st) {
     LDPC_TRY(check_order("ldpc_osd_simulate", order, depth));
     LDPC_TRY(check_decoder("ldpc_osd_simulate", h, (const Decoder*)dec));
-    if (channel != CH_BIAWGN && channel != CH_BSC) {
-        set_error("ldpc_osd_simulate: LDPC_CH_BIAWGN or LDPC_CH_BSC (over the erasure channel ldpc_bec_ml_* is the ML decoder)");
-        return LDPC_E_ARG;
-    }
-    if (codeword != 0 && codeword != 1) {
-        set_error("ldpc_osd_simulate: codeword must be 0 or 1");
-        return LDPC_E_ARG;
-    }
-    if (codeword == 1 && h->odd_check) {
-        set_error("ldpc_osd_simulate: codeword 1: the all-ones word is no codeword of this code (a check has odd degree)");
-        return LDPC_E_ARG;
-    }
     if (LDPC_FLAG_PRIOR_GRID_OF(flags) >= 0) {
         set_error("ldpc_osd_simulate: no prior grid (the exact-in-fp32 mode belongs to ldpc_simulate)");
         return LDPC_E_UNSUPPORTED;
     }
+    const bool bsc = channel == CH_BSC;
     const int dtype = ((const Decoder*)dec)->dtype;
     const size_t n = (size_t)h->code->n, esz = dtype == DT_F64 ? 8 : 4;
-    const int64_t cap = B < CHUNK ? B : CHUNK;
-    LDPC_HIP_TRY(hipSetDevice(h->code->device));
-    LDPC_TRY(h->pri.reserve((size_t)cap * n * esz));
-    if (channel == CH_BSC) LDPC_TRY(h->y.reserve((size_t)cap * n));
-    LDPC_TRY(h->xh.reserve((size_t)cap * n));
-    LDPC_TRY(h->iters.reserve((size_t)cap * sizeof(int32_t)));
-    LDPC_TRY(h->pick.reserve((size_t)cap * sizeof(int32_t)));
-    for (int64_t b0 = 0; b0 < B; b0 += CHUNK) {
-        const int64_t nb = B - b0 < CHUNK ? B - b0 : CHUNK;
-        uint8_t* y = channel == CH_BSC ? (uint8_t*)h->y.p : nullptr;
-        LDPC_TRY(channel_generate(channel, dtype, param, codeword, seed, stream_id, frame0 + (uint64_t)b0, nb, (int32_t)n, h->pri.p, y, st));
-        LDPC_TRY(bp_solve(h, dec, h->pri.p, y, nb, max_iter, flags, order, depth, (uint8_t*)h->xh.p, (int32_t*)h->iters.p, (int32_t*)h->pick.p, st));
-        LDPC_TRY(count_errors_bits((const uint32_t*)h->bits.p, nullptr, nullptr, codeword, (const int32_t*)h->iters.p, nb, (int32_t)n, hist_bins,
-                                   counters, st));
-    }
-    return LDPC_OK;
+    return sim_passes(
+        SimCall{"ldpc_osd_simulate", h->code, codeword, frame0, B, hist_bins, counters, st},
+        bsc || channel == CH_BIAWGN ? nullptr : "LDPC_CH_BIAWGN or LDPC_CH_BSC (over the erasure channel ldpc_bec_ml_* is the ML decoder)", CHUNK,
+        [&](int64_t cap) -> int {
+            LDPC_TRY(h->pri.reserve((size_t)cap * n * esz));
+            if (bsc) LDPC_TRY(h->y.reserve((size_t)cap * n));
+            LDPC_TRY(h->xh.reserve((size_t)cap * n));
+            LDPC_TRY(h->iters.reserve((size_t)cap * sizeof(int32_t)));
+            return h->pick.reserve((size_t)cap * sizeof(int32_t));
+        },
+        [&](uint64_t first, int64_t nb, const uint32_t*& bits, const int32_t*& iters) -> int {
+            uint8_t* y = bsc ? (uint8_t*)h->y.p : nullptr;
+            LDPC_TRY(channel_generate(channel, dtype, param, codeword, seed, stream_id, first, nb, (int32_t)n, h->pri.p, y, st));
+            LDPC_TRY(bp_solve(h, dec, h->pri.p, y, nb, max_iter, flags, order, depth, (uint8_t*)h->xh.p, (int32_t*)h->iters.p, (int32_t*)h->pick.p, st));
+            bits = (const uint32_t*)h->bits.p;  // (reserved by bp_solve)
+            iters = (const int32_t*)h->iters.p;
+            return LDPC_OK;
+        });
 }
 
 }  // namespace ldpc

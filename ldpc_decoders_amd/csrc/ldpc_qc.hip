@@ -29,7 +29,6 @@ struct Qc {
     Code* code = nullptr;
     int32_t Z = 1, mb = 0, nb = 0, dc_max = 0;
     FixedPoint fx;
-    bool odd_check = false;
     int num_cu = 0, nw = 1, frames_per_cu = 0, row_bytes = 8;
     int64_t lds_bytes = 0;
     int pack = 1, pack_grid = 0;  // frames per wave (>= 2: k_qc_pack); LDPC_QC_PACK_GRID, 0 = no cap on the packed kernel's grid
@@ -391,7 +390,6 @@ int qc_create(Code* code, int32_t Z, Qc** out) {
         const int32_t d = h->row_ptr[(size_t)i + 1] - h->row_ptr[(size_t)i];
         dmin = std::min(dmin, d);
         h->dc_max = std::max(h->dc_max, d);
-        h->odd_check |= (d & 1) != 0;
     }
     const int64_t need = lqmsa_lds_bytes(code->m, code->n, code->E, h->dc_max);
     rc = fx_check_degrees("ldpc_qc_create", "block row", dmin, code->max_dv, LQMSA_MAX_DV);
@@ -557,7 +555,7 @@ int qc_decode(Qc* h, int dtype, const void* priors, const uint8_t* y0, int64_t B
 
 int qc_simulate(Qc* h, int channel, double param, int codeword, uint64_t seed, uint64_t stream_id, uint64_t frame0, int64_t B, int32_t max_iter,
                 uint32_t flags, int32_t hist_bins, int64_t* counters, hipStream_t st) {
-    return fx_simulate("ldpc_qc_simulate", h->code, h->odd_check, h->sim, fx_lds_sim_cap(h->code->n), channel, param, codeword, seed, stream_id, frame0, B,
+    return fx_simulate("ldpc_qc_simulate", h->code, h->sim, fx_lds_sim_cap(h->code->n), channel, param, codeword, seed, stream_id, frame0, B,
                        hist_bins, counters, st, [&](const void* pri, const uint8_t* y, int64_t nb, uint32_t* bits, int32_t* iters) {
                            return qc_decode(h, DT_F32, pri, y, nb, max_iter, flags, nullptr, bits, iters, nullptr, st);
                        });

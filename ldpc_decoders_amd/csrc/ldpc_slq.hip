@@ -36,7 +36,6 @@ struct SlqSet {
 struct Slq {
     Code* code = nullptr;
     FixedPoint fx;
-    bool odd_check = false;
     std::vector<int32_t> layer_of_check, layer_start;
     DevBuf order;  // int32 [m]: the checks sorted by (layer, index), the processing order
     SlqSet set[2];  // set[0] holds the state when a chunk begins, every repack moves it to the other set
@@ -712,7 +711,6 @@ int slq_create(Code* code, Slq** out) {
     LDPC_HIP_TRY(hipSetDevice(code->device));
     Slq* h = new Slq();
     h->code = code;
-    h->odd_check = fx_odd_check(code);
     hipError_t e = hipHostMalloc(&h->pinned, 256, hipHostMallocDefault);
     for (int i = 0; i < SLQ_POLL_RING && e == hipSuccess; ++i) e = hipEventCreateWithFlags(&h->poll_ev[i], hipEventDisableTiming);
     if (e != hipSuccess) {
@@ -844,7 +842,7 @@ int slq_simulate(Slq* h, int channel, double param, int codeword, uint64_t seed,
                  uint32_t flags, int32_t hist_bins, int64_t* counters, hipStream_t st) {
     // the fp32 priors of one pass: a third of the workspace bound, whole state chunks where one fits
     const int64_t fit = std::max<int64_t>(workspace_bytes() / 3 / (int64_t)((size_t)h->code->n * sizeof(float)), 1), ct = (int64_t)chunk_tiles(h->code) * 64;
-    return fx_simulate("ldpc_slq_simulate", h->code, h->odd_check, h->sim, fit >= ct ? fit / ct * ct : fit, channel, param, codeword, seed, stream_id, frame0, B,
+    return fx_simulate("ldpc_slq_simulate", h->code, h->sim, fit >= ct ? fit / ct * ct : fit, channel, param, codeword, seed, stream_id, frame0, B,
                        hist_bins, counters, st, [&](const void* pri, const uint8_t* y, int64_t nb, uint32_t* bits, int32_t* iters) {
                            return slq_decode(h, DT_F32, pri, y, nb, max_iter, flags, nullptr, bits, iters, nullptr, st);
                        });

@@ -396,11 +396,22 @@ def test_nothing_throws_across_the_c_boundary():
     assert rc < 0 and b"bad graph arguments" in lib.ldpc_last_error()
     for m, n, E in ((-1, 4, 4), (4, 0, 4), (4, 4, -7)):
         assert lib.ldpc_plan_layout(m, n, E, chk.ctypes.data, chk.ctypes.data, 0, 0, 1000, None, info) < 0
-    # the guard is on every int-returning entry point of the shared object
+    # the guard is on every int-returning entry point of the shared object: the whole body of each is one `return guarded(...)`, or one
+    # `return <helper>(...)` of a helper in front of the extern "C" block whose own whole body is such a return
+    import re
+
     src = open(os.path.join(ROOT, "ldpc_decoders_amd", "csrc", "ldpc_api.hip")).read()
-    body = src[src.index('extern "C" {'):]
+    head, body = src.split('extern "C" {')
+    guards = ["guarded"]
+    for name, first in re.findall(r"^static int (\w+)\([^{]*\{\n\s*return (\w+)[(<]", head, re.M):
+        if first in guards:
+            guards.append(name)
+    assert guards[1:] and "handle_entry" in guards
     entries = [ln for ln in body.splitlines() if ln.startswith("int ldpc_") and "ldpc_abi_version" not in ln]
-    assert len(entries) >= 30 and body.count("return guarded(") == len(entries)
+    guarded_entries = re.findall(r"^int (ldpc_\w+)\([^{]*\{\s*return (\w+)[(<]", body, re.M)
+    assert len(entries) >= 30 and len(guarded_entries) == len(entries)
+    assert all(first in guards for _, first in guarded_entries), [e for e in guarded_entries if e[1] not in guards]
+    assert sum(body.count("return %s(" % g) + body.count("return %s<" % g) for g in guards) == len(entries)  # and no second return beside it
 
 
 # The Monte-Carlo (SIM) kernels behind `ldpc_simulate` for BASELINE configs 2-4 (+ the sum-product / irregular siblings main.py runs

@@ -64,7 +64,10 @@ def test_the_abi_declares_binds_and_exports_the_two_entries():
     assert lib.ldpc_qcpack_set and lib.ldpc_qcpack_get
     with open(os.path.join(ROOT, "ldpc_decoders_amd", "csrc", "ldpc_api.hip")) as fp:
         api = fp.read()
-    assert 'guarded("ldpc_qcpack_set"' in api and 'guarded("ldpc_qcpack_get"' in api
+    # defined under their own names, inside the guard (handle_entry's whole body is `return guarded(entry, ...)`) and on a Qc handle
+    assert "static int handle_entry(const char* entry, T h, bool ok, const char* what, F&& f) {\n    return guarded(entry, [&]() -> int {" in api
+    for name in ("ldpc_qcpack_set", "ldpc_qcpack_get"):
+        assert re.search(r'^int %s\(ldpc_qc_t h, [^{]*\{\s*return handle_entry<Qc>\("%s", h, ' % (name, name), api, re.M), name
 
 
 def test_the_parser_takes_the_flag_and_the_id_keys_stay():
