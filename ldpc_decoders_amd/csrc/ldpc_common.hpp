@@ -175,7 +175,7 @@ struct Decoder {
     DevBuf c2v16;      // fp16 storage: check -> variable lines, rebuilt by every check pass (not part of a set: a repack does not move them)
     DevBuf rmap;       // folded repack: source (tile, lane) of every frame of the new set
     DevBuf rbase;      // repack plan: first destination slot of every source tile
-    DevBuf flags;      // per-tile syndrome flags + the device poll words behind them
+    DevBuf flags;      // per-tile syndrome flags + the device poll ring behind them (LLR decoders: SweepPolls, ldpc_tiles.hpp)
     DevBuf graph_tab;  // variable-major view of the graph, built once (fp16 storage: edge_vpos; erasure: edge_vpos + chk_of_pos)
     DevBuf gridviol;   // exact-in-fp32 mode: device counter of guard events (LDPC_FLAG_PRIOR_GRID, ldpc_decoder_grid_violations)
     // staging: priors / received symbols / decisions / iteration counts of the *_host and simulate entry points, packed decisions and
@@ -192,7 +192,7 @@ struct Decoder {
     }
     // fused backend
     FusedPlan* fused = nullptr;
-    void* pinned = nullptr;  // small page-locked host block (polling word, counters)
+    void* pinned = nullptr;  // small page-locked host block (the host side of the poll ring, counters)
     // low-latency host path (ldpc_decode_host, a few frames per call -- the reference's one-frame-per-call loop, src/main.py:37-48):
     // page-locked, device-mapped staging the decode kernel reads priors from and writes decisions to DIRECTLY (no copy engine in the
     // path), a private stream and one event recorded right behind the kernel

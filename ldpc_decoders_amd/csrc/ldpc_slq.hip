@@ -12,9 +12,8 @@
 // 6E (2 + 2 + 1 + 1 per edge) + 2n.  Early termination per frame: syndrome of the planes before every sweep, polls of the live counters
 // that the host reads one behind, and a repack of the live frames into dense tiles (k_slq_repack) under the policy and the knobs of the
 // floating-point streaming decoders (LDPC_STREAM_REPACK, LDPC_STREAM_REPACK_FILL).
-// The tile helpers -- task order, planes, syndrome, unpack, poll ring -- restate those of ldpc_stream.hip under names of their own: its
-// kernels live in that file's unnamed namespace, and sharing them would have meant moving them (this file was added without touching the
-// machine code of any existing kernel).
+// The tile machinery -- task order, planes, syndrome, unpack, repack policy, poll ring and the check points of the sweep loop -- is that of
+// ldpc_stream.hip, shared through ldpc_tiles.hpp; the kernels of this file are the load, the passes, the repack copy and the soft output.
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
@@ -24,10 +23,9 @@
 #include "ldpc_layered_fx.hpp"
 #include "ldpc_repack.hpp"
 #include "ldpc_slq.hpp"
+#include "ldpc_tiles.hpp"
 
 namespace ldpc {
-
-constexpr int SLQ_POLL_RING = 4;
 
 struct SlqSet {
     DevBuf c2v, marg, planes, live, fmap;
@@ -40,9 +38,9 @@ struct Slq {
     DevBuf order;  // int32 [m]: the checks sorted by (layer, index), the processing order
     SlqSet set[2];  // set[0] holds the state when a chunk begins, every repack moves it to the other set
     DevBuf rbase;   // repack plan: first destination slot of every source tile
-    DevBuf flags;   // per-tile syndrome words + the device poll ring behind them
+    DevBuf flags;   // per-tile syndrome words + the device poll ring behind them (SweepPolls, ldpc_tiles.hpp)
     void* pinned = nullptr;  // page-locked poll ring
-    hipEvent_t poll_ev[SLQ_POLL_RING] = {};
+    hipEvent_t poll_ev[POLL_RING] = {};
     SimStage sim;   // staging of ldpc_slq_simulate
     // ldpc_slq_profile: [0] the layer passes of a sweep, [1] its decision pass, [2] a whole decode
     bool profile = false;
@@ -53,54 +51,6 @@ struct Slq {
 };
 
 namespace {
-
-using u64 = unsigned long long;
-
-// ---- tile helpers, as in ldpc_stream.hip ----------------------------------------------------------------------------------------------
-__device__ __forceinline__ u64 wave_or(u64 x) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-        const unsigned lo = __shfl_xor((unsigned)(x & 0xffffffffull), off, 64);
-        const unsigned hi = __shfl_xor((unsigned)(x >> 32), off, 64);
-        x |= ((u64)hi << 32) | lo;
-    }
-    return x;
-}
-
-// wave task -> (tile, chunk of nodes); XCD-aware order: the blocks of one tile all carry the same blockIdx.x % 8, hence one L2
-__device__ __forceinline__ bool task_of(int tiles, int chunks, int xcd_aware, int* tile, int* chunk) {
-    const int q = blockIdx.x, w = threadIdx.y;
-    if (xcd_aware) {
-        const int bpt = (chunks + 3) >> 2;
-        const int x = q & 7, local = q >> 3;
-        const int tl = local / bpt, cb = local - tl * bpt;
-        *tile = __builtin_amdgcn_readfirstlane(tl * 8 + x);
-        *chunk = __builtin_amdgcn_readfirstlane(cb * 4 + w);
-    } else {
-        const int task = q * 4 + w;
-        *tile = __builtin_amdgcn_readfirstlane(task / chunks);
-        *chunk = __builtin_amdgcn_readfirstlane(task - (task / chunks) * chunks);
-    }
-    return *tile < tiles && *chunk < chunks;
-}
-__host__ inline int task_blocks(int tiles, int chunks, int xcd_aware) {
-    return xcd_aware ? 8 * ((tiles + 7) / 8) * ((chunks + 3) / 4) : (int)(((long)tiles * chunks + 3) / 4);
-}
-
-// wave-uniform 8-byte read through the scalar cache: only for words no wave writes before this wave has read them in the same launch
-__device__ __forceinline__ u64 uniform_ld64(const u64* p) {
-    typedef const __attribute__((address_space(4))) u64* cptr;
-    return *(cptr)(uintptr_t)p;
-}
-__host__ __device__ __forceinline__ int64_t plane_at(int tile, int64_t v, int n) { return ((int64_t)(tile >> 3) * n + v) * 8 + (tile & 7); }
-__host__ inline size_t plane_words(int tiles, int n) { return (size_t)((tiles + 7) / 8) * n * 8; }
-
-__global__ void k_slq_init_live(u64* __restrict__ live, int64_t B, int tiles) {
-    const int t = blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= tiles) return;
-    const int64_t rem = B - (int64_t)t * 64;
-    live[t] = rem >= 64 ? ~0ull : (rem <= 0 ? 0ull : ((1ull << rem) - 1ull));
-}
 
 // ---- load: priors [B, n] (fp32 / fp64, frame-major) -> int16 marginal rows [n][64], quantised in the type they arrive in; y0 -> planes ---
 template <typename T>
@@ -291,61 +241,6 @@ __global__ void k_slq_soft_out(const int16_t* __restrict__ marg, const int32_t* 
     if (v < n && fr < B) out[fr * n + v] = iters[fr] > 0 ? marg[((int64_t)tile * n + v) * 64 + lane] : (int16_t)0;
 }
 
-// ---- syndrome of the planes; frames whose syndrome is zero leave (iters = sweeps run so far) -----------------------------------------
-__global__ __launch_bounds__(256) void k_slq_syndrome_part(const int32_t* __restrict__ row_ptr, const int32_t* __restrict__ edge_var,
-                                                           const u64* __restrict__ xbits, const u64* __restrict__ live, u64* __restrict__ unsat_acc,
-                                                           int m, int n, int tiles, int checks_per_block) {
-    const int grp = blockIdx.y, t = threadIdx.x;
-    const int t0 = grp * 8, nt = min(8, tiles - t0);
-    u64 any_live = 0;
-    for (int i = 0; i < nt; ++i) any_live |= live[t0 + i];
-    if (any_live == 0) return;
-    const ulonglong2* xb = reinterpret_cast<const ulonglong2*>(xbits + (int64_t)grp * n * 8);  // variable v: xb[4 v .. 4 v + 3]
-    const int c0 = blockIdx.x * checks_per_block, c1 = min(m, c0 + checks_per_block);
-    u64 acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    for (int c = c0 + t; c < c1; c += 256) {
-        u64 par[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-        for (int k = row_ptr[c]; k < row_ptr[c + 1]; ++k) {
-            const ulonglong2* w = xb + (int64_t)edge_var[k] * 4;
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const ulonglong2 x = w[q];
-                par[2 * q] ^= x.x;
-                par[2 * q + 1] ^= x.y;
-            }
-        }
-#pragma unroll
-        for (int i = 0; i < 8; ++i) acc[i] |= par[i];
-    }
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        const u64 a = wave_or(acc[i]);
-        if ((t & 63) == 0 && a && i < nt) atomicOr(&unsat_acc[2 * (t0 + i)], a);
-    }
-}
-
-__global__ __launch_bounds__(64) void k_slq_syndrome_fin(u64* __restrict__ unsat_acc, u64* __restrict__ live, int32_t* __restrict__ iters,
-                                                         int* __restrict__ live_tiles, int64_t B, int sweeps, const int32_t* __restrict__ frame_of) {
-    const int tile = blockIdx.x, t = threadIdx.x;
-    const u64 lv = live[tile];
-    if (lv == 0) return;
-    const u64 unsat = unsat_acc[2 * tile];
-    const u64 stay = lv & unsat, leave = lv & ~unsat;
-    __syncthreads();  // every lane has read the word before lane 0 clears it for the next sweep
-    if (t == 0) {
-        unsat_acc[2 * tile] = 0;
-        live[tile] = stay;
-        if (stay && live_tiles) {
-            atomicAdd(live_tiles, 1);                   // tiles that still hold a live frame
-            atomicAdd(live_tiles + 1, __popcll(stay));  // live frames
-        }
-    }
-    if ((leave >> t) & 1ull) {
-        const int64_t fr = frame_of ? (int64_t)frame_of[(int64_t)tile * 64 + t] : (int64_t)tile * 64 + t;
-        if (fr >= 0 && fr < B) iters[fr] = sweeps;
-    }
-}
-
 // ---- frame repack (ldpc_repack.hpp): the separate copy kernel for the two integer types ------------------------------------------------
 // destination lane j reads (source tile, source lane) of the j-th live frame: message rows, then per variable the marginal row and one
 // plane word; lanes beyond the live frames get zeros
@@ -382,47 +277,6 @@ __global__ __launch_bounds__(256) void k_slq_repack(const int8_t* __restrict__ m
     }
 }
 
-// ---- outputs -----------------------------------------------------------------------------------------------------------------------------
-__global__ void k_slq_finish_iters(const u64* __restrict__ live, int32_t* __restrict__ iters, int64_t B, int sweeps, const int32_t* __restrict__ frame_of) {
-    const int tile = blockIdx.x, t = threadIdx.x;
-    const u64 lv = live[tile];
-    const int64_t fr = frame_of ? (int64_t)frame_of[(int64_t)tile * 64 + t] : (int64_t)tile * 64 + t;
-    if (((lv >> t) & 1ull) && fr >= 0 && fr < B) iters[fr] = sweeps;
-}
-
-__global__ __launch_bounds__(256) void k_slq_unpack(const u64* __restrict__ xbits, uint8_t* __restrict__ xhat, int64_t B, int n,
-                                                    const int32_t* __restrict__ frame_of) {
-    const int tile = blockIdx.y;
-    const int v = blockIdx.x * 256 + threadIdx.x;
-    if (v >= n) return;
-    const u64 one = xbits[plane_at(tile, v, n)];
-    const int64_t f0 = (int64_t)tile * 64;
-    for (int f = 0; f < 64; ++f) {  // repacked tiles: lane f holds frame frame_of[tile][f] (-1: none)
-        const int64_t fr = frame_of ? (int64_t)frame_of[f0 + f] : f0 + f;
-        if (fr >= 0 && fr < B) xhat[fr * n + v] = (uint8_t)((one >> f) & 1ull);
-    }
-}
-
-// planes -> packed decisions [B, W] u32: one wave per (tile, 64 variables), the 64 x 64 bit block transposed with 64 ballots
-__global__ __launch_bounds__(256) void k_slq_unpack_bits(const u64* __restrict__ xbits, uint32_t* __restrict__ bits, int64_t B, int n, int W,
-                                                         const int32_t* __restrict__ frame_of) {
-    const int tile = blockIdx.y, lane = threadIdx.x;
-    const int vb = blockIdx.x * 4 + threadIdx.y, v0 = vb * 64;
-    if (v0 >= n) return;
-    const u64 col = v0 + lane < n ? xbits[plane_at(tile, v0 + lane, n)] : 0ull;
-    u64 row = 0;
-    for (int f = 0; f < 64; ++f) {
-        const u64 b = __ballot((col >> f) & 1ull);
-        if (lane == f) row = b;
-    }
-    const int64_t fr = frame_of ? (int64_t)frame_of[(int64_t)tile * 64 + lane] : (int64_t)tile * 64 + lane;
-    if (fr >= 0 && fr < B) {
-        uint32_t* out = bits + fr * W + 2 * vb;
-        out[0] = (uint32_t)row;
-        if (2 * vb + 1 < W) out[1] = (uint32_t)(row >> 32);
-    }
-}
-
 // ---- host side ------------------------------------------------------------------------------------------------------------------------
 // the arguments of one chunk of a decode: every pointer already points at the chunk's first frame
 struct SlqCall {
@@ -442,24 +296,6 @@ struct SlqGeometry {
     int tiles, cpw, vn_chunks, vpw, xcd_aware, freeze;
     int scale64, offset, vmax;
 };
-
-// decisions of the frames of `tiles` tiles in every form the caller asked for
-void launch_unpack(const SlqCall& k, const u64* xbits, int n, int tiles, const int32_t* fmap) {
-    if (k.bits)
-        hipLaunchKernelGGL(k_slq_unpack_bits, dim3(((n + 63) / 64 + 3) / 4, tiles), dim3(64, 4), 0, k.stream, xbits, k.bits, k.B, n, (n + 31) / 32, fmap);
-    if (k.xhat) hipLaunchKernelGGL(k_slq_unpack, dim3((n + 255) / 256, tiles), dim3(256), 0, k.stream, xbits, k.xhat, k.B, n, fmap);
-}
-
-void launch_syndrome(const Code* c, const SlqCall& k, const u64* xbits, u64* live, u64* tflags, int* poll_dev, int tiles, int sweeps, const int32_t* fmap) {
-    // groups of eight tiles x chunks of the checks: enough blocks to fill the chip, at least 1024 checks each
-    const int groups = (tiles + 7) / 8;
-    int sblocks = (1024 + groups - 1) / groups;
-    const int smax = (c->m + 1023) / 1024;
-    sblocks = sblocks < 1 ? 1 : (sblocks > smax ? smax : sblocks);
-    const int cpb = (c->m + sblocks - 1) / sblocks;
-    hipLaunchKernelGGL(k_slq_syndrome_part, dim3(sblocks, groups), dim3(256), 0, k.stream, c->d_row_ptr, c->d_edge_var, xbits, live, tflags, c->m, c->n, tiles, cpb);
-    hipLaunchKernelGGL(k_slq_syndrome_fin, dim3(tiles), dim3(64), 0, k.stream, tflags, live, k.iters, poll_dev, k.B, sweeps, fmap);
-}
 
 // Degree classes of the layer pass, those of ldpc_stream.hip's check_class -- regular dc = 6; degrees up to 6; else the next power of two
 // up to 64 -- and the two-pass kernel above 64.  Checks in flight per wave: about 32 VGPRs of rows.
@@ -501,24 +337,6 @@ int slq_event(Slq* h, size_t idx, hipEvent_t* out) {
     return LDPC_OK;
 }
 
-struct PendingPoll {
-    int slot, it, sweeps;
-    bool tiling_current;  // false once a repack has been enqueued after this poll
-};
-
-// the repack policy of the streaming decoders (ldpc_stream.hip RepackPolicy), read from the environment at the top of every decode
-struct SlqRepackPolicy {
-    bool on;
-    double fill = 0.75;
-    explicit SlqRepackPolicy(bool eligible) : on(eligible) {
-        if (const char* e = std::getenv("LDPC_STREAM_REPACK")) on = on && atoi(e) != 0;
-        if (const char* e = std::getenv("LDPC_STREAM_REPACK_FILL")) fill = atof(e);
-        if (fill > 0.95) fill = 0.95;
-        if (!(fill >= 0.0)) fill = 0.0;
-    }
-    bool wants(int live_tiles, int live_frames) const { return live_tiles >= 2 && (double)live_frames <= fill * 64.0 * live_tiles; }
-};
-
 int64_t workspace_bytes() {
     if (const char* e = std::getenv("LDPC_SLQ_WORKSPACE_MB")) {
         const long long mb = atoll(e);
@@ -533,7 +351,8 @@ int chunk_tiles(const Code* c) {
     return (int)std::min<int64_t>(std::max<int64_t>(workspace_bytes() / (2 * per_tile), 1), 1 << 15);
 }
 
-// One chunk of frames, LMSA's loop (ldpc_stream.hip run<T, ALG_LMSA>).  `prof_next`: first free profile event of the pool.
+// One chunk of frames: the sweep loop of ldpc_stream.hip's run<T, ALG_LMSA>, its check points those of SweepPolls (ldpc_tiles.hpp).
+// `prof_next`: first free profile event of the pool.
 template <typename T>
 int run_chunk(Slq* h, const SlqCall& k, size_t* prof_next, std::vector<hipEvent_t>* spans, int* sweeps_out, int* repacks_out) {
     const Code* c = h->code;
@@ -542,17 +361,16 @@ int run_chunk(Slq* h, const SlqCall& k, size_t* prof_next, std::vector<hipEvent_
     const hipStream_t st = k.stream;
     const int tiles = (int)((B + 63) / 64);
     const bool early = !(k.flags & FLAG_NO_EARLY_EXIT);
-    SlqRepackPolicy repack(early && k.soft == nullptr && tiles >= 2);
+    RepackPolicy repack(early && k.soft == nullptr && tiles >= 2);
 
     SlqSet* const set = h->set;
     LDPC_TRY(set[0].c2v.reserve((size_t)tiles * E * 64));
     LDPC_TRY(set[0].marg.reserve((size_t)tiles * n * 64 * sizeof(int16_t)));
     LDPC_TRY(set[0].planes.reserve(plane_words(tiles, n) * 8));
     LDPC_TRY(set[0].live.reserve((size_t)tiles * 8));
-    LDPC_TRY(h->flags.reserve((size_t)tiles * 16 + 64 + SLQ_POLL_RING * 16));
+    LDPC_TRY(h->flags.reserve((size_t)tiles * 16 + 64 + POLL_RING_BYTES));
     if (repack.on) {
-        // second state set: the first repack fires at <= fill * 64 live frames per tile, later ones only shrink
-        const size_t nt = (size_t)(repack.fill * tiles) + 2;
+        const size_t nt = repack.target_tiles(tiles);  // second state set
         if (set[1].c2v.reserve(nt * E * 64) || set[1].marg.reserve(nt * n * 64 * sizeof(int16_t)) || set[1].planes.reserve(plane_words((int)nt, n) * 8) ||
             set[1].live.reserve(nt * 8) || set[1].fmap.reserve(nt * 64 * sizeof(int32_t)) || set[0].fmap.reserve(nt * 64 * sizeof(int32_t)) ||
             h->rbase.reserve(((size_t)tiles + 1) * sizeof(int32_t)))
@@ -571,9 +389,7 @@ int run_chunk(Slq* h, const SlqCall& k, size_t* prof_next, std::vector<hipEvent_
         live = (u64*)set[s].live.p;
     };
     use_set(0);
-    u64* tflags = (u64*)h->flags.p;                                        // [tiles][2]
-    int* poll_dev = (int*)((char*)h->flags.p + (size_t)tiles * 16 + 64);  // [SLQ_POLL_RING][4] ints: live tiles, live frames
-    volatile int* poll_host = (volatile int*)h->pinned;
+    u64* tflags = (u64*)h->flags.p;  // [tiles][2], the device poll ring behind them
 
     SlqGeometry g;
     g.tiles = tiles;
@@ -595,72 +411,35 @@ int run_chunk(Slq* h, const SlqCall& k, size_t* prof_next, std::vector<hipEvent_
     g.xcd_aware = (size_t)n * 64 * sizeof(int16_t) <= ((size_t)4 << 20) ? 1 : 0;  // a tile's marginal rows fit one XCD's L2
 
     LDPC_HIP_TRY(hipMemsetAsync(xbits, 0, plane_words(tiles, n) * 8, st));
-    LDPC_HIP_TRY(hipMemsetAsync(tflags, 0, (size_t)tiles * 16 + 64 + SLQ_POLL_RING * 16, st));
+    LDPC_HIP_TRY(hipMemsetAsync(tflags, 0, (size_t)tiles * 16 + 64 + POLL_RING_BYTES, st));
     LDPC_HIP_TRY(hipMemsetAsync(k.iters, 0, (size_t)B * sizeof(int32_t), st));
     hipLaunchKernelGGL((k_slq_load<T>), dim3((n + 63) / 64, tiles), dim3(256), 0, st, (const T*)k.priors, k.y0, B, n, (T)h->fx.step(), (T)g.vmax, marg, xbits);
-    hipLaunchKernelGGL(k_slq_init_live, dim3((tiles + 255) / 256), dim3(256), 0, st, live, B, tiles);
+    tiles_init_live(live, B, tiles, st);
 
     const int cap = k.max_iter > 0 ? k.max_iter : 100000;
-    // how often the live counters are polled: about every 300 us of streaming work
     const double bytes_per_frame = 6.0 * E + 2.0 * n;
-    const double iter_us = 15.0 + (double)tiles * 64.0 * bytes_per_frame / 5.0e6;
-    int poll_every = (int)(300.0 / iter_us);
-    poll_every = poll_every < 1 ? 1 : (poll_every > 16 ? 16 : poll_every);
-    int cur_tiles = tiles, repacks = 0, sweeps = 0, polls = 0;
-    std::vector<PendingPoll> pending;
-    bool all_left = false;
-    for (int it = 0; it < cap && !all_left; ++it) {
-        const bool check = early && (it > 0 || k.y0 != nullptr);
-        if (check) {
-            const bool poll = (it % poll_every) == 0 || k.max_iter <= 0;
-            int* slot_dev = nullptr;
-            int slot = 0;
-            if (poll) {
-                slot = polls % SLQ_POLL_RING;
-                slot_dev = poll_dev + 4 * slot;
-                LDPC_HIP_TRY(hipMemsetAsync(slot_dev, 0, 2 * sizeof(int), st));
-            }
-            launch_syndrome(c, k, xbits, live, tflags, slot_dev, cur_tiles, sweeps, fmap);
-            if (poll) {
-                LDPC_HIP_TRY(hipMemcpyAsync((void*)(poll_host + 4 * slot), slot_dev, 2 * sizeof(int), hipMemcpyDeviceToHost, st));
-                LDPC_HIP_TRY(hipEventRecord(h->poll_ev[slot], st));
-                pending.push_back({slot, it, sweeps, true});
-                ++polls;
-                // the oldest poll is read once a newer one is enqueued behind it; a single tile, an unbounded run or a long sweep (more than
-                // ~1.5 ms of streaming work) reads the newest at once, as the floating-point loop does
-                const double sweep_us_now = (double)cur_tiles * 64.0 * bytes_per_frame / 5.0e6;
-                const bool eager = k.max_iter <= 0 || cur_tiles < 2 || sweep_us_now > 1500.0;
-                while (!pending.empty() && (pending.size() >= 2 || eager)) {
-                    const PendingPoll pp = pending.front();
-                    pending.erase(pending.begin());
-                    LDPC_HIP_TRY(hipEventSynchronize(h->poll_ev[pp.slot]));
-                    const int lt = poll_host[4 * pp.slot], lf = poll_host[4 * pp.slot + 1];
-                    if (lt == 0) {  // every frame had left at that check point; what was enqueued since found no live tile
-                        all_left = true;
-                        sweeps = pp.sweeps;
-                        break;
-                    }
-                    if (repack.on && pp.tiling_current && pp.it > 0 && repack.wants(lt, lf) && it + 1 < cap) {
-                        const int nt = (lf + 63) / 64;
-                        const SlqSet& to = set[1 - cur];
-                        // the decisions of every frame of the old tiles (those that left keep them; the moved ones overwrite theirs later)
-                        launch_unpack(k, xbits, n, cur_tiles, fmap);
-                        hipLaunchKernelGGL(k_repack_plan, dim3(1), dim3(1024), 0, st, live, cur_tiles, (int32_t*)h->rbase.p);
-                        const int rows_per_wave = 128;
-                        const int chunks = (int)((E + n + rows_per_wave - 1) / rows_per_wave);
-                        hipLaunchKernelGGL(k_slq_repack, dim3((chunks + 3) / 4, nt), dim3(64, 4), 0, st, msg, (int8_t*)to.c2v.p, marg, (int16_t*)to.marg.p, xbits,
-                                           (u64*)to.planes.p, live, (u64*)to.live.p, (const int32_t*)h->rbase.p, fmap, (int32_t*)to.fmap.p, cur_tiles, n, E,
-                                           rows_per_wave);
-                        use_set(1 - cur);
-                        fmap = (int32_t*)to.fmap.p;
-                        cur_tiles = nt;
-                        g.tiles = nt;
-                        ++repacks;
-                        for (PendingPoll& q : pending) q.tiling_current = false;
-                    }
-                }
-                if (all_left) break;
-            }
+    SweepPolls p{st, (int*)((char*)h->flags.p + (size_t)tiles * 16 + 64), (volatile int*)h->pinned, h->poll_ev, repack, cap, tiles, bytes_per_frame};
+    p.poll_every = SweepPolls::poll_every_300us(tiles, bytes_per_frame);
+    p.every_sweep = p.eager = k.max_iter <= 0;  // an unbounded run polls at every sweep and reads at once
+    const auto syndrome = [&](int* slot_dev) { tiles_syndrome(c, xbits, live, tflags, k.iters, slot_dev, B, p.cur_tiles, p.sweeps, fmap, st); };
+    const auto repack_into = [&](int nt) {
+        const SlqSet& to = set[1 - cur];
+        // the decisions of every frame of the old tiles (those that left keep them; the moved ones overwrite theirs later)
+        tiles_unpack(xbits, k.xhat, k.bits, B, n, p.cur_tiles, fmap, st);
+        hipLaunchKernelGGL(k_repack_plan, dim3(1), dim3(1024), 0, st, live, p.cur_tiles, (int32_t*)h->rbase.p);
+        const int rows_per_wave = 128;
+        const int chunks = (int)((E + n + rows_per_wave - 1) / rows_per_wave);
+        hipLaunchKernelGGL(k_slq_repack, dim3((chunks + 3) / 4, nt), dim3(64, 4), 0, st, msg, (int8_t*)to.c2v.p, marg, (int16_t*)to.marg.p, xbits,
+                           (u64*)to.planes.p, live, (u64*)to.live.p, (const int32_t*)h->rbase.p, fmap, (int32_t*)to.fmap.p, p.cur_tiles, n, E, rows_per_wave);
+        use_set(1 - cur);
+        fmap = (int32_t*)to.fmap.p;
+        g.tiles = nt;
+        return nt;
+    };
+    for (int it = 0; it < cap && !p.all_left; ++it) {
+        if (early && (it > 0 || k.y0 != nullptr)) {
+            LDPC_TRY(p.check_point(it, syndrome, repack_into));
+            if (p.all_left) break;
         }
         hipEvent_t e[3] = {};
         if (h->profile) {
@@ -675,17 +454,16 @@ int run_chunk(Slq* h, const SlqCall& k, size_t* prof_next, std::vector<hipEvent_
             LDPC_HIP_TRY(hipEventRecord(e[2], st));
             spans->insert(spans->end(), e, e + 3);
         }
-        ++sweeps;
+        ++p.sweeps;
     }
-    hipLaunchKernelGGL(k_slq_finish_iters, dim3(cur_tiles), dim3(64), 0, st, live, k.iters, B, sweeps, fmap);
-    launch_unpack(k, xbits, n, cur_tiles, fmap);
+    tiles_finish_iters(live, k.iters, B, p.cur_tiles, p.sweeps, fmap, st);
+    tiles_unpack(xbits, k.xhat, k.bits, B, n, p.cur_tiles, fmap, st);
     // (a soft-output decode never repacks: `marg` is set 0 in the identity tiling)
     if (k.soft) hipLaunchKernelGGL(k_slq_soft_out, dim3((n + 3) / 4, tiles), dim3(256), 0, st, marg, (const int32_t*)k.iters, k.soft, B, n);
-    // polls still in flight copy into the pinned ring: let the last copy land before the next chunk or call reuses the slots
-    if (!pending.empty()) LDPC_HIP_TRY(hipEventSynchronize(h->poll_ev[pending.back().slot]));
+    LDPC_TRY(p.finish());  // (before the next chunk or call reuses the slots)
     LDPC_HIP_TRY(hipGetLastError());
-    *sweeps_out = sweeps;
-    *repacks_out = repacks;
+    *sweeps_out = p.sweeps;
+    *repacks_out = p.repacks;
     return LDPC_OK;
 }
 
@@ -712,7 +490,7 @@ int slq_create(Code* code, Slq** out) {
     Slq* h = new Slq();
     h->code = code;
     hipError_t e = hipHostMalloc(&h->pinned, 256, hipHostMallocDefault);
-    for (int i = 0; i < SLQ_POLL_RING && e == hipSuccess; ++i) e = hipEventCreateWithFlags(&h->poll_ev[i], hipEventDisableTiming);
+    for (int i = 0; i < POLL_RING && e == hipSuccess; ++i) e = hipEventCreateWithFlags(&h->poll_ev[i], hipEventDisableTiming);
     if (e != hipSuccess) {
         set_error("ldpc_slq_create: device setup failed: %s", hipGetErrorString(e));
         slq_destroy(h);

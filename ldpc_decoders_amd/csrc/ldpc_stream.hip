@@ -38,12 +38,11 @@
 #include "ldpc_common.hpp"
 #include "ldpc_repack.hpp"
 #include "ldpc_rng.hpp"
+#include "ldpc_tiles.hpp"
 
 namespace ldpc {
 
 namespace {
-
-using u64 = unsigned long long;
 
 // streaming (non-temporal) access, selectable per pass and per direction (measured): the check pass streams
 // its c2v lines through with non-temporal loads AND stores so that they do not push the marginal lines (re-used dv times) out of
@@ -55,49 +54,6 @@ template <bool NT, typename T> __device__ __forceinline__ T msg_ld(const T* p) {
 template <bool NT, typename T> __device__ __forceinline__ void msg_st(T* p, T v) {
     if constexpr (NT) __builtin_nontemporal_store(v, p); else *p = v;
 }
-
-__device__ __forceinline__ u64 wave_or(u64 x) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-        const unsigned lo = __shfl_xor((unsigned)(x & 0xffffffffull), off, 64);
-        const unsigned hi = __shfl_xor((unsigned)(x >> 32), off, 64);
-        x |= ((u64)hi << 32) | lo;
-    }
-    return x;
-}
-
-// Wave task -> (tile, chunk of nodes).  XCD-aware (MI355X_MICROARCH.md: block b runs on XCD b % 8, each XCD has its own L2): the
-// blocks of ONE tile all carry the same b % 8, so the marginal lines a check pass re-reads (each is used by dv checks of the tile)
-// are re-read through ONE L2 instead of up to dv different ones.  Grid = 8 x ceil(tiles / 8) x blocks per tile (4 waves per block).
-__device__ __forceinline__ bool task_of(int tiles, int chunks, int xcd_aware, int* tile, int* chunk) {
-    const int q = blockIdx.x, w = threadIdx.y;
-    if (xcd_aware) {
-        const int bpt = (chunks + 3) >> 2;
-        const int x = q & 7, local = q >> 3;
-        const int tl = local / bpt, cb = local - tl * bpt;
-        *tile = __builtin_amdgcn_readfirstlane(tl * 8 + x);
-        *chunk = __builtin_amdgcn_readfirstlane(cb * 4 + w);
-    } else {
-        const int task = q * 4 + w;
-        *tile = __builtin_amdgcn_readfirstlane(task / chunks);
-        *chunk = __builtin_amdgcn_readfirstlane(task - (task / chunks) * chunks);
-    }
-    return *tile < tiles && *chunk < chunks;
-}
-__host__ inline int task_blocks(int tiles, int chunks, int xcd_aware) {
-    return xcd_aware ? 8 * ((tiles + 7) / 8) * ((chunks + 3) / 4) : (int)(((long)tiles * chunks + 3) / 4);
-}
-
-// index of the bit-plane word of (tile, variable): eight tiles interleaved per variable
-// Wave-uniform 8-byte read through the SCALAR cache (constant address space: the compiler emits s_load_dwordx2, counted by lgkmcnt and
-// therefore independent of the vector loads and stores in flight).  Only for words no wave writes before this wave has read them in the
-// same launch: the decision word of (tile, variable) is read and then written by exactly one wave per sweep.
-__device__ __forceinline__ u64 uniform_ld64(const u64* p) {
-    typedef const __attribute__((address_space(4))) u64* cptr;
-    return *(cptr)(uintptr_t)p;
-}
-__host__ __device__ __forceinline__ int64_t plane_at(int tile, int64_t v, int n) { return ((int64_t)(tile >> 3) * n + v) * 8 + (tile & 7); }
-__host__ inline size_t plane_words(int tiles, int n) { return (size_t)((tiles + 7) / 8) * n * 8; }
 
 // ---------------------------------------------------------------------------------------------------
 // priors [B,n] (frame-major, as numpy hands them over) -> prior tile [n][64]; optional hard word y0 -> planes.
@@ -673,30 +629,44 @@ __global__ __launch_bounds__(256) void k_unpack_bits(const u64* __restrict__ xbi
     }
 }
 
-// decisions of the frames of `tiles` tiles in the form the caller asked for: bytes [B,n] (ldpc_decode) or packed words (ldpc_decode_bits)
-void launch_unpack(const DecodeCall& k, const u64* xbits, int n, int tiles, const int32_t* fmap) {
-    if (k.bits)
-        hipLaunchKernelGGL(k_unpack_bits, dim3(((n + 63) / 64 + 3) / 4, tiles), dim3(64, 4), 0, k.stream, xbits, k.bits, k.B, n, (n + 31) / 32, fmap);
-    else
-        hipLaunchKernelGGL(k_unpack, dim3((n + 255) / 256, tiles), dim3(256), 0, k.stream, xbits, k.xhat, k.B, n, fmap);
+}  // namespace
+
+// The launchers of the bookkeeping kernels above (ldpc_tiles.hpp), for this file's loops and SLQMSA's (ldpc_slq.hip).
+void tiles_init_live(u64* live, int64_t B, int tiles, hipStream_t st) {
+    hipLaunchKernelGGL(k_init_live, dim3((tiles + 255) / 256), dim3(256), 0, st, live, B, tiles);
 }
 
-// syndrome of the decisions of `tiles` tiles: frames that satisfy every check leave (live bit cleared, iteration count written); with
-// `poll_dev` the live tiles / live frames are added into it
-void launch_syndrome(const Code* c, const DecodeCall& k, const u64* xbits, u64* live, u64* tflags, int* poll_dev, int tiles, int sweeps, const int32_t* fmap) {
+void tiles_syndrome(const Code* c, const u64* xbits, u64* live, u64* tflags, int32_t* iters, int* poll_dev, int64_t B, int tiles, int sweeps,
+                    const int32_t* fmap, hipStream_t st) {
     // groups of eight tiles x chunks of the checks: enough blocks to fill the chip (about 4 per CU), at least 1024 checks each
     const int groups = (tiles + 7) / 8;
     int sblocks = (1024 + groups - 1) / groups;
     const int smax = (c->m + 1023) / 1024;
     sblocks = sblocks < 1 ? 1 : (sblocks > smax ? smax : sblocks);
     const int cpb = (c->m + sblocks - 1) / sblocks;
-    hipLaunchKernelGGL(k_syndrome_part, dim3(sblocks, groups), dim3(256), 0, k.stream, c->d_row_ptr, c->d_edge_var, xbits, live, tflags, c->m, c->n, tiles, cpb);
-    hipLaunchKernelGGL(k_syndrome_fin, dim3(tiles), dim3(64), 0, k.stream, tflags, live, k.iters, poll_dev, k.B, sweeps, fmap);
+    hipLaunchKernelGGL(k_syndrome_part, dim3(sblocks, groups), dim3(256), 0, st, c->d_row_ptr, c->d_edge_var, xbits, live, tflags, c->m, c->n, tiles, cpb);
+    hipLaunchKernelGGL(k_syndrome_fin, dim3(tiles), dim3(64), 0, st, tflags, live, iters, poll_dev, B, sweeps, fmap);
+}
+
+void tiles_unpack(const u64* xbits, uint8_t* xhat, uint32_t* bits, int64_t B, int n, int tiles, const int32_t* fmap, hipStream_t st) {
+    if (bits) hipLaunchKernelGGL(k_unpack_bits, dim3(((n + 63) / 64 + 3) / 4, tiles), dim3(64, 4), 0, st, xbits, bits, B, n, (n + 31) / 32, fmap);
+    if (xhat) hipLaunchKernelGGL(k_unpack, dim3((n + 255) / 256, tiles), dim3(256), 0, st, xbits, xhat, B, n, fmap);
+}
+
+void tiles_finish_iters(const u64* live, int32_t* iters, int64_t B, int tiles, int sweeps, const int32_t* fmap, hipStream_t st) {
+    hipLaunchKernelGGL(k_finish_iters, dim3(tiles), dim3(64), 0, st, live, iters, B, sweeps, fmap);
+}
+
+namespace {
+
+// decisions in the form the caller asked for: packed words (ldpc_decode_bits) if set, else bytes [B,n] (ldpc_decode)
+void launch_unpack(const DecodeCall& k, const u64* xbits, int n, int tiles, const int32_t* fmap) {
+    tiles_unpack(xbits, k.bits ? nullptr : k.xhat, k.bits, k.B, n, tiles, fmap, k.stream);
 }
 
 // what every LLR decode ends with: iteration counts of the frames still live, decisions in the form the caller asked for
 void launch_decisions(const DecodeCall& k, const u64* xbits, const u64* live, int n, int tiles, int sweeps, const int32_t* fmap) {
-    hipLaunchKernelGGL(k_finish_iters, dim3(tiles), dim3(64), 0, k.stream, live, k.iters, k.B, sweeps, fmap);
+    tiles_finish_iters(live, k.iters, k.B, tiles, sweeps, fmap, k.stream);
     launch_unpack(k, xbits, n, tiles, fmap);
 }
 
@@ -705,22 +675,6 @@ bool degrees_supported(const Code* c) {
     set_error("streaming backend supports node degrees up to 64 (max_dc=%d, max_dv=%d)", c->max_dc, c->max_dv);
     return false;
 }
-
-// Frame repack (see k_repack): LLR decoders without soft output.  Policy: at a poll, when the live frames would fill less than
-// `fill` of the tiles that still hold one, gather them into dense tiles -- a repack moves (E + 2n) lines per tile once, a sweep
-// moves about (3E + 3n), so it pays as soon as about one more sweep follows.  Read from the environment at the top of every decode.
-struct RepackPolicy {
-    bool on;
-    double fill = 0.75;
-    explicit RepackPolicy(bool eligible) : on(eligible) {
-        if (const char* e = std::getenv("LDPC_STREAM_REPACK")) on = on && atoi(e) != 0;
-        if (const char* e = std::getenv("LDPC_STREAM_REPACK_FILL")) fill = atof(e);
-        if (fill > 0.95) fill = 0.95;
-    }
-    // (a "rent or buy" schedule -- repack once the tile-sweeps spent on departed lanes reach the cost of a repack -- was measured within
-    // the run-to-run spread of this rule in round 5 and removed in round 6: HISTORY.md)
-    bool wants(int live_tiles, int live_frames) const { return live_tiles >= 2 && (double)live_frames <= fill * 64.0 * live_tiles; }
-};
 
 // Per-kernel timing of a decode when Decoder::profile is set (no-ops otherwise): event pairs around the two passes of every sweep
 // (kinds 0 and 1) and, optionally, around the whole decode (kind 3).  `next`: first free entry of the decoder's event pool.
@@ -867,15 +821,6 @@ int env_int(const char* name, int dflt) {
     return e && *e ? atoi(e) : dflt;
 }
 
-// One poll of the live counters, in flight: the syndrome kernels of a check point add the live tiles / frames into `slot` of the
-// device ring, a copy brings them to the pinned ring, an event marks it.  The host reads poll k only after it has enqueued the work
-// up to poll k + 1, so the GPU never waits for the host inside the sweep loop.
-struct PendingPoll {
-    int slot, it, sweeps, tiles;
-    bool tiling_current;  // false once a repack has been enqueued after this poll: its tile count no longer describes the state
-};
-constexpr int POLL_RING = 4;
-
 template <typename T, int ALG>
 int run(Decoder* d, const DecodeCall& k, const SimSource* sim = nullptr) {
     const Code* c = d->code;
@@ -899,10 +844,10 @@ int run(Decoder* d, const DecodeCall& k, const SimSource* sim = nullptr) {
     if (!LAYERED) LDPC_TRY(set[0].prior.reserve((size_t)tiles * n * 64 * sizeof(T)));
     LDPC_TRY(set[0].planes.reserve(plane_words(tiles, n) * 8));
     LDPC_TRY(set[0].live.reserve((size_t)tiles * 8));
-    LDPC_TRY(d->flags.reserve((size_t)tiles * 16 + 64 + POLL_RING * 16));
+    LDPC_TRY(d->flags.reserve((size_t)tiles * 16 + 64 + POLL_RING_BYTES));
     if (repack.on) {
         // second state set: the first repack fires at <= fill * 64 live frames per tile, later ones only shrink
-        const size_t nt = (size_t)(repack.fill * tiles) + 2;
+        const size_t nt = repack.target_tiles(tiles);
         if (set[1].edge.reserve(nt * E * 64 * sizeof(T)) || set[1].node.reserve(nt * n * 64 * sizeof(T)) ||
             (!LAYERED && set[1].prior.reserve(nt * n * 64 * sizeof(T))) || set[1].planes.reserve(plane_words((int)nt, n) * 8) || set[1].live.reserve(nt * 8) ||
             set[1].fmap.reserve(nt * 64 * sizeof(int32_t)) || set[0].fmap.reserve(nt * 64 * sizeof(int32_t)) ||
@@ -926,9 +871,7 @@ int run(Decoder* d, const DecodeCall& k, const SimSource* sim = nullptr) {
         live = (u64*)set[s].live.p;
     };
     use_set(0);
-    u64* tflags = (u64*)d->flags.p;                                        // [tiles][2]
-    int* poll_dev = (int*)((char*)d->flags.p + (size_t)tiles * 16 + 64);  // [POLL_RING][4] ints: live tiles, live frames
-    volatile int* poll_host = (volatile int*)d->pinned;                    // [POLL_RING][4] page-locked
+    u64* tflags = (u64*)d->flags.p;  // [tiles][2], the device poll ring behind them
     hipEvent_t poll_ev[POLL_RING];
     for (int i = 0; i < POLL_RING; ++i) LDPC_TRY(prof_event(d, i, &poll_ev[i]));
     DecodeProf prof{d, st, POLL_RING};
@@ -959,7 +902,7 @@ int run(Decoder* d, const DecodeCall& k, const SimSource* sim = nullptr) {
 
     LDPC_TRY(prof.begin_decode());
     LDPC_HIP_TRY(hipMemsetAsync(xbits, 0, plane_words(tiles, n) * 8, st));
-    LDPC_HIP_TRY(hipMemsetAsync(tflags, 0, (size_t)tiles * 16 + 64 + POLL_RING * 16, st));
+    LDPC_HIP_TRY(hipMemsetAsync(tflags, 0, (size_t)tiles * 16 + 64 + POLL_RING_BYTES, st));
     LDPC_HIP_TRY(hipMemsetAsync(iters, 0, (size_t)B * sizeof(int32_t), st));
     if (k.soft && !LAYERED) LDPC_HIP_TRY(hipMemsetAsync(marg, 0, (size_t)tiles * n * 64 * sizeof(T), st));  // frames that never sweep report 0
     if (sim) {  // device Monte-Carlo over BI-AWGN: the noise goes straight into the tile layout
@@ -969,84 +912,43 @@ int run(Decoder* d, const DecodeCall& k, const SimSource* sim = nullptr) {
     if (!sim)
         hipLaunchKernelGGL((k_load_tile<T>), dim3((n + 63) / 64, tiles), dim3(256), 0, st, (const T*)k.priors, y0, B, n, LAYERED ? marg : prior, xbits);
     if constexpr (ALG == ALG_QMSA) launch_quantise<T>(g.rule, prior, (int64_t)tiles * n * 64, st);  // priors -> levels, in the workspace
-    hipLaunchKernelGGL(k_init_live, dim3((tiles + 255) / 256), dim3(256), 0, st, live, B, tiles);
+    tiles_init_live(live, B, tiles, st);
 
     const int cap = max_iter > 0 ? max_iter : 100000;  // max_iter <= 0 == unlimited upstream (src/bpa.py:28); bounded here
-    // how often the live counters are polled: about every 300 us of streaming work
-    const double iter_us = 15.0 + (double)tiles * 64.0 * sizeof(T) * (4.0 * E + n) / 5.0e6;
-    int poll_every = (int)(300.0 / iter_us);
-    poll_every = poll_every < 1 ? 1 : (poll_every > 16 ? 16 : poll_every);
-    int cur_tiles = tiles;
-    int repacks = 0;
-    int sweeps = 0;
-    int polls = 0;
+    const double bytes_per_frame = sizeof(T) * (4.0 * E + n);
+    SweepPolls p{st, (int*)((char*)d->flags.p + (size_t)tiles * 16 + 64), (volatile int*)d->pinned, poll_ev, repack, cap, tiles, bytes_per_frame};
+    p.poll_every = SweepPolls::poll_every_300us(tiles, bytes_per_frame);
+    p.every_sweep = p.eager = max_iter <= 0;  // an unbounded run polls at every sweep and reads at once
     const T *gather_msg = nullptr, *gather_marg = nullptr, *gather_prior = nullptr;  // non-null: the next sweep carries a folded repack out of that set
-    std::vector<PendingPoll> pending;
-    bool all_left = false;
-    for (int it = 0; it < cap && !all_left; ++it) {
-        const bool check = early && (it > 0 || y0 != nullptr);
-        if (check) {
-            const bool poll = (it % poll_every) == 0 || max_iter <= 0;
-            int* slot_dev = nullptr;
-            int slot = 0;
-            if (poll) {
-                slot = polls % POLL_RING;
-                slot_dev = poll_dev + 4 * slot;
-                LDPC_HIP_TRY(hipMemsetAsync(slot_dev, 0, 2 * sizeof(int), st));
-            }
-            launch_syndrome(c, k, xbits, live, tflags, slot_dev, cur_tiles, sweeps, fmap);
-            if (poll) {
-                LDPC_HIP_TRY(hipMemcpyAsync((void*)(poll_host + 4 * slot), slot_dev, 2 * sizeof(int), hipMemcpyDeviceToHost, st));
-                LDPC_HIP_TRY(hipEventRecord(poll_ev[slot], st));
-                pending.push_back({slot, it, sweeps, cur_tiles, true});
-                ++polls;
-                // Read the OLDEST poll once a newer one is enqueued behind it (its event has long fired: a block of sweeps lies in
-                // between); with a single-tile batch, or an unbounded run, there is nothing to overlap and the newest is read at once.
-                // LONG sweeps (more than ~1.5 ms of streaming work: n = 64 800 x 512 tiles is 19 ms) also read the newest at once: the
-                // host round trip is a percent of one sweep, and the repack decision then rests on the live counts of THIS check point
-                // instead of those of a sweep ago -- while frames leave by the thousand per sweep (profiles/r05_config5_timeline.txt).
-                const double sweep_us_now = (double)cur_tiles * 64.0 * sizeof(T) * (4.0 * E + n) / 5.0e6;
-                const bool eager = max_iter <= 0 || cur_tiles < 2 || sweep_us_now > 1500.0;
-                while (!pending.empty() && (pending.size() >= 2 || eager)) {
-                    const PendingPoll pp = pending.front();
-                    pending.erase(pending.begin());
-                    LDPC_HIP_TRY(hipEventSynchronize(poll_ev[pp.slot]));
-                    const int lt = poll_host[4 * pp.slot], lf = poll_host[4 * pp.slot + 1];
-                    if (lt == 0) {  // every frame had left at that check point; what was enqueued since found no live tile
-                        all_left = true;
-                        sweeps = pp.sweeps;
-                        break;
-                    }
-                    if (repack.on && pp.tiling_current && pp.it > 0 && repack.wants(lt, lf) && it + 1 < cap) {
-                        const int nt = (lf + 63) / 64;
-                        const TileSet& to = set[1 - cur];
-                        // the decisions of every frame of the old tiles (those that left keep them; the moved ones overwrite theirs later)
-                        launch_unpack(k, xbits, n, cur_tiles, fmap);
-                        hipLaunchKernelGGL(k_repack_plan, dim3(1), dim3(1024), 0, st, live, cur_tiles, (int32_t*)d->rbase.p);
-                        if (fold_repack) {
-                            // only the map now; the sweep enqueued below moves the state (GATHER passes: old set in, new set out)
-                            hipLaunchKernelGGL(k_repack_map, dim3(nt), dim3(64), 0, st, live, (u64*)to.live.p, (const int32_t*)d->rbase.p, fmap,
-                                               (int32_t*)to.fmap.p, (int32_t*)d->rmap.p, cur_tiles);
-                            gather_msg = msg;
-                            gather_marg = marg;
-                            gather_prior = prior;
-                        } else {
-                            const int rows_per_wave = 128;
-                            const int chunks = (int)((E + n + rows_per_wave - 1) / rows_per_wave);
-                            hipLaunchKernelGGL((k_repack<T, !LAYERED>), dim3((chunks + 3) / 4, nt), dim3(64, 4), 0, st, msg, (T*)to.edge.p, marg, (T*)to.node.p, prior,
-                                               (T*)to.prior.p, xbits, (u64*)to.planes.p, live, (u64*)to.live.p, (const int32_t*)d->rbase.p, fmap,
-                                               (int32_t*)to.fmap.p, cur_tiles, n, E, rows_per_wave);
-                        }
-                        use_set(1 - cur);
-                        fmap = (int32_t*)to.fmap.p;
-                        cur_tiles = nt;
-                        g.tiles = nt;
-                        ++repacks;
-                        for (PendingPoll& q : pending) q.tiling_current = false;
-                    }
-                }
-                if (all_left) break;
-            }
+    const auto syndrome = [&](int* slot_dev) { tiles_syndrome(c, xbits, live, tflags, iters, slot_dev, B, p.cur_tiles, p.sweeps, fmap, st); };
+    const auto repack_into = [&](int nt) {
+        const TileSet& to = set[1 - cur];
+        // the decisions of every frame of the old tiles (those that left keep them; the moved ones overwrite theirs later)
+        launch_unpack(k, xbits, n, p.cur_tiles, fmap);
+        hipLaunchKernelGGL(k_repack_plan, dim3(1), dim3(1024), 0, st, live, p.cur_tiles, (int32_t*)d->rbase.p);
+        if (fold_repack) {
+            // only the map now; the sweep enqueued below moves the state (GATHER passes: old set in, new set out)
+            hipLaunchKernelGGL(k_repack_map, dim3(nt), dim3(64), 0, st, live, (u64*)to.live.p, (const int32_t*)d->rbase.p, fmap, (int32_t*)to.fmap.p,
+                               (int32_t*)d->rmap.p, p.cur_tiles);
+            gather_msg = msg;
+            gather_marg = marg;
+            gather_prior = prior;
+        } else {
+            const int rows_per_wave = 128;
+            const int chunks = (int)((E + n + rows_per_wave - 1) / rows_per_wave);
+            hipLaunchKernelGGL((k_repack<T, !LAYERED>), dim3((chunks + 3) / 4, nt), dim3(64, 4), 0, st, msg, (T*)to.edge.p, marg, (T*)to.node.p, prior,
+                               (T*)to.prior.p, xbits, (u64*)to.planes.p, live, (u64*)to.live.p, (const int32_t*)d->rbase.p, fmap, (int32_t*)to.fmap.p,
+                               p.cur_tiles, n, E, rows_per_wave);
+        }
+        use_set(1 - cur);
+        fmap = (int32_t*)to.fmap.p;
+        g.tiles = nt;
+        return nt;
+    };
+    for (int it = 0; it < cap && !p.all_left; ++it) {
+        if (early && (it > 0 || y0 != nullptr)) {
+            LDPC_TRY(p.check_point(it, syndrome, repack_into));
+            if (p.all_left) break;
         }
         LDPC_TRY(prof.mark(0));
         if constexpr (LAYERED) {
@@ -1065,15 +967,13 @@ int run(Decoder* d, const DecodeCall& k, const SimSource* sim = nullptr) {
             dispatch_vn<T, ALG>(c, msg, prior, marg, live, xbits, g, st);
         }
         LDPC_TRY(prof.mark(2));
-        ++sweeps;
+        ++p.sweeps;
     }
-    launch_decisions(k, xbits, live, n, cur_tiles, sweeps, fmap);
+    launch_decisions(k, xbits, live, n, p.cur_tiles, p.sweeps, fmap);
     if (k.soft && LAYERED) hipLaunchKernelGGL(k_soft_out_swept<T>, dim3((n + 3) / 4, tiles), dim3(256), 0, st, marg, (const int32_t*)iters, (T*)k.soft, B, n);
     if (k.soft && !LAYERED) hipLaunchKernelGGL(k_soft_out<T>, dim3((n + 3) / 4, tiles), dim3(256), 0, st, marg, (T*)k.soft, B, n);
-    // polls still in flight copy into the pinned ring; the next decode of this handle may run on another stream and reuse the slots:
-    // let the last copy land first (everything of this decode is enqueued by now, the GPU is not waiting for the host)
-    if (!pending.empty()) LDPC_HIP_TRY(hipEventSynchronize(poll_ev[pending.back().slot]));
-    return end_decode(d, prof, sweeps, repacks);
+    LDPC_TRY(p.finish());
+    return end_decode(d, prof, p.sweeps, p.repacks);
 }
 
 }  // namespace
@@ -1392,7 +1292,7 @@ int run16(Decoder* d, const DecodeCall& k, const SimSource* sim) {
     // Frame repack (k_repack16; policy of the fp32 passes): the live frames are gathered into dense pair-tiles
     RepackPolicy repack(early && soft_out == nullptr && tiles0 >= 4);
     if (repack.on) {
-        const size_t np2 = ((size_t)(repack.fill * tiles0) + 2 + 1) / 2;  // pairs of the second set: the first repack fires at <= fill * tiles
+        const size_t np2 = (repack.target_tiles(tiles0) + 1) / 2;  // pairs of the second set
         if (set[1].edge.reserve(np2 * E * 64 * sizeof(__half2)) || set[1].prior.reserve(np2 * n * 64 * sizeof(float2)) ||
             set[1].planes.reserve(plane_words((int)(2 * np2), n) * 8) || set[1].live.reserve(2 * np2 * 8) || set[1].fmap.reserve(2 * np2 * 64 * sizeof(int32_t)) ||
             set[0].fmap.reserve(2 * np2 * 64 * sizeof(int32_t)) || d->rbase.reserve(((size_t)tiles0 + 2) * sizeof(int32_t)))
@@ -1409,7 +1309,7 @@ int run16(Decoder* d, const DecodeCall& k, const SimSource* sim) {
     LDPC_TRY(set[0].prior.reserve((size_t)pairs * n * 64 * sizeof(float2)));
     LDPC_TRY(set[0].planes.reserve(plane_words(2 * pairs, n) * 8));
     LDPC_TRY(set[0].live.reserve((size_t)2 * pairs * 8));
-    LDPC_TRY(d->flags.reserve((size_t)2 * pairs * 16 + 64));
+    LDPC_TRY(d->flags.reserve((size_t)2 * pairs * 16 + 64 + POLL_RING_BYTES));
     __half2* msg = (__half2*)d->c2v16.p;
     float2* marg = soft_out ? (float2*)set[0].node.p : nullptr;
     int cur = 0;  // which set holds the state; the pointers below are re-read from it after a flip
@@ -1425,11 +1325,12 @@ int run16(Decoder* d, const DecodeCall& k, const SimSource* sim) {
         live = (u64*)set[s].live.p;
     };
     use_set(0);
-    u64* tflags = (u64*)d->flags.p;
-    int* live_tiles = (int*)((char*)d->flags.p + (size_t)2 * pairs * 16);
-    volatile int* poll_host = (volatile int*)d->pinned;
+    u64* tflags = (u64*)d->flags.p;  // [2 * pairs][2], the device poll ring behind them
+    hipEvent_t poll_ev[POLL_RING];
+    for (int i = 0; i < POLL_RING; ++i) LDPC_TRY(prof_event(d, i, &poll_ev[i]));
+    DecodeProf prof{d, st, POLL_RING};
     LDPC_HIP_TRY(hipMemsetAsync(xbits, 0, plane_words(2 * pairs, n) * 8, st));
-    LDPC_HIP_TRY(hipMemsetAsync(tflags, 0, (size_t)2 * pairs * 16 + 64, st));
+    LDPC_HIP_TRY(hipMemsetAsync(tflags, 0, (size_t)2 * pairs * 16 + 64 + POLL_RING_BYTES, st));
     LDPC_HIP_TRY(hipMemsetAsync(live, 0, (size_t)2 * pairs * 8, st));
     LDPC_HIP_TRY(hipMemsetAsync(iters, 0, (size_t)B * sizeof(int32_t), st));
     if (marg) LDPC_HIP_TRY(hipMemsetAsync(marg, 0, (size_t)pairs * n * 64 * sizeof(float2), st));  // frames that never sweep report 0
@@ -1440,48 +1341,38 @@ int run16(Decoder* d, const DecodeCall& k, const SimSource* sim) {
         hipLaunchKernelGGL(k_load_tile16, dim3((n + 63) / 64, pairs), dim3(256), 0, st, (const float*)k.priors, y0, B, n, prior, xbits);
     }
     if constexpr (ALG == ALG_QMSA) launch_quantise<float>(rule, reinterpret_cast<float*>(prior), (int64_t)pairs * n * 128, st);  // priors -> levels
-    hipLaunchKernelGGL(k_init_live, dim3((tiles + 255) / 256), dim3(256), 0, st, live, B, tiles);
-    int repacks = 0;
+    tiles_init_live(live, B, tiles, st);
     const int cpw = 4, vpw = 16;
     const int cn_chunks = (m + cpw - 1) / cpw, vn_chunks = (n + vpw - 1) / vpw;
     const int cap = max_iter > 0 ? max_iter : 100000;
-    // the live counters are read (synchronously) every fourth sweep; every sweep where a sweep is more than ~1.5 ms of streaming work
+    // the live counters are read at once, every fourth sweep; every sweep where a sweep is more than ~1.5 ms of streaming work
     // (the round trip is then a percent of it, and frames leave by the thousand per sweep: the repack should not wait three sweeps)
-    const int poll_every = (double)tiles * 64.0 * (8.0 * E + 4.0 * n) / 5.0e6 > 1500.0 ? 1 : 4;
-    DecodeProf prof{d, st, 0};
-    int sweeps = 0;
-    bool all_left = false;
-    for (int it = 0; it < cap && !all_left; ++it) {
+    const double bytes_per_frame = 8.0 * E + 4.0 * n;
+    SweepPolls p{st, (int*)((char*)d->flags.p + (size_t)2 * pairs * 16 + 64), (volatile int*)d->pinned, poll_ev, repack, cap, tiles, bytes_per_frame};
+    p.poll_every = sweep_us(tiles, bytes_per_frame) > 1500.0 ? 1 : 4;
+    p.eager = true;
+    const auto syndrome = [&](int* slot_dev) { tiles_syndrome(c, xbits, live, tflags, iters, slot_dev, B, tiles, p.sweeps, fmap, st); };
+    const auto repack_into = [&](int nt) {
+        const int np = (nt + 1) / 2;
+        const TileSet& to = set[1 - cur];
+        // the decisions of every frame of the old tiles (those that left keep them; the moved ones overwrite theirs at the end)
+        launch_unpack(k, xbits, n, tiles, fmap);
+        hipLaunchKernelGGL(k_repack_plan, dim3(1), dim3(1024), 0, st, live, tiles, (int32_t*)d->rbase.p);
+        const int rows_per_wave = 128;
+        const int chunks = (int)((E + n + rows_per_wave - 1) / rows_per_wave);
+        hipLaunchKernelGGL(k_repack16, dim3((chunks + 3) / 4, np), dim3(64, 4), 0, st, v2c, (__half2*)to.edge.p, prior, (float2*)to.prior.p, xbits,
+                           (u64*)to.planes.p, live, (u64*)to.live.p, (const int32_t*)d->rbase.p, (const int32_t*)fmap, (int32_t*)to.fmap.p, tiles, n, E,
+                           rows_per_wave);
+        use_set(1 - cur);
+        fmap = (int32_t*)to.fmap.p;
+        pairs = np;
+        tiles = 2 * np;  // (an odd tile count leaves the last pair's second tile without a live frame)
+        return tiles;
+    };
+    for (int it = 0; it < cap && !p.all_left; ++it) {
         if (early && (it > 0 || y0 != nullptr)) {
-            const bool poll = (it % poll_every) == 0;
-            if (poll) LDPC_HIP_TRY(hipMemsetAsync(live_tiles, 0, 2 * sizeof(int), st));
-            launch_syndrome(c, k, xbits, live, tflags, poll ? live_tiles : nullptr, tiles, sweeps, fmap);
-            if (poll) {
-                LDPC_HIP_TRY(hipMemcpyAsync((void*)poll_host, live_tiles, 2 * sizeof(int), hipMemcpyDeviceToHost, st));
-                LDPC_HIP_TRY(hipStreamSynchronize(st));
-                const int lt = poll_host[0], lf = poll_host[1];  // tiles that still hold a live frame, live frames
-                if (lt == 0) {
-                    all_left = true;
-                    break;
-                }
-                if (repack.on && it > 0 && repack.wants(lt, lf) && it + 1 < cap) {
-                    const int nt = (lf + 63) / 64, np = (nt + 1) / 2;
-                    const TileSet& to = set[1 - cur];
-                    // the decisions of every frame of the old tiles (those that left keep them; the moved ones overwrite theirs at the end)
-                    launch_unpack(k, xbits, n, tiles, fmap);
-                    hipLaunchKernelGGL(k_repack_plan, dim3(1), dim3(1024), 0, st, live, tiles, (int32_t*)d->rbase.p);
-                    const int rows_per_wave = 128;
-                    const int chunks = (int)((E + n + rows_per_wave - 1) / rows_per_wave);
-                    hipLaunchKernelGGL(k_repack16, dim3((chunks + 3) / 4, np), dim3(64, 4), 0, st, v2c, (__half2*)to.edge.p, prior, (float2*)to.prior.p, xbits,
-                                       (u64*)to.planes.p, live, (u64*)to.live.p, (const int32_t*)d->rbase.p, (const int32_t*)fmap, (int32_t*)to.fmap.p, tiles, n, E,
-                                       rows_per_wave);
-                    use_set(1 - cur);
-                    fmap = (int32_t*)to.fmap.p;
-                    pairs = np;
-                    tiles = 2 * np;  // (an odd tile count leaves the last pair's second tile without a live frame)
-                    ++repacks;
-                }
-            }
+            LDPC_TRY(p.check_point(it, syndrome, repack_into));
+            if (p.all_left) break;
         }
         LDPC_TRY(prof.mark(0));
         const dim3 cgrid(task_blocks(pairs, cn_chunks, 0)), vgrid(task_blocks(pairs, vn_chunks, 0)), blk(64, 4);
@@ -1498,11 +1389,12 @@ int run16(Decoder* d, const DecodeCall& k, const SimSource* sim) {
                                pairs, tiles, vn_chunks, vpw);
         });
         LDPC_TRY(prof.mark(2));
-        ++sweeps;
+        ++p.sweeps;
     }
-    launch_decisions(k, xbits, live, n, tiles, sweeps, fmap);
+    launch_decisions(k, xbits, live, n, tiles, p.sweeps, fmap);
     if (soft_out) hipLaunchKernelGGL(k_soft_out16, dim3((n + 3) / 4, pairs), dim3(256), 0, st, marg, soft_out, B, n);  // (no repack with a soft output)
-    return end_decode(d, prof, sweeps, repacks);
+    LDPC_TRY(p.finish());
+    return end_decode(d, prof, p.sweeps, p.repacks);
 }
 
 bool batch_fits(int64_t B) {
