@@ -302,6 +302,37 @@ int ldpc_encode_random(ldpc_encoder_t enc, uint64_t seed, uint64_t stream_id, ui
 int ldpc_channel_sent(int channel, int dtype, double param, const uint8_t* sent_dev, uint64_t seed, uint64_t stream_id, uint64_t frame0,
                       int64_t B, int32_t n, void* priors_dev, uint8_t* y_dev, void* stream);
 
+/* ---- Punctured and shortened transmission (csrc/ldpc_ratematch.hip; no upstream counterpart) -------------------
+ * A transmission pattern is one byte per variable of the mother code, kind_dev [n] uint8:
+ *   0  sent
+ *   1  punctured: a codeword bit that is not transmitted; the decoder starts it from a prior of 0
+ *   2  shortened: a filler bit known to be 0 and not transmitted; the decoder starts it from the prior +short_llr
+ * (a byte above 2 is not a kind; both entry points read it as shortened).
+ * No decoder changes: the pattern lives in what the channel writes and in what the tally counts.  The channel parameter keeps its
+ * meaning PER TRANSMITTED SYMBOL (sigma^2 = 10^(-snr/10), src/biawgn.py:10); no rate correction is applied.
+ *
+ * ldpc_channel_pattern: LDPC_CH_BIAWGN and LDPC_CH_BSC, dtype fp32 / fp64, frames [frame0, frame0 + B); one thread = 4 consecutive
+ * variables = one Philox block, as ldpc_channel.  sent_dev [B, n] uint8 is the word of every frame, or NULL for the all-`codeword` word.
+ *   kind 0   the outputs of ldpc_channel_sent (sent_dev NULL: of ldpc_channel(codeword)) for the same (seed, stream_id, global frame,
+ *            variable), draw for draw and bit for bit: the Philox block and word of a variable are those of its index in the mother
+ *            code, so a pattern moves the noise of no other bit
+ *   kind 1   prior +0.0; y = 0 on the BSC
+ *   kind 2   prior +short_llr (positive = bit 0, as -2y/sigma^2); y = 0
+ * short_llr must be finite and > 0; 32.0 wherever the package exposes it (a power of two: exact on every prior grid and under the
+ * fixed-point quantisers; below |v| ~ 38.2, from where the verbatim fp64 sum-product's tanh is exactly 1.0).  priors_dev / y_dev as
+ * ldpc_channel_sent.  kind_dev is read as dwords, and the outputs written as float4 / double2, when n % 4 == 0 and every buffer lies on
+ * its natural boundary; as bytes and scalars otherwise.  LDPC_E_ARG, each with a sentence that names this entry point: sent_dev NULL with
+ * codeword == 1 and any shortened variable (that word is no codeword of the shortened code; to find out, EVERY call with sent_dev NULL and
+ * codeword == 1 copies kind_dev to the host and waits for `stream` -- a caller that knows its pattern passes words of ones in sent_dev
+ * and keeps the stream asynchronous, as _device.PatternHandle does), LDPC_CH_BEC, LDPC_CH_RAW_OBSERVATION, LDPC_CH_PRIOR_GRID, a short_llr out of range. */
+int ldpc_channel_pattern(int channel, int dtype, double param, const uint8_t* sent_dev, int codeword, const uint8_t* kind_dev, double short_llr,
+                         uint64_t seed, uint64_t stream_id, uint64_t frame0, int64_t B, int32_t n, void* priors_dev, uint8_t* y_dev, void* stream);
+/* The counters of ldpc_count_errors, ACCUMULATED into counters_dev, with a frame's errors taken over the variables of kind < 2: a
+ * punctured bit is a codeword bit and is counted, a shortened bit is known and is not.  sent_dev [B, n] (one word PER FRAME, as
+ * ldpc_count_errors_words) or NULL for the all-`codeword` word; iters_dev may be NULL.  One wave per frame, as ldpc_count_errors. */
+int ldpc_count_errors_pattern(const uint8_t* xhat_dev, const uint8_t* sent_dev, int codeword, const uint8_t* kind_dev, const int32_t* iters_dev,
+                              int64_t B, int32_t n, int32_t hist_bins, int64_t* counters_dev, void* stream);
+
 /* ---- Maximum-likelihood decoding of the short codes by codebook search -----------------------------------------
  * Replaces biawgn.ML (src/biawgn.py:66-78), bsc.ML (src/bsc.py:63-75) and bec.ML (src/bec.py:21-36).  `codebook` is
  * Code.cb (src/codes.py:11-14): [K, n] bytes in {0,1}, host pointer, K <= 2^20 words of n <= 64 bits. */

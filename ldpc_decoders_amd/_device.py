@@ -142,6 +142,40 @@ def channel_sent(channel, precision, param, sent, seed, stream_id, frame0, prior
     return pri, y
 
 
+def channel_pattern(channel, precision, param, sent, codeword, kind, short_llr, seed, stream_id, frame0, B=None):
+    """``ldpc_channel_pattern``: the channel of ``channel_sent`` under a transmission pattern, ``kind`` CUDA uint8 [n] (0 sent, 1 punctured:
+    prior +0.0, 2 shortened: prior +short_llr).  ``sent`` CUDA uint8 [B, n], or None for ``B`` frames of the all-``codeword`` word.
+    -> (priors in ``precision``, y or None)"""
+    import torch
+
+    n = kind.shape[0]
+    B = int(B) if sent is None else sent.shape[0]
+    dt = torch.float64 if precision == "f64" else torch.float32
+    pri = torch.empty((B, n), dtype=dt, device=kind.device)
+    y = None if channel == "biawgn" else torch.empty((B, n), dtype=torch.uint8, device=kind.device)
+    st = torch.cuda.current_stream(kind.device).cuda_stream
+    _lib.check(_lib.load().ldpc_channel_pattern(_lib.CHANNEL[channel], _lib.IO_DTYPE[precision], float(param), None if sent is None else sent.data_ptr(),
+                                                int(codeword), kind.data_ptr(), float(short_llr), int(seed), int(stream_id), int(frame0), B, n,
+                                                pri.data_ptr(), None if y is None else y.data_ptr(), st))
+    return pri, y
+
+
+def decode_drawn(handle, draw, max_iter, flags):
+    """The decode of given words, stated once for every LLR handle class (``DecoderHandle``, ``OsdHandle``, ``LqmsaHandle`` and its
+    subclasses): -> ``decode(sent, first frame)`` -> (xhat, iters), which asks ``draw(precision, sent, first)`` -- ``channel_sent``, or
+    ``channel_pattern`` under a transmission pattern -- for (priors, y) in the handle's precision and hands them to its ``decode_device``."""
+    def decode(sent, first):
+        pri, y = draw(handle.precision, sent, first)
+        return handle.decode_device(pri, y, max_iter, flags)[:2]
+
+    return decode
+
+
+def draw_sent(channel, param, seed, stream_id):
+    """The ``draw`` of ``decode_drawn`` without a pattern: ``channel_sent`` of the words."""
+    return lambda precision, sent, first: channel_sent(channel, precision, param, sent, seed, stream_id, first)
+
+
 def simulate_random_codewords(code, device, seed, stream_id, frame0, B, chunk, counters, hist_bins, decode):
     """``codeword == -1`` for a code without a code book, stated once for every handle class: frames [frame0, frame0 + B) in chunks of
     ``chunk`` (the class's ``words_chunk``), each a random codeword from the systematic encoder (``Code.encoder()``) ->
@@ -371,12 +405,8 @@ class DecoderHandle(FixedPointLayers, FamilyHandle):
         if getattr(self, "_cb_dev", None) is None:
             cb = getattr(self.code, "cb", None)
             if cb is None:
-                def decode(sent, first):
-                    pri, y = self.channel_sent_device(channel, param, sent, seed, stream_id, first)
-                    return self.decode_device(pri, y, max_iter, flags)
-
                 return simulate_random_codewords(self.code, self.code_handle.device, seed, stream_id, frame0, B, self.words_chunk(channel),
-                                                 counters, hist_bins, decode)
+                                                 counters, hist_bins, decode_drawn(self, draw_sent(channel, param, seed, stream_id), max_iter, flags))
             self._cb_dev = torch.from_numpy(np.ascontiguousarray(cb, dtype=np.uint8)).cuda()
         n, K = self.code.n, int(self._cb_dev.shape[0])
         dt = torch.float64 if self.precision == "f64" else torch.float32
@@ -715,11 +745,8 @@ class OsdHandle(FamilyHandle):
                                              int(frame0), int(B), int(max_iter), flags, self.order, self.depth, hist_bins, counters.data_ptr(), st))
             return
 
-        def decode(sent, first):
-            pri, y = self.bp.channel_sent_device(channel, param, sent, seed, stream_id, first)
-            return self.decode_device(pri, y, max_iter, flags)[:2]
-
-        simulate_random_codewords(self.code, self.device, seed, stream_id, frame0, B, self.words_chunk(channel), counters, hist_bins, decode)
+        simulate_random_codewords(self.code, self.device, seed, stream_id, frame0, B, self.words_chunk(channel), counters, hist_bins,
+                                  decode_drawn(self, draw_sent(channel, param, seed, stream_id), max_iter, flags))
 
 
 class HardHandle(FamilyHandle):
@@ -816,6 +843,7 @@ class LqmsaHandle(FixedPointLayers, FamilyHandle):
     """Layered fixed-point min-sum with the frame resident in the LDS as integers (``ldpc_lqmsa_*``): one workgroup per frame, int16
     marginals, int8 check messages; priors in fp32 or fp64, quantised on load."""
     family = "ldpc_lqmsa"  # the handle family of the C ABI the calls below go to (QcHandle: the same call shapes under ldpc_qc_*)
+    precision = "f32"  # the type ``simulate`` draws its priors in (``decode_device`` takes fp32 and fp64; the integers are the same)
 
     def __init__(self, code, device=None, bits=6, frac_bits=2, scale=0.8125, offset=0):
         self._create_on_code(code, device)
@@ -867,11 +895,8 @@ class LqmsaHandle(FixedPointLayers, FamilyHandle):
                                             int(B), int(max_iter), flags, hist_bins, counters.data_ptr(), st))
             return
 
-        def decode(sent, first):
-            pri, y = channel_sent(channel, "f32", param, sent, seed, stream_id, first)
-            return self.decode_device(pri, y, max_iter, flags)
-
-        simulate_random_codewords(self.code, self.device, seed, stream_id, frame0, B, self.words_chunk(channel), counters, hist_bins, decode)
+        simulate_random_codewords(self.code, self.device, seed, stream_id, frame0, B, self.words_chunk(channel), counters, hist_bins,
+                                  decode_drawn(self, draw_sent(channel, param, seed, stream_id), max_iter, flags))
 
     def words_chunk(self, channel):
         return max(2048, min(1 << 17, (1 << 26) // self.code.n))
@@ -1032,3 +1057,102 @@ class AdmmHandle(FamilyHandle):
                 counters[_lib.CNT_HIST0:_lib.CNT_HIST0 + hist_bins] += torch.bincount(iters.clamp(max=hist_bins - 1).long(), minlength=hist_bins)
             if self.on_iters is not None:
                 self.on_iters(iters)
+
+
+def check_pattern_run(channel, exact=False, prior_grid=None):
+    """What a transmission pattern cannot be combined with -- ValueError, before any device call."""
+    if channel == "bec":
+        raise ValueError("a transmission pattern works on the LLR channels (biawgn, bsc): over the bec a punctured bit is simply an erased one")
+    if exact:
+        raise ValueError("--exact draws its noise on the host for every bit of the mother code and has no transmission pattern")
+    if prior_grid is not None:
+        raise ValueError("--prior-grid: the exactness guard vouches for the priors the fused kernel draws itself; a transmission pattern draws them outside it")
+
+
+class PatternHandle:
+    """A transmission pattern (``ratematch.Pattern``) around the handle of an LLR decoder: ``simulate`` in the call shape of
+    ``DecoderHandle.simulate``, so ``montecarlo.DeviceSimulator`` and the multi-GPU driver take it as they take ``inner``.  Per chunk of
+    ``inner.words_chunk(channel)`` frames: the sent words (``codeword == -1``; none for the all-zero / all-one word) ->
+    ``ldpc_channel_pattern`` in the inner handle's precision -> the inner handle's decode of given priors (``decode_drawn``) ->
+    ``ldpc_count_errors_pattern``.  Every draw is keyed by the global frame index, so sharding and chunking change no counter.
+
+    Served: ``DecoderHandle`` (SPA, MSA, NMSA, QMSA, LMSA), ``OsdHandle``, ``LqmsaHandle``, ``QcHandle``, ``SlqHandle``.  Refused
+    (ValueError, before any device call): ``HardHandle``, ``AdmmHandle``, ``MlHandle``, ``BecMlHandle``, the erasure decoder, the bec channel
+    and the prior-grid flag."""
+    CHUNK = None  # frames per chunk; None: ``inner.words_chunk(channel)`` (a test forces a small one here)
+    REFUSED = ((HardHandle, "a hard-decision decoder passes one bit per message and has no erasure to start a punctured bit from"),
+               (AdmmHandle, "the ADMM decoder has no transmission pattern: it is the LLR decoders (SPA, MSA and the min-sum variants, OSD) that take one"),
+               (MlHandle, "codebook ML has no transmission pattern: it is the LLR decoders (SPA, MSA and the min-sum variants, OSD) that take one"),
+               (BecMlHandle, "ML over the erasure channel has no transmission pattern: a punctured bit is simply an erased one there"))
+
+    def __init__(self, inner, pattern, short_llr=32.0):
+        for cls, why in self.REFUSED:
+            if isinstance(inner, cls):
+                raise ValueError(why)
+        if not isinstance(inner, (DecoderHandle, OsdHandle, LqmsaHandle)) or getattr(inner, "alg", None) == "BEC":
+            raise ValueError("a transmission pattern wraps the handle of an LLR decoder (DecoderHandle but the erasure decoder, OsdHandle, LqmsaHandle, QcHandle, SlqHandle)")
+        if pattern.n != inner.code.n:
+            raise ValueError("a pattern of %d variables on a code of %d" % (pattern.n, inner.code.n))
+        short_llr = float(short_llr)
+        if not 0.0 < short_llr < float("inf"):
+            raise ValueError("short_llr must be finite and > 0 (got %r)" % short_llr)
+        self.inner, self.pattern, self.short_llr = inner, pattern, short_llr
+        self.code, self.device, self.precision = inner.code, inner.code_handle.device, inner.precision
+
+    def kind_device(self):
+        """The pattern's ``kind`` as a CUDA uint8 tensor [n] on the handle's device, kept on the handle."""
+        import torch
+
+        if getattr(self, "_kind_dev", None) is None:
+            self._kind_dev = torch.from_numpy(self.pattern.kind).to(torch.device("cuda", self.device))
+        return self._kind_dev
+
+    def ones_words(self, B):
+        """``B`` all-one words, CUDA uint8 [B, n] (kept, grown on demand): what ``codeword == 1`` hands to ``ldpc_channel_pattern``, which for
+        the all-one word without sent words would read the pattern back and wait for the stream at every call -- the check it makes
+        there (no shortened bit) is made on the host in ``simulate``."""
+        import torch
+
+        if getattr(self, "_ones", None) is None or self._ones.shape[0] < B:
+            self._ones = torch.ones((int(B), self.code.n), dtype=torch.uint8, device=torch.device("cuda", self.device))
+        return self._ones[:int(B)]
+
+    def sent_words(self, seed, stream_id, frame0, B):
+        """Random codewords of the shortened code for frames [frame0, frame0 + B), CUDA uint8 [B, n], zero on the shortened set: the words
+        of ``Code.encoder()`` of ``pattern.shortened_code(code)`` scattered through its index map; with no shortened bit exactly the
+        words of ``Code.encoder()`` of the code itself."""
+        import torch
+
+        if self.pattern.shortened.size == 0:
+            return self.code.encoder().handle(self.device).encode_random(seed, stream_id, frame0, B)
+        short, index = self.pattern.shortened_code(self.code)
+        words = short.encoder().handle(self.device).encode_random(seed, stream_id, frame0, B)
+        if getattr(self, "_index_dev", None) is None:
+            self._index_dev = torch.from_numpy(index).to(words.device)
+        return torch.zeros((int(B), self.code.n), dtype=torch.uint8, device=words.device).index_copy_(1, self._index_dev, words)
+
+    def simulate(self, channel, param, codeword, seed, stream_id, frame0, B, max_iter, counters, flags=0, hist_bins=0):
+        """Same call shape as DecoderHandle.simulate; ``counters`` (CUDA int64 [4 + hist_bins]) is accumulated into.  BEC counts the bit errors
+        over the sent and the punctured variables (``pattern.n_counted`` per frame)."""
+        import torch
+
+        check_pattern_run(channel, prior_grid=_lib.prior_grid_of_flags(flags))
+        codeword = int(codeword)
+        if codeword not in (-1, 0, 1):
+            raise ValueError("codeword is 0, 1 or -1 (a random codeword per frame)")
+        if codeword == 1 and self.pattern.shortened.size:
+            raise ValueError("the all-one word is no codeword of the shortened code")
+        if B <= 0:
+            return
+        lib, n, kind = _lib.load(), self.code.n, self.kind_device()
+        st = torch.cuda.current_stream(counters.device).cuda_stream
+        chunk = int(self.CHUNK or self.inner.words_chunk(channel))
+        last = int(frame0) + int(B)
+        decode = decode_drawn(self.inner, lambda precision, sent, first: channel_pattern(
+            channel, precision, param, sent, 0, kind, self.short_llr, seed, stream_id, first, min(chunk, last - first)), max_iter, flags)
+        for first in range(int(frame0), last, chunk):
+            nb = min(chunk, last - first)
+            sent = self.sent_words(seed, stream_id, first, nb) if codeword == -1 else None
+            xhat, iters = decode(self.ones_words(nb) if codeword == 1 else sent, first)
+            _lib.check(lib.ldpc_count_errors_pattern(xhat.data_ptr(), None if sent is None else sent.data_ptr(), max(codeword, 0), kind.data_ptr(),
+                                                     None if iters is None else iters.data_ptr(), nb, n, hist_bins, counters.data_ptr(), st))

@@ -27,6 +27,12 @@ def flag_prior_grid(k):
     return 0 if k is None else (int(k) + 1) << 8
 
 
+def prior_grid_of_flags(flags):
+    """The inverse of ``flag_prior_grid``: the k a flags word asks for (LDPC_FLAG_PRIOR_GRID_OF), or None."""
+    field = (int(flags) >> 8) & 0x1f
+    return field - 1 if field else None
+
+
 def ch_prior_grid(k):
     """LDPC_CH_PRIOR_GRID(k): the channel kernel rounds the LLRs it writes to multiples of 2^-k (None: off)."""
     return 0 if k is None else (int(k) + 1) << 12
@@ -90,6 +96,9 @@ SIGNATURES = {
     "ldpc_encode_random": (_c.c_int, [_P, _c.c_uint64, _c.c_uint64, _c.c_uint64, _c.c_int64, _P, _P]),
     "ldpc_channel_sent": (_c.c_int, [_c.c_int, _c.c_int, _c.c_double, _P, _c.c_uint64, _c.c_uint64, _c.c_uint64, _c.c_int64, _c.c_int32,
                                      _P, _P, _P]),
+    "ldpc_channel_pattern": (_c.c_int, [_c.c_int, _c.c_int, _c.c_double, _P, _c.c_int, _P, _c.c_double, _c.c_uint64, _c.c_uint64, _c.c_uint64,
+                                        _c.c_int64, _c.c_int32, _P, _P, _P]),
+    "ldpc_count_errors_pattern": (_c.c_int, [_P, _P, _c.c_int, _P, _P, _c.c_int64, _c.c_int32, _c.c_int32, _P, _P]),
     "ldpc_ml_create": (_c.c_int, [_c.c_int, _P, _c.c_int64, _c.c_int32, _c.POINTER(_P)]),
     "ldpc_ml_destroy": (_c.c_int, [_P]),
     "ldpc_ml_decode": (_c.c_int, [_P, _c.c_int, _c.c_int, _c.POINTER(_c.c_double), _P, _c.c_int64, _P, _P, _P, _P, _P, _P, _P]),

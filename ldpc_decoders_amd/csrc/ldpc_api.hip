@@ -18,6 +18,7 @@
 #include "ldpc_lqmsa.hpp"
 #include "ldpc_osd.hpp"
 #include "ldpc_qc.hpp"
+#include "ldpc_ratematch.hpp"
 #include "ldpc_sim.hpp"
 #include "ldpc_slq.hpp"
 
@@ -1133,6 +1134,21 @@ int ldpc_channel_sent(int channel, int dtype, double param, const uint8_t* sent_
                       int32_t n, void* priors_dev, uint8_t* y_dev, void* stream) {
     return guarded("ldpc_channel_sent", [&]() -> int {
         return channel_sent(channel, dtype, param, sent_dev, seed, stream_id, frame0, B, n, priors_dev, y_dev, (hipStream_t)stream);
+    });
+}
+
+int ldpc_channel_pattern(int channel, int dtype, double param, const uint8_t* sent_dev, int codeword, const uint8_t* kind_dev, double short_llr,
+                         uint64_t seed, uint64_t stream_id, uint64_t frame0, int64_t B, int32_t n, void* priors_dev, uint8_t* y_dev, void* stream) {
+    return guarded("ldpc_channel_pattern", [&]() -> int {
+        return channel_pattern(channel, dtype, param, sent_dev, codeword, kind_dev, short_llr, seed, stream_id, frame0, B, n, priors_dev, y_dev,
+                               (hipStream_t)stream);
+    });
+}
+
+int ldpc_count_errors_pattern(const uint8_t* xhat_dev, const uint8_t* sent_dev, int codeword, const uint8_t* kind_dev, const int32_t* iters_dev,
+                              int64_t B, int32_t n, int32_t hist_bins, int64_t* counters_dev, void* stream) {
+    return guarded("ldpc_count_errors_pattern", [&]() -> int {
+        return count_errors_pattern(xhat_dev, sent_dev, codeword, kind_dev, iters_dev, B, n, hist_bins, counters_dev, (hipStream_t)stream);
     });
 }
 

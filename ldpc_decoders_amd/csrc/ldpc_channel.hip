@@ -117,6 +117,7 @@ __global__ __launch_bounds__(256) void k_discrete(uint64_t thr, double llr, int 
 }
 
 // one wavefront per frame, grid-stride; counters are combined per block (LDS) before touching global atomics
+// (k_count_pattern, ldpc_ratematch.hip, is this body with the shortened bits left out: a change to the counters belongs in both)
 __global__ __launch_bounds__(256) void k_count(const uint8_t* __restrict__ xhat, const uint8_t* __restrict__ sent, int codeword,
                                                const int32_t* __restrict__ iters, int64_t B, int n, int hist_bins,
                                                unsigned long long* __restrict__ counters, int sent_per_frame) {

@@ -5,7 +5,8 @@
 Same positional/flag grammar, same logger names, same JSON result files (see ``utils``), so the arg-lines emitted by
 the reference's ``simulations.py`` run unchanged and ``graph.py`` reads the outputs.  Differences, all additive:
 frames are decoded in batches on the GPU (``--batch`` per round and rank, ``--seed`` for the device noise, ``--precision`` /
-``--backend`` for the kernels, ``--max-frames`` to stop a parameter whose error rate is too low to reach ``--min-wec``); ``--exact``
+``--backend`` for the kernels, ``--puncture`` / ``--shorten`` for a transmission pattern (``ratematch``), ``--max-frames`` to stop a
+parameter whose error rate is too low to reach ``--min-wec``); ``--exact``
 selects the reference-exact mode (host noise, sequential stopping rule, ``--np-seed``); under ``torchrun`` each rank drives one GPU
 and the counters are all-reduced once per round.
 """
@@ -15,10 +16,21 @@ from collections import OrderedDict
 
 import numpy as np
 
-from . import codes, dist, qc, utils
+from . import codes, dist, qc, ratematch, utils
+from ._device import PatternHandle, check_pattern_run
 from .models import all_decoder_names, models
 from .registry import BY_NAME
 from .montecarlo import DeviceSimulator, run_point_exact
+
+
+def run_ids(args, decoder_id_keys, pattern=None):
+    """-> (id keys, their values): what names a run -- its logger, its result file (``utils.Saver``) and the head of that file.  A
+    transmission pattern adds ``puncture`` / ``shorten``; without one the keys are exactly the reference's and the decoder's own."""
+    id_keys = ["channel", "code", "decoder", "codeword", "min_wec"] + list(decoder_id_keys)
+    id_val = [vars(args)[key] for key in id_keys]
+    if pattern is not None:  # (the canonical spec strings, block columns merged in, so two patterns never share a file; ``args`` stays as parsed)
+        id_keys, id_val = id_keys + ["puncture", "shorten"], id_val + [pattern.puncture_spec or "none", pattern.shorten_spec or "none"]
+    return id_keys, id_val
 
 
 def test(args, comm=None):
@@ -50,10 +62,32 @@ def test(args, comm=None):
             qc.check_pack(getattr(args, "qc_pack", 0), args.qc_lift, qc.frame_bytes(code, base))
         except ValueError as e:
             raise SystemExit("--qc-pack: %s" % e)
-    id_keys = ["channel", "code", "decoder", "codeword", "min_wec"] + dec_fac.id_keys
-    id_val = [vars(args)[key] for key in id_keys]
+    # a transmission pattern (--puncture / --shorten and their block-column forms; ratematch.Pattern): everything it cannot be combined with
+    # is refused here, before a decoder exists; without the flags nothing below differs from a run of the mother code
+    try:
+        pattern = ratematch.from_args(args, code)
+    except ValueError as e:
+        raise SystemExit("--puncture / --shorten: %s" % e)
+    if pattern is not None:
+        if not row.pattern:
+            raise SystemExit("--puncture / --shorten: %s takes no transmission pattern; the LLR decoders do (%s)"
+                             % (row.name, ", ".join(r.name for r in BY_NAME.values() if r.pattern)))
+        try:
+            check_pattern_run(args.channel, bool(args.exact), getattr(args, "prior_grid", None))
+        except ValueError as e:
+            raise SystemExit("--puncture / --shorten: %s" % e)
+        if not 0.0 < args.short_llr < float("inf"):
+            raise SystemExit("--short-llr must be finite and > 0")
+        if args.codeword == 1 and pattern.shortened.size:
+            raise SystemExit("--codeword 1: the all-one word is no codeword of a shortened code (a shortened bit is 0)")
+        lost = pattern.unrecoverable(code)
+        if lost.size:
+            raise SystemExit("--puncture: the punctured set contains a stopping set -- no BP decoder can recover variable %d (and %d more)"
+                             % (lost[0], lost.size - 1))
+    id_keys, id_val = run_ids(args, dec_fac.id_keys, pattern)
     log = logging.getLogger(".".join(utils.strl(id_val)))
     code_n = code.get_n()
+    n_counted = code_n if pattern is None else pattern.n_counted  # (a shortened bit is known: its errors are not counted, nor is it a bit of the BER)
     saver = utils.Saver(args.data_dir, list(zip(id_keys, id_val))) if comm.is_root else None
     # --codeword -1 (a random codeword per frame, src/main.py:38): on the device for the BP decoders -- from the code book where the code
     # has one, from the systematic GF(2) encoder (Code.encoder()) otherwise -- and for ML over the BEC of a code without a code book (the
@@ -97,7 +131,7 @@ def test(args, comm=None):
 
         def log_status(c, final=False):
             tot, wec, bec = c["tot"], c["wec"], c["bec"]
-            wer, ber = (wec / tot, bec / (tot * code_n)) if tot else (0., 0.)
+            wer, ber = (wec / tot, bec / (tot * n_counted)) if tot else (0., 0.)
             keys = ["tot", "wec", "wer", "bec", "ber"]
             vals = [int(tot), int(wec), float(wer), int(bec), float(ber)]
             if comm.is_root:
@@ -138,6 +172,8 @@ def test(args, comm=None):
             c = run_point_exact(channel, decoder, x, args.min_wec, chunk=chunk, on_progress=progress, pick_word=pick)
         else:
             handle = decoder.handle if hasattr(decoder, "handle") else decoder.dec.handle
+            if pattern is not None:
+                handle = PatternHandle(handle, pattern, args.short_llr)
             # a decoder that reports statistics (ADMM: iteration histogram, src/main.py:34) gets them from the REDUCED counters, so
             # that `dec` describes the same frames as tot/wec/bec -- the whole job, not rank 0's shard
             own_hist = hasattr(decoder, "stats") and hasattr(inner, "iter")

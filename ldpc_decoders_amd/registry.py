@@ -22,16 +22,17 @@ Row = namedtuple("Row", [
     "pops_layers",    # the ADMMA flag --layers must not reach it (to LMSA ``layers`` is a layering of the checks)
     "refuses_fused",  # --backend fused is refused before a decoder exists
     "hard",           # decodes hard decisions (one bit per message): words drawn on the device, no --precision f16, no --prior-grid, --max-iter >= 1
+    "pattern",        # takes a transmission pattern (--puncture / --shorten, ratematch.Pattern): its handle decodes LLR priors, so _device.PatternHandle wraps it
     "integer_layered",  # the LDS-resident integer kernel on the layered schedule: words drawn on the device, --layers dropped, no --precision f16, no --prior-grid, no --backend stream
     "integer_streamed",  # the integer kernels on the layered schedule with the state in HBM tiles: words drawn on the device, --layers dropped, no --precision f16, no --prior-grid, no --backend fused
     "quasi_cyclic",   # the shift-addressed integer kernel for quasi-cyclic codes: as integer_layered, and --qc-lift resolved to the code's lifting size
 ])
-Row.__new__.__defaults__ = (None, False, False, False, False, None, False, False, False, False, False, False)
+Row.__new__.__defaults__ = (None, False, False, False, False, None, False, False, False, False, False, False, False)
 
 ROWS = [
     Row("ML", "reference", {"biawgn": ml.BiawgnML, "bsc": ml.BscML}),
-    Row("SPA", "reference", bpa.SPA, osd_front=True, device_words=True, f16=True),
-    Row("MSA", "reference", bpa.MSA, osd_front=True, device_words=True, tie_dominated=True, f16=True, prior_grid=True),
+    Row("SPA", "reference", bpa.SPA, osd_front=True, device_words=True, f16=True, pattern=True),
+    Row("MSA", "reference", bpa.MSA, osd_front=True, device_words=True, tie_dominated=True, f16=True, prior_grid=True, pattern=True),
     Row("LP", "reference", None),
     Row("ADMM", "reference", admm.ADMM),
     Row("ADMMA", "reference", None),
@@ -39,25 +40,25 @@ ROWS = [
     Row("NMSA", "extra", bpa.NMSA,  # corrected (normalised / offset) min-sum
         ("Corrected min-sum has no meaning over the erasure channel: the ternary decoder has no magnitudes to scale or offset.",
          "decoder NMSA (corrected min-sum) does not exist over the bec: the erasure decoder has no magnitudes to correct; use SPA / MSA there"),
-        osd_front=True, device_words=True, tie_dominated=True, f16=True, prior_grid=False),
+        osd_front=True, device_words=True, tie_dominated=True, f16=True, prior_grid=False, pattern=True),
     Row("QMSA", "fixed_point", bpa.QMSA,  # fixed-point min-sum (q-bit saturating messages); its integers are the same in every arithmetic
         ("Fixed-point min-sum has no meaning over the erasure channel either: the ternary decoder has no magnitudes to quantise.",
          "decoder QMSA (fixed-point min-sum) does not exist over the bec: the erasure decoder has no magnitudes to quantise; use SPA / MSA there"),
-        osd_front=True, device_words=True, f16=True, prior_grid=False),
+        osd_front=True, device_words=True, f16=True, prior_grid=False, pattern=True),
     Row("LMSA", "layered", bpa.LMSA,  # layered (serial-C) corrected min-sum on the streaming kernels
         ("Layered min-sum is corrected min-sum on another schedule: it has no meaning over the erasure channel either.",
          "decoder LMSA (layered corrected min-sum) does not exist over the bec: the erasure decoder has no magnitudes to correct; use SPA / MSA there"),
-        osd_front=True, device_words=True, tie_dominated=True, prior_grid=False, pops_layers=True, refuses_fused=True),
+        osd_front=True, device_words=True, tie_dominated=True, prior_grid=False, pops_layers=True, refuses_fused=True, pattern=True),
     # LQMSA's contract with the integer state in HBM tiles, for the codes beyond the LDS; bec writes its own (refusing) class of this name
-    Row("SLQMSA", "streaming_fixed_point", layered.SLQMSA, integer_streamed=True),
+    Row("SLQMSA", "streaming_fixed_point", layered.SLQMSA, integer_streamed=True, pattern=True),
     Row("OSD", "post_processing", bpa.OSD,  # BP + ordered-statistics decoding of the frames BP fails on (NMSA in front)
         ("Ordered-statistics post-processing orders soft values; over the erasure channel ``ML`` (elimination of the erased bits) is exact.",
          "decoder OSD (BP + ordered-statistics post-processing) does not exist over the bec: use ML there, the elimination decoder is exact"),
-        device_words=True, tie_dominated=True, prior_grid=False, pops_layers=True),
+        device_words=True, tie_dominated=True, prior_grid=False, pops_layers=True, pattern=True),
     # LQMSA's contract on a quasi-cyclic code with the block rows as layers, shift-addressed; bec writes its own (refusing) class of this name
-    Row("QCMSA", "quasi_cyclic", qc.QCMSA, quasi_cyclic=True),
+    Row("QCMSA", "quasi_cyclic", qc.QCMSA, quasi_cyclic=True, pattern=True),
     # QMSA's integer rule on LMSA's schedule, the frame resident in the LDS as integers; bec writes its own (refusing) class of this name
-    Row("LQMSA", "layered_fixed_point", layered.LQMSA, integer_layered=True),
+    Row("LQMSA", "layered_fixed_point", layered.LQMSA, integer_layered=True, pattern=True),
     # hard-decision decoding of the received bits (bit-sliced Gallager-B); biawgn / bsc / bec write their own class of this name, as for ADMM
     Row("GALB", "hard_decision", hard.GALB, hard=True),
 ]

@@ -1,7 +1,7 @@
 """CLI flags, logging and the JSON result store -- mirror of the reference's ``src/utils.py:21-68,118-140``.
 
 The argument grammar (positional ``channel code decoder`` + ``--codeword --min-wec --params --max-iter ...``) and
-the result files (``<channel>-<code>-<decoder>-<codeword>-<min_wec>-<max_iter>.json``; NMSA, LMSA: ``...-<max_iter>-<msa_scale>-<msa_offset>.json``; QMSA, LQMSA, SLQMSA: ``...-<max_iter>-<msa_bits>-<msa_frac_bits>-<msa_scale>-<msa_offset>.json``; QCMSA: the same followed by ``-<qc_lift>``; OSD: ``...-<max_iter>-<msa_scale>-<msa_offset>-<osd_order>-<osd_depth>.json``; GALB: ``...-<max_iter>-<gal_threshold>.json``; with the id keys first, then
+the result files (``<channel>-<code>-<decoder>-<codeword>-<min_wec>-<max_iter>.json``; NMSA, LMSA: ``...-<max_iter>-<msa_scale>-<msa_offset>.json``; QMSA, LQMSA, SLQMSA: ``...-<max_iter>-<msa_bits>-<msa_frac_bits>-<msa_scale>-<msa_offset>.json``; QCMSA: the same followed by ``-<qc_lift>``; OSD: ``...-<max_iter>-<msa_scale>-<msa_offset>-<osd_order>-<osd_depth>.json``; GALB: ``...-<max_iter>-<gal_threshold>.json``; under a transmission pattern (``--puncture`` / ``--shorten``) every name is followed by ``-<puncture>-<shorten>``; with the id keys first, then
 ``tot wec wer bec ber`` as ``{str(param): value}``) are what ``simulations.py`` / ``run_sims.sh`` emit and what
 ``graph.py`` reads upstream (src/graph.py:25-58), so flag names, defaults and the file layout are kept; the help texts are
 this build's own.  ``--mu --eps --allow-pseudo`` configure the ADMM decoder; ``--layers --train --apprx`` belong to ADMMA, which
@@ -90,6 +90,17 @@ def setup_parser(code_names, channel_names, decoder_names):
                    help="QCMSA: frames per wave for lifting sizes up to 32 (P Z <= 64); 0 = as many as the lanes and the LDS take, 1 = one frame "
                         "per workgroup; changes the speed, no result")
     g.add_argument("--osd-depth", type=int, default=64, metavar="N", help="OSD order 1: how many single flips are tried (N >= 0)")
+    g.add_argument("--puncture", default=None, metavar="SPEC",
+                   help="transmission pattern: variables whose codeword bit is NOT sent (the decoder starts them from a prior of 0); comma-separated "
+                        "indices and half-open ranges a:b, e.g. 0:54,600,1100:1200.  The LLR decoders over biawgn / bsc, device noise; the channel "
+                        "parameter stays per transmitted symbol (no rate correction)")
+    g.add_argument("--shorten", default=None, metavar="SPEC",
+                   help="transmission pattern: filler variables known to be 0 and not sent (the decoder starts them from --short-llr; their errors are "
+                        "not counted); same grammar as --puncture")
+    g.add_argument("--puncture-cols", default=None, metavar="LIST",
+                   help="--puncture by whole block columns of a quasi-cyclic code (same grammar, over block columns; Z from --qc-lift, 0 = detected); any decoder")
+    g.add_argument("--shorten-cols", default=None, metavar="LIST", help="--shorten by whole block columns of a quasi-cyclic code")
+    g.add_argument("--short-llr", type=float, default=32.0, metavar="X", help="the prior of a shortened bit (finite, > 0)")
     return bind_parser_common(p)
 
 
