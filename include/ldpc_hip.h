@@ -333,6 +333,46 @@ int ldpc_channel_pattern(int channel, int dtype, double param, const uint8_t* se
 int ldpc_count_errors_pattern(const uint8_t* xhat_dev, const uint8_t* sent_dev, int codeword, const uint8_t* kind_dev, const int32_t* iters_dev,
                               int64_t B, int32_t n, int32_t hist_bins, int64_t* counters_dev, void* stream);
 
+/* ---- Incremental-redundancy HARQ (csrc/ldpc_harq.hip; no upstream counterpart) ---------------------------------
+ * The retransmission loop around a rate-matched code: per-frame soft buffers that survive between decodes, a retransmission for the
+ * frames whose decode failed, noise for the later copies of a bit that is independent of the first, a tally that knows when a frame
+ * leaves.  The schedule is made on the host (ratematch.Harq): the circular buffer is the kind-0 variables of a transmission pattern in
+ * ascending index (kind 1: never in the buffer; kind 2: shortened, as above), transmission t sends E_t buffer positions from its start
+ * k_t, wrapping; E_t beyond the buffer length repeats.  Per transmission the device gets two bytes per variable, cnt_dev [n] (copies of
+ * the variable in this transmission; 0 outside the buffer) and first_dev [n] (copies in all earlier transmissions = the ordinal of this
+ * transmission's first copy); over a whole schedule a variable has at most 255 copies.  No decoder changes.
+ *
+ * ldpc_harq_transmit: LDPC_CH_BIAWGN and LDPC_CH_BSC, dtype fp32 / fp64; one thread = 4 consecutive variables of one output row.
+ * Output row i (0 <= i < B_out) of soft_new_dev [B_out, n] is
+ *     row src_dev[i] of soft_old_dev [old_rows, n]   (src_dev NULL: row i; soft_old_dev NULL: the first transmission, which starts from
+ *                                                      +0.0 for a buffer variable, +0.0 for kind 1 and +short_llr for kind 2)
+ *   + the LLR of every copy of this transmission, added in ascending ordinal r = first .. first + cnt - 1, one addition each in dtype
+ * for the frame  frame0 + orig_dev[i]  (orig_dev NULL: i) whose sent word is row orig_dev[i] of sent_dev [sent_rows, n] (NULL: the
+ * all-`codeword` word).  Copy ordinal r of variable v draws word v % 4 of Philox block v / 4 of the stream word stream_id + (r << 16),
+ * through the Box-Muller pairing and the -(2/sigma^2) y form (BSC: the threshold and +-llr) of ldpc_channel_pattern: r = 0 is that
+ * entry point's draw bit for bit, every later copy is independent of it and still a function of (seed, stream_id, global frame) alone.
+ * A block none of whose four variables has a copy at ordinal r draws nothing for r.  A kind-2 value never changes.  The two buffers
+ * ping-pong (soft_old_dev == soft_new_dev is refused): the gather of the frames that go on rides inside the transmission.  A row whose
+ * src / orig entry lies outside [0, old_rows) / [0, sent_rows) is left unwritten.  The dword / float4 / double2 path under the alignment
+ * rule of ldpc_channel_pattern.  LDPC_E_ARG, each with a sentence that names this entry point: what ldpc_channel_pattern refuses
+ * (LDPC_CH_BEC, LDPC_CH_RAW_OBSERVATION, LDPC_CH_PRIOR_GRID, a short_llr out of range, the all-one word with a shortened variable --
+ * with the same read-back of kind_dev), and stream_id >= 65536 (the ordinal lives in bits 16 and up of the stream word). */
+int ldpc_harq_transmit(int channel, int dtype, double param, const uint8_t* sent_dev, int64_t sent_rows, int codeword, const uint8_t* kind_dev,
+                       const uint8_t* cnt_dev, const uint8_t* first_dev, double short_llr, uint64_t seed, uint64_t stream_id, uint64_t frame0,
+                       const int64_t* src_dev, const int64_t* orig_dev, const void* soft_old_dev, int64_t old_rows, int64_t B_out, int32_t n,
+                       void* soft_new_dev, void* stream);
+/* fail_dev [B] uint8: 1 where xhat_dev [B, n] (bytes, bit 0 counts) leaves some check of the code unsatisfied -- the acknowledgement rule
+ * of a system without a CRC.  One wave per frame; lanes stride over the checks of the code handle's device edge list. */
+int ldpc_harq_syndrome(ldpc_code_t code, const uint8_t* xhat_dev, int64_t B, uint8_t* fail_dev, void* stream);
+/* The tally of transmission t of T (1 <= T <= 16), ACCUMULATED into counters_dev [4 + hist_bins + T + 2].  Every row is one decode attempt:
+ * its iters enter ITER_SUM and the histogram, and tx_bits (E_t) enters sym.  A row LEAVES when fail_dev[i] == 0 or t == T - 1: it adds 1 to
+ * TOT, err > 0 to WEC and err to BEC, err taken over kind < 2 against row orig_dev[i] of sent_dev [sent_rows, n] (orig_dev NULL: row i;
+ * sent_dev NULL: the all-`codeword` word).  Behind the histogram: ack[t] (rows leaving with fail == 0 at transmission t; T words),
+ * undetected (fail == 0 and err > 0), sym.  iters_dev may be NULL.  One wave per row, as ldpc_count_errors_pattern. */
+int ldpc_harq_tally(const uint8_t* xhat_dev, const uint8_t* sent_dev, int64_t sent_rows, int codeword, const uint8_t* kind_dev, const int32_t* iters_dev,
+                    const uint8_t* fail_dev, const int64_t* orig_dev, int64_t B, int32_t n, int32_t hist_bins, int32_t t, int32_t T, int64_t tx_bits,
+                    int64_t* counters_dev, void* stream);
+
 /* ---- Maximum-likelihood decoding of the short codes by codebook search -----------------------------------------
  * Replaces biawgn.ML (src/biawgn.py:66-78), bsc.ML (src/bsc.py:63-75) and bec.ML (src/bec.py:21-36).  `codebook` is
  * Code.cb (src/codes.py:11-14): [K, n] bytes in {0,1}, host pointer, K <= 2^20 words of n <= 64 bits. */

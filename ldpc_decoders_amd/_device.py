@@ -1156,3 +1156,138 @@ class PatternHandle:
             xhat, iters = decode(self.ones_words(nb) if codeword == 1 else sent, first)
             _lib.check(lib.ldpc_count_errors_pattern(xhat.data_ptr(), None if sent is None else sent.data_ptr(), max(codeword, 0), kind.data_ptr(),
                                                      None if iters is None else iters.data_ptr(), nb, n, hist_bins, counters.data_ptr(), st))
+
+
+def _io_dtype(precision):
+    import torch
+
+    return torch.float64 if precision == "f64" else torch.float32
+
+
+def harq_transmit(channel, precision, param, sent, codeword, kind, cnt, first, short_llr, seed, stream_id, frame0, B=None, src=None, orig=None,
+                  soft_old=None):
+    """``ldpc_harq_transmit``: one transmission of a HARQ schedule into a new soft buffer.  ``kind`` / ``cnt`` / ``first`` CUDA uint8 [n] (the
+    pattern and the transmission's row of ``ratematch.Harq.cnt`` / ``.first``); ``sent`` CUDA uint8 [rows, n] or None for the
+    all-``codeword`` word; ``src`` / ``orig`` CUDA int64 [B_out] or None for the identity (the row of ``soft_old`` an output row continues;
+    its frame, and its row of ``sent``, relative to ``frame0``); ``soft_old`` in ``precision`` or None for the first transmission.
+    ``B`` is needed when neither list is given.  -> the new soft buffer [B_out, n]: what the decoder gets as priors."""
+    import torch
+
+    n = kind.shape[0]
+    B_out = int(src.shape[0] if src is not None else orig.shape[0] if orig is not None else B)
+    dt = _io_dtype(precision)
+    for name, idx in (("src", src), ("orig", orig)):
+        if idx is not None and (idx.dtype != torch.int64 or not idx.is_contiguous() or not idx.is_cuda or tuple(idx.shape) != (B_out,)):
+            raise ValueError("%s must be a contiguous CUDA int64 tensor [%d]" % (name, B_out))
+    if soft_old is not None and (soft_old.dtype != dt or not soft_old.is_contiguous() or not soft_old.is_cuda or soft_old.dim() != 2 or soft_old.shape[1] != n):
+        raise ValueError("soft_old must be a contiguous CUDA tensor [rows, %d] of dtype %s" % (n, dt))
+    if sent is not None and (sent.dtype != torch.uint8 or not sent.is_contiguous() or not sent.is_cuda or sent.dim() != 2 or sent.shape[1] != n):
+        raise ValueError("sent must be a contiguous CUDA uint8 tensor [rows, %d]" % n)
+    for tab in (cnt, first):
+        if tab.dtype != torch.uint8 or not tab.is_contiguous() or not tab.is_cuda or tuple(tab.shape) != (n,):
+            raise ValueError("cnt and first must be contiguous CUDA uint8 tensors [%d]" % n)
+    soft = torch.empty((B_out, n), dtype=dt, device=kind.device)
+    st = torch.cuda.current_stream(kind.device).cuda_stream
+    _lib.check(_lib.load().ldpc_harq_transmit(
+        _lib.CHANNEL[channel], _lib.IO_DTYPE[precision], float(param), None if sent is None else sent.data_ptr(), 0 if sent is None else sent.shape[0],
+        int(codeword), kind.data_ptr(), cnt.data_ptr(), first.data_ptr(), float(short_llr), int(seed), int(stream_id), int(frame0),
+        None if src is None else src.data_ptr(), None if orig is None else orig.data_ptr(), None if soft_old is None else soft_old.data_ptr(),
+        0 if soft_old is None else soft_old.shape[0], B_out, n, soft.data_ptr(), st))
+    return soft
+
+
+def harq_syndrome(code_h, xhat):
+    """``ldpc_harq_syndrome``: -> fail CUDA uint8 [B], 1 where ``xhat`` (CUDA uint8 [B, n]) leaves a check of ``code_h`` (a ``CodeHandle``)
+    unsatisfied."""
+    import torch
+
+    if xhat.dtype != torch.uint8 or not xhat.is_contiguous() or not xhat.is_cuda or xhat.dim() != 2 or xhat.shape[1] != code_h.code.n:
+        raise ValueError("xhat must be a contiguous CUDA uint8 tensor [B, %d]" % code_h.code.n)
+    fail = torch.empty((xhat.shape[0],), dtype=torch.uint8, device=xhat.device)
+    _lib.check(_lib.load().ldpc_harq_syndrome(code_h.h, xhat.data_ptr(), xhat.shape[0], fail.data_ptr(), torch.cuda.current_stream(xhat.device).cuda_stream))
+    return fail
+
+
+def harq_tally(xhat, sent, codeword, kind, iters, fail, orig, hist_bins, t, T, tx_bits, counters):
+    """``ldpc_harq_tally``: transmission ``t`` of ``T`` accumulated into ``counters`` (CUDA int64 [4 + hist_bins + T + 2])."""
+    import torch
+
+    B, n = xhat.shape
+    if counters.dtype != torch.int64 or not counters.is_contiguous() or counters.numel() != 4 + int(hist_bins) + int(T) + 2:
+        raise ValueError("counters must be a contiguous CUDA int64 tensor [%d]" % (4 + int(hist_bins) + int(T) + 2))
+    if tuple(fail.shape) != (B,) or fail.dtype != torch.uint8 or (orig is not None and (tuple(orig.shape) != (B,) or orig.dtype != torch.int64)) \
+            or (iters is not None and (tuple(iters.shape) != (B,) or iters.dtype != torch.int32)) or tuple(kind.shape) != (n,) \
+            or (sent is not None and (sent.dim() != 2 or sent.shape[1] != n or not sent.is_contiguous())):
+        raise ValueError("fail uint8 [B], orig int64 [B], iters int32 [B], kind uint8 [n], sent uint8 [rows, n]")
+    _lib.check(_lib.load().ldpc_harq_tally(xhat.data_ptr(), None if sent is None else sent.data_ptr(), 0 if sent is None else sent.shape[0], int(codeword),
+                                           kind.data_ptr(), None if iters is None else iters.data_ptr(), fail.data_ptr(),
+                                           None if orig is None else orig.data_ptr(), B, n, int(hist_bins), int(t), int(T), int(tx_bits),
+                                           counters.data_ptr(), torch.cuda.current_stream(counters.device).cuda_stream))
+
+
+class HarqHandle:
+    """An incremental-redundancy schedule (``ratematch.Harq``) around the handle of an LLR decoder: ``simulate`` in the call shape of
+    ``DecoderHandle.simulate`` with ``extra_counters = T + 2`` more words behind the histogram (``ack[T]``, ``undetected``, ``sym``).  Per
+    chunk of ``inner.words_chunk(channel)`` frames: the sent words as ``PatternHandle.sent_words`` makes them, then for
+    ``t = 0 .. T - 1`` while rows remain: ``ldpc_harq_transmit`` (old soft buffer -> new, gathering the surviving rows) -> the inner
+    handle's ``decode_device(priors, None, ..)`` -> ``ldpc_harq_syndrome`` -> ``ldpc_harq_tally`` -> the ascending list of the failing rows.
+    ``y0`` is None on both channels: a combined buffer has no received word to check at iteration 0.  The length of the survivor list is
+    read on the host once per transmission and chunk -- the next decode needs its batch size.
+
+    Served: ``DecoderHandle`` (SPA, MSA, NMSA, QMSA, LMSA), ``LqmsaHandle``, ``QcHandle``, ``SlqHandle``.  Refused (ValueError, before any
+    device call): everything ``PatternHandle`` refuses, and ``OsdHandle``, whose output is always a codeword."""
+    CHUNK = None  # frames per chunk; None: ``inner.words_chunk(channel)`` (a test forces a small one here)
+
+    def __init__(self, inner, harq, short_llr=32.0):
+        if isinstance(inner, OsdHandle):
+            raise ValueError("OSD always returns a codeword, so the acknowledgement rule (a satisfied syndrome) never asks for a retransmission")
+        self.words = PatternHandle(inner, harq.pattern, short_llr)  # its refusals; the pattern on the device and the sent words
+        self.inner, self.harq, self.pattern, self.short_llr = inner, harq, harq.pattern, self.words.short_llr
+        self.code, self.device, self.precision = self.words.code, self.words.device, self.words.precision
+        self.extra_counters = harq.T + 2
+
+    def tables_device(self):
+        """``harq.cnt`` and ``harq.first`` as CUDA uint8 tensors [T, n] on the handle's device, kept on the handle."""
+        import torch
+
+        if getattr(self, "_tables", None) is None:
+            dev = torch.device("cuda", self.device)
+            self._tables = (torch.from_numpy(self.harq.cnt).to(dev), torch.from_numpy(self.harq.first).to(dev))
+        return self._tables
+
+    def simulate(self, channel, param, codeword, seed, stream_id, frame0, B, max_iter, counters, flags=0, hist_bins=0):
+        """Same call shape as DecoderHandle.simulate; ``counters`` (CUDA int64 [4 + hist_bins + T + 2]) is accumulated into.  TOT / WEC / BEC
+        count FRAMES (once, when they leave); ITER_SUM and the histogram count decode attempts."""
+        import torch
+
+        check_pattern_run(channel, prior_grid=_lib.prior_grid_of_flags(flags))
+        codeword = int(codeword)
+        if codeword not in (-1, 0, 1):
+            raise ValueError("codeword is 0, 1 or -1 (a random codeword per frame)")
+        if codeword == 1 and self.pattern.shortened.size:
+            raise ValueError("the all-one word is no codeword of the shortened code")
+        if not 0 <= int(stream_id) < 65536:
+            raise ValueError("stream_id below 65536: the copy ordinal lives in bits 16 and up of the stream word")
+        if B <= 0:
+            return
+        harq, T, kind = self.harq, self.harq.T, self.words.kind_device()
+        cnt, first = self.tables_device()
+        chunk = int(self.CHUNK or self.inner.words_chunk(channel))
+        last = int(frame0) + int(B)
+        for start in range(int(frame0), last, chunk):
+            rows = min(chunk, last - start)
+            sent = self.words.sent_words(seed, stream_id, start, rows) if codeword == -1 else self.words.ones_words(rows) if codeword == 1 else None
+            src = orig = soft = None
+            for t in range(T):
+                soft = harq_transmit(channel, self.precision, param, sent, 0, kind, cnt[t], first[t], self.short_llr, seed, stream_id, start,
+                                     rows, src, orig, soft)
+                xhat, iters = self.inner.decode_device(soft, None, max_iter, flags)[:2]
+                fail = harq_syndrome(self.inner.code_handle, xhat)
+                harq_tally(xhat, sent, 0, kind, iters, fail, orig, hist_bins, t, T, harq.tx_bits[t], counters)
+                if t == T - 1:
+                    break
+                src = torch.nonzero(fail).squeeze(1)  # ascending
+                rows = int(src.shape[0])  # the one host read per transmission and chunk
+                if rows == 0:
+                    break
+                orig = src if orig is None else orig[src]

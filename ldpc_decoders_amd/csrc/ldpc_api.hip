@@ -15,6 +15,7 @@
 #include "ldpc_bec_ml.hpp"
 #include "ldpc_encode.hpp"
 #include "ldpc_hard.hpp"
+#include "ldpc_harq.hpp"
 #include "ldpc_lqmsa.hpp"
 #include "ldpc_osd.hpp"
 #include "ldpc_qc.hpp"
@@ -1149,6 +1150,31 @@ int ldpc_count_errors_pattern(const uint8_t* xhat_dev, const uint8_t* sent_dev, 
                               int64_t B, int32_t n, int32_t hist_bins, int64_t* counters_dev, void* stream) {
     return guarded("ldpc_count_errors_pattern", [&]() -> int {
         return count_errors_pattern(xhat_dev, sent_dev, codeword, kind_dev, iters_dev, B, n, hist_bins, counters_dev, (hipStream_t)stream);
+    });
+}
+
+int ldpc_harq_transmit(int channel, int dtype, double param, const uint8_t* sent_dev, int64_t sent_rows, int codeword, const uint8_t* kind_dev,
+                       const uint8_t* cnt_dev, const uint8_t* first_dev, double short_llr, uint64_t seed, uint64_t stream_id, uint64_t frame0,
+                       const int64_t* src_dev, const int64_t* orig_dev, const void* soft_old_dev, int64_t old_rows, int64_t B_out, int32_t n,
+                       void* soft_new_dev, void* stream) {
+    return guarded("ldpc_harq_transmit", [&]() -> int {
+        return harq_transmit(channel, dtype, param, sent_dev, sent_rows, codeword, kind_dev, cnt_dev, first_dev, short_llr, seed, stream_id, frame0,
+                             src_dev, orig_dev, soft_old_dev, old_rows, B_out, n, soft_new_dev, (hipStream_t)stream);
+    });
+}
+
+int ldpc_harq_syndrome(ldpc_code_t code, const uint8_t* xhat_dev, int64_t B, uint8_t* fail_dev, void* stream) {
+    return guarded("ldpc_harq_syndrome", [&]() -> int {
+        return harq_syndrome((const Code*)code, xhat_dev, B, fail_dev, (hipStream_t)stream);
+    });
+}
+
+int ldpc_harq_tally(const uint8_t* xhat_dev, const uint8_t* sent_dev, int64_t sent_rows, int codeword, const uint8_t* kind_dev, const int32_t* iters_dev,
+                    const uint8_t* fail_dev, const int64_t* orig_dev, int64_t B, int32_t n, int32_t hist_bins, int32_t t, int32_t T, int64_t tx_bits,
+                    int64_t* counters_dev, void* stream) {
+    return guarded("ldpc_harq_tally", [&]() -> int {
+        return harq_tally(xhat_dev, sent_dev, sent_rows, codeword, kind_dev, iters_dev, fail_dev, orig_dev, B, n, hist_bins, t, T, tx_bits, counters_dev,
+                          (hipStream_t)stream);
     });
 }
 

@@ -5,7 +5,8 @@
 Same positional/flag grammar, same logger names, same JSON result files (see ``utils``), so the arg-lines emitted by
 the reference's ``simulations.py`` run unchanged and ``graph.py`` reads the outputs.  Differences, all additive:
 frames are decoded in batches on the GPU (``--batch`` per round and rank, ``--seed`` for the device noise, ``--precision`` /
-``--backend`` for the kernels, ``--puncture`` / ``--shorten`` for a transmission pattern (``ratematch``), ``--max-frames`` to stop a
+``--backend`` for the kernels, ``--puncture`` / ``--shorten`` for a transmission pattern and ``--harq-bits`` / ``--harq-starts`` for a retransmission schedule over it
+(``ratematch``), ``--max-frames`` to stop a
 parameter whose error rate is too low to reach ``--min-wec``); ``--exact``
 selects the reference-exact mode (host noise, sequential stopping rule, ``--np-seed``); under ``torchrun`` each rank drives one GPU
 and the counters are all-reduced once per round.
@@ -17,20 +18,33 @@ from collections import OrderedDict
 import numpy as np
 
 from . import codes, dist, qc, ratematch, utils
-from ._device import PatternHandle, check_pattern_run
+from ._device import HarqHandle, PatternHandle, check_pattern_run
 from .models import all_decoder_names, models
 from .registry import BY_NAME
 from .montecarlo import DeviceSimulator, run_point_exact
 
 
-def run_ids(args, decoder_id_keys, pattern=None):
+def run_ids(args, decoder_id_keys, pattern=None, harq=None):
     """-> (id keys, their values): what names a run -- its logger, its result file (``utils.Saver``) and the head of that file.  A
-    transmission pattern adds ``puncture`` / ``shorten``; without one the keys are exactly the reference's and the decoder's own."""
+    transmission pattern adds ``puncture`` / ``shorten``, a HARQ schedule ``harq_bits`` / ``harq_starts`` behind them; without either the
+    keys are exactly the reference's and the decoder's own."""
     id_keys = ["channel", "code", "decoder", "codeword", "min_wec"] + list(decoder_id_keys)
     id_val = [vars(args)[key] for key in id_keys]
     if pattern is not None:  # (the canonical spec strings, block columns merged in, so two patterns never share a file; ``args`` stays as parsed)
         id_keys, id_val = id_keys + ["puncture", "shorten"], id_val + [pattern.puncture_spec or "none", pattern.shorten_spec or "none"]
+    if harq is not None:  # (the canonical strings too: ``rv`` is written out as the starts it stands for)
+        id_keys, id_val = id_keys + ["harq_bits", "harq_starts"], id_val + [harq.bits_spec, harq.starts_spec]
     return id_keys, id_val
+
+
+def harq_record(extra, T, c, K):
+    """What a HARQ point adds to its record, from the ``extra`` words of ``DeviceSimulator.run_point`` (ack[T], undetected, sym): ``avg_tx``
+    is decode attempts per frame, ``tput`` the information bits delivered per transmitted symbol, ``(tot - wec) K / sym``."""
+    ack, undetected, sym = [int(a) for a in extra[:T]], int(extra[T]), int(extra[T + 1])
+    tot, wec = int(c["tot"]), int(c["wec"])
+    attempts = sum((tot - sum(ack[:t])) for t in range(T))
+    return [("ack", ack), ("undetected", undetected), ("sym", sym), ("avg_tx", attempts / tot if tot else 0.),
+            ("tput", (tot - wec) * K / sym if sym else 0.)]
 
 
 def test(args, comm=None):
@@ -68,6 +82,9 @@ def test(args, comm=None):
         pattern = ratematch.from_args(args, code)
     except ValueError as e:
         raise SystemExit("--puncture / --shorten: %s" % e)
+    harq_flags = getattr(args, "harq_bits", None) is not None or getattr(args, "harq_starts", None) is not None
+    if harq_flags and pattern is None:  # (a schedule without pattern flags runs over the empty pattern: every bit is in the buffer)
+        pattern = ratematch.Pattern(code.n)
     if pattern is not None:
         if not row.pattern:
             raise SystemExit("--puncture / --shorten: %s takes no transmission pattern; the LLR decoders do (%s)"
@@ -84,7 +101,18 @@ def test(args, comm=None):
         if lost.size:
             raise SystemExit("--puncture: the punctured set contains a stopping set -- no BP decoder can recover variable %d (and %d more)"
                              % (lost[0], lost.size - 1))
-    id_keys, id_val = run_ids(args, dec_fac.id_keys, pattern)
+    # a HARQ schedule over the pattern (--harq-bits / --harq-starts; ratematch.Harq): refused where the pattern is, and for OSD
+    harq = None
+    if harq_flags:
+        if row.group == "post_processing":
+            raise SystemExit("--harq-bits: OSD always returns a codeword, so the acknowledgement rule (a satisfied syndrome) never asks for a retransmission")
+        try:
+            harq = ratematch.harq_from_args(args, pattern)
+        except ValueError as e:
+            raise SystemExit("--harq-bits / --harq-starts: %s" % e)
+        if len(args.params) > 65536:  # (the parameter index is the stream id, and the copy ordinal lives above its 16 bits)
+            raise SystemExit("--harq-bits: at most 65536 parameters in one run")
+    id_keys, id_val = run_ids(args, dec_fac.id_keys, pattern, harq)
     log = logging.getLogger(".".join(utils.strl(id_val)))
     code_n = code.get_n()
     n_counted = code_n if pattern is None else pattern.n_counted  # (a shortened bit is known: its errors are not counted, nor is it a bit of the BER)
@@ -138,6 +166,9 @@ def test(args, comm=None):
                 log.info(", ".join("%s:%s" % (k.upper(), v) for k, v in zip(keys, vals)))
             if hasattr(decoder, "stats"):  # e.g. the ADMM iteration histogram (src/main.py:34)
                 keys.append("dec"), vals.append(decoder.stats())
+            if c.get("harq"):  # a HARQ point: acknowledgements per transmission, undetected errors, symbols, mean transmissions, throughput
+                for k, v in c["harq"]:
+                    keys.append(k), vals.append(v)
             if c.get("capped"):  # an addition: the point was stopped by --max-frames before reaching --min-wec
                 keys.append("capped"), vals.append(True)
             if comm.is_root:
@@ -172,7 +203,9 @@ def test(args, comm=None):
             c = run_point_exact(channel, decoder, x, args.min_wec, chunk=chunk, on_progress=progress, pick_word=pick)
         else:
             handle = decoder.handle if hasattr(decoder, "handle") else decoder.dec.handle
-            if pattern is not None:
+            if harq is not None:
+                handle = HarqHandle(handle, harq, args.short_llr)
+            elif pattern is not None:
                 handle = PatternHandle(handle, pattern, args.short_llr)
             # a decoder that reports statistics (ADMM: iteration histogram, src/main.py:34) gets them from the REDUCED counters, so
             # that `dec` describes the same frames as tot/wec/bec -- the whole job, not rank 0's shard
@@ -187,6 +220,8 @@ def test(args, comm=None):
             sim = DeviceSimulator(handle, args.channel, args.max_iter, args.codeword, args.seed, comm, hist_bins=bins, prior_grid=grid)
             c = sim.run_point(param, stream_id=pi, min_wec=args.min_wec, batch_per_rank=args.batch, on_progress=progress,
                               max_frames=(args.max_frames or None))
+            if harq is not None:
+                c["harq"] = harq_record(c["extra"], harq.T, c, pattern.shortened_code(code)[0].encoder().k)
             if own_hist:
                 inner.iter[:] = 0
                 inner.iter[:bins] = c["hist"]

@@ -77,8 +77,13 @@ class DeviceSimulator:
         self.prior_grid, self.redone = prior_grid, 0
         if prior_grid is not None and (channel != "biawgn" or int(codeword) not in (0, 1)):
             raise ValueError("--prior-grid: min-sum over BI-AWGN with the all-zero / all-one word")
+        # a handle may count more than the common words (``extra_counters``, e.g. _device.HarqHandle: ack[T], undetected, sym): they follow
+        # the histogram in every counter row, are reduced with it, and ``run_point`` returns their sums as ``extra``
+        self.extra = int(getattr(handle, "extra_counters", 0))
+        if self.extra and prior_grid is not None:
+            raise ValueError("--prior-grid: a handle with counters of its own has no exact-in-fp32 mode")
         # exact-in-fp32 rounds carry two more words behind the counters: frames re-decoded in fp64, and a flag "the redo list overflowed"
-        k = 4 + self.hist_bins + (2 if prior_grid is not None else 0)
+        k = 4 + self.hist_bins + self.extra + (2 if prior_grid is not None else 0)
         on_gpu = device == "cuda"
         self._slots = [dict(dev=torch.zeros(k, dtype=torch.int64, device=device),
                             host=torch.zeros(k, dtype=torch.int64).pin_memory() if on_gpu else torch.zeros(k, dtype=torch.int64),
@@ -125,7 +130,7 @@ class DeviceSimulator:
         split over ranks like ``launch_round`` -- as one call with one counter row per round and ONE all-reduce of the whole block; returns a
         ticket for ``finish_rounds``."""
         torch = self.torch
-        k = 4 + self.hist_bins + (2 if self.prior_grid is not None else 0)
+        k = 4 + self.hist_bins + self.extra + (2 if self.prior_grid is not None else 0)
         blk = None
         for b in self._multi:
             if not b["busy"] and b["dev"].shape[0] == rounds:
@@ -227,7 +232,7 @@ class DeviceSimulator:
         round is already running; that round is drained and DISCARDED, so the counters are exactly those of the synchronous loop
         (a function of the round size only, not of the pipeline depth or the number of ranks).  ``on_progress(tot, wec, bec, hist)``
         receives the reduced counters after every counted round (``hist`` = the histogram bins or None)."""
-        tot = np.zeros(4 + self.hist_bins, dtype=np.int64)
+        tot = np.zeros(4 + self.hist_bins + self.extra, dtype=np.int64)
         frame0 = 0
         per_round = int(batch_per_rank) * self.comm.world
         inflight = []
@@ -240,7 +245,7 @@ class DeviceSimulator:
             nonlocal tot
             tot += got
             if on_progress:
-                on_progress(int(tot[0]), int(tot[1]), int(tot[2]), tot[4:].copy() if self.hist_bins else None)
+                on_progress(int(tot[0]), int(tot[1]), int(tot[2]), tot[4:4 + self.hist_bins].copy() if self.hist_bins else None)
 
         count(self.run_round(param, stream_id, frame0, per_round))
         frame0 += per_round
@@ -267,5 +272,7 @@ class DeviceSimulator:
             capped = True  # stopped by max_frames, not by the word-error target
         out = dict(tot=int(tot[0]), wec=int(tot[1]), bec=int(tot[2]), iter_sum=int(tot[3]), capped=capped)
         if self.hist_bins:
-            out["hist"] = tot[4:].tolist()
+            out["hist"] = tot[4:4 + self.hist_bins].tolist()
+        if self.extra:
+            out["extra"] = tot[4 + self.hist_bins:].tolist()
         return out

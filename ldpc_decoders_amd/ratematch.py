@@ -143,6 +143,104 @@ class Pattern:
             raise ValueError("a pattern of %d variables on a code of %d" % (self.n, code.n))
 
 
+HARQ_MAX_TX = 16    # transmissions of one schedule (csrc/ldpc_harq.hpp)
+HARQ_MAX_COPIES = 255  # of one variable over a whole schedule: the tables are bytes
+
+
+def rv_starts(Ncb, T, Z=1):
+    """Starts that step through the buffer in the order 0, 2, 3, 1 quarters: ``floor((0, 2, 3, 1)[t mod 4] * Ncb / 4)`` rounded down to a
+    multiple of ``Z``.  A rule, not a standard's table."""
+    Ncb, T, Z = int(Ncb), int(T), int(Z)
+    if Ncb < 1 or T < 1 or Z < 1:
+        raise ValueError("rv_starts needs Ncb >= 1, T >= 1 and Z >= 1")
+    return tuple(((0, 2, 3, 1)[t % 4] * Ncb // 4) // Z * Z for t in range(T))
+
+
+def _int_list(what, values):
+    try:
+        out = tuple(int(v) for v in values)
+        if any(float(v) != int(v) for v in values):
+            raise ValueError
+    except (TypeError, ValueError):
+        raise ValueError("%s: a list of integers" % what)
+    return out
+
+
+def parse_ints(what, spec):
+    """The command-line form of ``--harq-bits`` / ``--harq-starts``: comma-separated non-negative integers, e.g. ``800,800,400``."""
+    parts = [p.strip() for p in str(spec).split(",")]
+    if not parts or any(not p.isdigit() for p in parts):
+        raise ValueError("%s %r: comma-separated non-negative integers" % (what, spec))
+    return tuple(int(p) for p in parts)
+
+
+class Harq:
+    """``Harq(pattern, tx_bits, starts=None)``: an incremental-redundancy schedule over the circular buffer of ``pattern``.
+
+    The buffer is the variables of kind 0 in ascending index, ``Ncb = pattern.n_tx`` of them (kind 1, punctured, now reads "never in the
+    buffer"; kind 2, shortened, is as before).  Transmission ``t`` of ``T = len(tx_bits)`` (1 .. 16) sends the buffer positions
+    ``(starts[t] + i) mod Ncb`` for ``i = 0 .. tx_bits[t] - 1``; ``tx_bits[t] > Ncb`` repeats bits.  ``starts`` defaults to all 0: Chase
+    combining.  ``cnt`` and ``first``, uint8 [T, n], are what the device reads: the copies of every variable in transmission ``t`` and in
+    all transmissions before it (0 outside the buffer).  ValueError for a variable with more than 255 copies over the schedule."""
+
+    def __init__(self, pattern, tx_bits, starts=None):
+        self.pattern, self.n, self.Ncb = pattern, pattern.n, int(pattern.n_tx)
+        if self.Ncb < 1:
+            raise ValueError("the circular buffer is empty: every variable is punctured or shortened")
+        self.tx_bits = _int_list("tx_bits", tx_bits)
+        self.T = len(self.tx_bits)
+        if not 1 <= self.T <= HARQ_MAX_TX or min(self.tx_bits) < 1:
+            raise ValueError("a schedule has 1 .. %d transmissions of at least one bit each" % HARQ_MAX_TX)
+        self.starts = (0,) * self.T if starts is None else _int_list("starts", starts)
+        if len(self.starts) != self.T or min(self.starts) < 0 or max(self.starts) >= self.Ncb:
+            raise ValueError("one start per transmission, each inside the buffer 0 .. %d" % (self.Ncb - 1))
+        self.buffer = np.flatnonzero(pattern.kind == SENT).astype(np.int64)
+        pos = np.arange(self.Ncb, dtype=np.int64)
+        total = np.zeros(self.Ncb, dtype=np.int64)
+        cnt = np.zeros((self.T, self.n), dtype=np.int64)
+        first = np.zeros((self.T, self.n), dtype=np.int64)
+        for t, (E, k) in enumerate(zip(self.tx_bits, self.starts)):
+            d = (pos - k) % self.Ncb
+            c = np.where(d >= E, 0, 1 + (E - 1 - d) // self.Ncb)
+            cnt[t, self.buffer], first[t, self.buffer] = c, total
+            total += c
+        if total.max() > HARQ_MAX_COPIES:
+            raise ValueError("variable %d is sent %d times over the schedule; the tables hold at most %d copies"
+                             % (self.buffer[int(total.argmax())], total.max(), HARQ_MAX_COPIES))
+        self.cnt, self.first = cnt.astype(np.uint8), first.astype(np.uint8)
+
+    def copies(self, t, p):
+        """Copies of buffer position ``p`` in transmission ``t``."""
+        d = (int(p) - self.starts[t]) % self.Ncb
+        return 0 if d >= self.tx_bits[t] else 1 + (self.tx_bits[t] - 1 - d) // self.Ncb
+
+    def first_copy(self, t, p):
+        """Copies of buffer position ``p`` in the transmissions before ``t``: the ordinal of the first copy of transmission ``t``."""
+        return sum(self.copies(u, p) for u in range(t))
+
+    @property
+    def bits_spec(self):
+        return ",".join(str(E) for E in self.tx_bits)
+
+    @property
+    def starts_spec(self):
+        return ",".join(str(k) for k in self.starts)
+
+
+def harq_from_args(args, pattern):
+    """The schedule of a command line (``--harq-bits E0,E1,..`` with ``--harq-starts k0,k1,..`` or ``rv``) over ``pattern``, or None without
+    ``--harq-bits``.  ``rv`` takes Z from ``--qc-lift`` (1 when that is 0)."""
+    bits, starts = getattr(args, "harq_bits", None), getattr(args, "harq_starts", None)
+    if bits is None:
+        if starts is not None:
+            raise ValueError("--harq-starts needs --harq-bits")
+        return None
+    bits = parse_ints("--harq-bits", bits)
+    if starts is not None:
+        starts = rv_starts(pattern.n_tx, len(bits), getattr(args, "qc_lift", 0) or 1) if starts == "rv" else parse_ints("--harq-starts", starts)
+    return Harq(pattern, bits, starts)
+
+
 def from_args(args, code):
     """The pattern of a command line (``--puncture --shorten --puncture-cols --shorten-cols``), or None when none of them is given.
     The block-column flags take Z from ``--qc-lift`` / ``qc.resolve``."""

@@ -1,7 +1,7 @@
 """CLI flags, logging and the JSON result store -- mirror of the reference's ``src/utils.py:21-68,118-140``.
 
 The argument grammar (positional ``channel code decoder`` + ``--codeword --min-wec --params --max-iter ...``) and
-the result files (``<channel>-<code>-<decoder>-<codeword>-<min_wec>-<max_iter>.json``; NMSA, LMSA: ``...-<max_iter>-<msa_scale>-<msa_offset>.json``; QMSA, LQMSA, SLQMSA: ``...-<max_iter>-<msa_bits>-<msa_frac_bits>-<msa_scale>-<msa_offset>.json``; QCMSA: the same followed by ``-<qc_lift>``; OSD: ``...-<max_iter>-<msa_scale>-<msa_offset>-<osd_order>-<osd_depth>.json``; GALB: ``...-<max_iter>-<gal_threshold>.json``; under a transmission pattern (``--puncture`` / ``--shorten``) every name is followed by ``-<puncture>-<shorten>``; with the id keys first, then
+the result files (``<channel>-<code>-<decoder>-<codeword>-<min_wec>-<max_iter>.json``; NMSA, LMSA: ``...-<max_iter>-<msa_scale>-<msa_offset>.json``; QMSA, LQMSA, SLQMSA: ``...-<max_iter>-<msa_bits>-<msa_frac_bits>-<msa_scale>-<msa_offset>.json``; QCMSA: the same followed by ``-<qc_lift>``; OSD: ``...-<max_iter>-<msa_scale>-<msa_offset>-<osd_order>-<osd_depth>.json``; GALB: ``...-<max_iter>-<gal_threshold>.json``; under a transmission pattern (``--puncture`` / ``--shorten``) every name is followed by ``-<puncture>-<shorten>``, under a HARQ schedule (``--harq-bits``) by ``-<puncture>-<shorten>-<harq_bits>-<harq_starts>``; with the id keys first, then
 ``tot wec wer bec ber`` as ``{str(param): value}``) are what ``simulations.py`` / ``run_sims.sh`` emit and what
 ``graph.py`` reads upstream (src/graph.py:25-58), so flag names, defaults and the file layout are kept; the help texts are
 this build's own.  ``--mu --eps --allow-pseudo`` configure the ADMM decoder; ``--layers --train --apprx`` belong to ADMMA, which
@@ -101,6 +101,14 @@ def setup_parser(code_names, channel_names, decoder_names):
                    help="--puncture by whole block columns of a quasi-cyclic code (same grammar, over block columns; Z from --qc-lift, 0 = detected); any decoder")
     g.add_argument("--shorten-cols", default=None, metavar="LIST", help="--shorten by whole block columns of a quasi-cyclic code")
     g.add_argument("--short-llr", type=float, default=32.0, metavar="X", help="the prior of a shortened bit (finite, > 0)")
+    g.add_argument("--harq-bits", default=None, metavar="E0,E1,..",
+                   help="incremental-redundancy HARQ over the transmission pattern (the empty one without pattern flags): the circular buffer is "
+                        "the sent variables in ascending index, transmission t sends E_t buffer positions from its start, wrapping (E_t beyond "
+                        "the buffer repeats); a frame is retransmitted, and its LLRs combined, until its decisions satisfy every check; 1..16 "
+                        "transmissions.  Result files gain ack, undetected, sym, avg_tx and tput; the channel parameter stays per transmitted symbol")
+    g.add_argument("--harq-starts", default=None, metavar="k0,k1,..|rv",
+                   help="--harq-bits: where in the buffer each transmission begins (default: all 0, Chase combining); rv = 0, 2, 3, 1 quarters of "
+                        "the buffer in turn, rounded down to a multiple of --qc-lift")
     return bind_parser_common(p)
 
 
